@@ -146,6 +146,8 @@ def parse():
                          "minkunet_mk34_cr10_fsa.yaml:14,34, is 16 at bs 6)")
     ap.add_argument("--image-layout", default=None, choices=["nhwc", "nchw"],
                     help="tiaf: memory format of UNet2D and form of the image gather (default: taseg_amd.options.image_layout = nhwc)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last one computed to DIR/<name>.npy (float32 / float64, <= 64 MB)")
     ap.add_argument("--no-secondary", action="store_true",
                     help="skip the short runs of the other workloads (minkunet_ms, --amp, nuscenes_ms --amp) that the "
                          "default N=1 run appends as `secondary`")
@@ -741,6 +743,37 @@ def build_roofline(prof, amp, bracket_us):
     return roof
 
 
+DUMP_MAX_BYTES = 60 * 2 ** 20      # --dump-outputs: array data of one dump (under 64 MB with the .npy headers)
+
+
+def dump_outputs(out_dir, arrays, seed=0):
+    """--dump-outputs DIR: {name: array} -> DIR/<name>.npy, float64 for float64 and integer arrays, float32 otherwise.  Smallest
+    first, each array gets an even share of what is left of DUMP_MAX_BYTES; a larger one is replaced by a fixed, seeded sample of
+    its flattened elements (positions ascending) - the same positions on every run with the same arguments."""
+    os.makedirs(out_dir, exist_ok=True)
+    left = DUMP_MAX_BYTES
+    items = sorted(((k, np.asarray(v)) for k, v in arrays.items()), key=lambda kv: kv[1].size)
+    for i, (name, a) in enumerate(items):
+        dt = np.float64 if a.dtype == np.float64 or a.dtype.kind in "iub" else np.float32
+        cap = left // (len(items) - i) // np.dtype(dt).itemsize
+        if a.size > cap:
+            pos = np.sort(np.random.default_rng(seed).choice(a.size, cap, replace=False))
+            a = a.reshape(-1)[pos]
+        a = np.ascontiguousarray(a, dtype=dt)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        left -= a.nbytes
+    note(f"outputs of the last timed step: {len(items)} arrays in {out_dir}")
+
+
+def train_step_outputs(model, loss):
+    """what a caller of the timed train step holds after it: the step's loss and the model state it left (parameters, BatchNorm
+    running statistics) - every floating tensor of the state dict flattened in state-dict order, plus each tensor's L2 norm"""
+    state = [v.detach() for v in model.state_dict().values() if v.is_floating_point()]
+    return {"loss": np.float64(float(loss.detach().float())),
+            "state": np.concatenate([v.float().reshape(-1).cpu().numpy() for v in state]),
+            "state_norms": np.array([float(v.double().norm()) for v in state], dtype=np.float64)}
+
+
 def secondary_runs(steps=30, warmup=8, only=None):
     """Short runs of the other BASELINE configurations (4-scan TFA, AMP, nuScenes shape + AMP) as CHILD processes after
     the headline measurement, so that the driver's default invocation observes them too.  Each entry is the child's
@@ -882,6 +915,9 @@ def eval_run(args):
     out = passes(args.steps)                     # K passes issued AND collected inside the timed region
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if args.dump_outputs:                        # (before the passes below: the arrays are views of the tail's host buffers)
+        dump_outputs(args.dump_outputs, {k: np.concatenate(out[k]) for k in ("point_predict", "point_predict_logits", "point_labels")
+                                         if out[k]})
     # per-launch events around the convolution kernels of a few more passes AFTER the timed region (the roofline of the line)
     roofline = None
     if not args.no_kernel_events:
@@ -1211,6 +1247,8 @@ def main():
         t = torch.tensor([dt], device="cuda", dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if args.dump_outputs and rank == 0:       # before anything below runs the model again (TIAF phase table, image gathers)
+        dump_outputs(args.dump_outputs, train_step_outputs(model, loss))
     ms_per_step = 1e3 * dt / args.steps
     value = args.batch * world * args.steps / dt
     bus = None
