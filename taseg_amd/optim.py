@@ -18,7 +18,7 @@ import torch
 
 from . import _lib as L
 from . import planes as _planes
-from .parallel import GradBucketReducer
+from .parallel import GradBucketReducer, slot_view
 
 __all__ = ["FlatSGD"]
 
@@ -33,14 +33,17 @@ class FlatSGD:
         dev = self.reducer.buckets[0]["flat"].device
         L.require_device(self.reducer.buckets[0]["flat"])
         # parameters move into flat buckets too (p.data becomes a view): the update is one launch per bucket
+        names = {id(p): n for n, p in model.named_parameters()}
+        self._aliases = []              # (parameter, name, address of its slice): step() refuses a rebound parameter
         for b in self.reducer.buckets:
             flat = torch.zeros_like(b["flat"])
-            for p, off in zip(b["params"], b["offsets"]):      # same (64-byte aligned) layout as the gradient bucket
+            for p, off in zip(b["params"], b["offsets"]):      # same (64-byte aligned) layout and strides as the gradient bucket
                 if p.dtype != torch.float32:
                     raise TypeError("FlatSGD keeps fp32 master parameters")
-                view = flat[off:off + p.numel()].view_as(p)
+                view = slot_view(flat, off, p)
                 view.copy_(p.data)
                 p.data = view
+                self._aliases.append((p, names.get(id(p), "?"), view.data_ptr()))
             b["pflat"], b["mflat"] = flat, torch.zeros_like(flat)
         self.state = torch.zeros(8, dtype=torch.float32, device=dev)
         self.state[0] = init_scale if amp else 1.0
@@ -60,7 +63,16 @@ class FlatSGD:
                 p.grad = None
                 p._taseg_dest_claimed = False
 
+    def check_aliases(self):
+        """raises unless every parameter still IS its slice of the flat buckets: a `p.data = ...` after construction (Module.to,
+        load_state_dict(assign=True), ...) leaves a tensor the flat update never writes - the parameter would silently freeze"""
+        for p, name, ptr in self._aliases:
+            if p.data_ptr() != ptr:
+                raise RuntimeError(f"FlatSGD: parameter '{name}' no longer aliases its slice of the flat bucket (its .data was "
+                                   "rebound after the optimizer was built); the update would not reach it")
+
     def step(self):
+        self.check_aliases()
         self.reducer.finish()                         # gradients sit in the flat buckets (reduced over ranks)
         lib, st = L.load(), L.stream()
         for b in self.reducer.buckets:

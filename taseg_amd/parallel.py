@@ -14,7 +14,7 @@ import torch.distributed as dist
 from .options import options
 
 __all__ = ["env_rank", "init_distributed", "shard_seeds", "wrap_ddp", "reduce_max", "reduce_confusion",
-           "GradBucketReducer"]
+           "GradBucketReducer", "slot_view"]
 
 
 _grad_epoch = 0
@@ -92,6 +92,14 @@ def reduce_confusion(hist: torch.Tensor) -> torch.Tensor:
     return hist
 
 
+def slot_view(flat, off, p):
+    """p's slot in a flat bucket: flat[off:off + p.numel()] as a tensor of p's shape AND p's dense strides (a channels-last
+    Conv2d weight stays channels-last).  The parameter and gradient buckets are viewed through this one function: the flat
+    update pairs element i of one with element i of the other, so both views must lay the tensor out alike."""
+    stride = torch.empty_like(p, device="meta").stride()     # p's own strides when p is dense, else dense ones in p's order
+    return flat[off:off + p.numel()].as_strided(p.shape, stride)
+
+
 class GradBucketReducer:
     """Gradient averaging over ranks in a few flat buckets, overlapped with backward - what DDP's reducer does,
     minus its per-parameter device copies.  With `gradient_as_bucket_view` DDP copies every freshly produced
@@ -163,7 +171,7 @@ class GradBucketReducer:
         n_flags = -(-len(params) // self.ALIGN) * self.ALIGN
         flat_all = torch.zeros(off + n_flags, dtype=first.dtype, device=first.device)
         flat, flags = flat_all[:off], flat_all[off:off + len(params)]
-        views = [flat[o:o + p.numel()].view_as(p) for o, p in zip(offsets, params)]
+        views = [slot_view(flat, o, p) for o, p in zip(offsets, params)]
         import weakref
         bucket_index = len(self.buckets)
         for i, (p, v) in enumerate(zip(params, views)):

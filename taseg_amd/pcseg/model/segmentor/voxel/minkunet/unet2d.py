@@ -443,15 +443,23 @@ class UNet2D(nn.Module):
         self.up3 = UpBlock(cs[6], cs[7], 0.2, mid_filters=cs[6] // 4 + cs[2])
         self.up4 = UpBlock(cs[7], cs[8], 0.2, drop_out=False, mid_filters=cs[7] // 4 + cs[1])
         self.classifier = nn.Sequential(nn.Conv2d(cs[8], num_class, kernel_size=1, stride=1))
-        self._layout = None
+
+    def _apply(self, fn, *args, **kwargs):
+        """Module._apply - behind .cuda(), .to(device), .half(), ... - plus the memory format of options.image_layout for the
+        parameters of a module on the device, in the SAME pass that rebinds them anyway.  An optimizer is built on the moved module
+        (FlatSGD, taseg_amd/optim.py, makes every p.data a view into its flat buckets); nothing after that - forward included -
+        reallocates a parameter (a weight already in the format is left as it is).  On the host the parameters keep the plain
+        contiguous format of the reference's own modules."""
+        out = super()._apply(fn, *args, **kwargs)
+        if any(p.is_cuda for p in self.parameters()):
+            want = self._set_layout()
+            super()._apply(lambda t: t.contiguous(memory_format=want) if t.dim() == 4 else t)
+        return out
 
     def _set_layout(self):
-        """parameters in the memory format of options.image_layout (once; the Parameter objects stay)"""
-        want = torch.channels_last if options.image_layout == "nhwc" else torch.contiguous_format
-        if self._layout is not want:
-            self.to(memory_format=want)
-            self._layout = want
-        return want
+        """the memory format of options.image_layout, for the activations.  Never reallocates a parameter: they take the format when
+        the module moves to the device (_apply); a later change of the option converts the activations only"""
+        return torch.channels_last if options.image_layout == "nhwc" else torch.contiguous_format
 
     # the dense network in three pieces around the two maps the hand-over reads (unet2d.py:155-172); a test can stand in for them
     def _encode(self, x):

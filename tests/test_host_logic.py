@@ -433,3 +433,61 @@ def test_a_model_with_a_reducer_still_pickles_and_finds_its_reducer():
     red.buckets[0]["launched"] = True
     with pytest.raises(RuntimeError, match="already launched"):
         red.check_open([lin.weight])
+
+
+@pytest.mark.parametrize("layout", ["nhwc", "nchw"])
+def test_unet2d_forward_and_host_conversions_never_reallocate_a_parameter(layout):
+    """On the host UNet2D's convolution weights keep the reference's contiguous format (they take options.image_layout's when the
+    module moves to the device - UNet2D._apply, in the pass that rebinds them anyway); host-side conversions (.float(), .cpu()), the
+    layout step of forward and a whole pass of the dense network in either activation format leave every parameter's storage where it
+    was - an optimizer that made p.data a view of its flat buckets (taseg_amd/optim.py) keeps updating them."""
+    from taseg_amd.options import options
+    from taseg_amd.pcseg.model.segmentor.voxel.minkunet.unet2d import UNet2D
+    fmt = torch.channels_last if layout == "nhwc" else torch.contiguous_format
+    other = "nchw" if layout == "nhwc" else "nhwc"
+    with options.override(image_layout=layout):
+        net = UNet2D()
+    convs = [(n, p) for n, p in net.named_parameters() if p.dim() == 4]
+    assert len(convs) == 24
+    for n, p in convs:
+        assert p.is_contiguous(), (n, p.stride())
+    ptrs = {n: (p.data_ptr(), p.stride()) for n, p in net.named_parameters()}
+    with options.override(image_layout=layout):
+        net.float().cpu().train()
+        assert net._set_layout() is fmt
+        x = torch.randn(2, 3, 16, 32).contiguous(memory_format=net._set_layout())
+        x5, skips = net._encode(x)
+        net.classifier(net._decode_u4(net._decode_u2(x5, skips), skips)).float().sum().backward()
+    with options.override(image_layout=other):
+        assert net._set_layout() is not fmt
+    assert {n: (p.data_ptr(), p.stride()) for n, p in net.named_parameters()} == ptrs
+    assert all(p.grad is not None for _, p in convs)
+
+
+def test_grad_buckets_view_each_parameter_with_its_own_strides():
+    """GradBucketReducer's slot of a channels-last Conv2d weight is a channels-last view (the parameter buckets of FlatSGD are built by
+    the same parallel.slot_view: the flat update pairs element i of both); the gradients land in the slots with their values"""
+    from taseg_amd import parallel as P
+    torch.manual_seed(3)
+    net = torch.nn.Sequential(torch.nn.Conv2d(5, 8, 3, padding=1), torch.nn.Conv2d(8, 4, 1), torch.nn.Linear(6, 3))
+    net[0].to(memory_format=torch.channels_last)
+    ref = [p.detach().clone() for p in net.parameters()]
+    red = P.GradBucketReducer(net, bucket_mb=1e-4)
+    for b in red.buckets:
+        for p, v, off in zip(b["params"], b["views"], b["offsets"]):
+            assert v.shape == p.shape and v.stride() == p.stride(), (tuple(p.shape), v.stride(), p.stride())
+            assert v.data_ptr() == b["flat"].data_ptr() + 4 * off
+    assert net[0].weight.stride() == (45, 1, 15, 5)
+    x = torch.randn(2, 5, 4, 6)
+    net(x).square().sum().backward()
+    red.finish()
+    twin = torch.nn.Sequential(torch.nn.Conv2d(5, 8, 3, padding=1), torch.nn.Conv2d(8, 4, 1), torch.nn.Linear(6, 3))
+    with torch.no_grad():
+        for q, r in zip(twin.parameters(), ref):
+            q.copy_(r)
+    twin(x).square().sum().backward()
+    for b in red.buckets:
+        for p, v in zip(b["params"], b["views"]):
+            assert p.grad.data_ptr() == v.data_ptr()
+    for p, q in zip(net.parameters(), twin.parameters()):
+        assert torch.allclose(p.grad, q.grad, rtol=1e-6, atol=1e-6)
