@@ -1,7 +1,11 @@
 """bench.py - scans/sec of the TASeg hot path (train step: rulebook construction + MinkUNet forward +
 CE/Lovasz loss + backward + SGD step) on synthetic SemanticKITTI-shaped scans, one process per GPU.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload minkunet|minkunet_ms]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload minkunet|minkunet_ms] [--full]
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line.  --full adds what takes runs of
+its own: the CPU baseline legs and the `secondary` child runs of the default line, the TIAF image-gather roofline and phase table,
+the evaluation roofline and the gradient all-reduce bandwidth of N > 1.
 
 N > 1: one rank per GPU over RCCL (the reference's launch, R/dist_train.sh:17-19 + R/train.py:247-251).  The driver
 starts the ranks through torch.distributed.run; run by hand as `python bench.py --gpus N` (WORLD_SIZE unset) this
@@ -33,7 +37,7 @@ EVENT_EVERY = 20            # per-launch HIP events bracket the conv kernels of 
 
 
 def note(msg):
-    """progress line on stderr (a default run takes minutes: main measurement, CPU baseline legs, side runs)"""
+    """progress line on stderr (a --full run takes minutes: main measurement, CPU baseline legs, side runs)"""
     print(f"[bench {time.strftime('%H:%M:%S')}] {msg}", file=sys.stderr, flush=True)
 
 
@@ -150,7 +154,11 @@ def parse():
                     help="after the timed steps write what the last one computed to DIR/<name>.npy (float32 / float64, <= 64 MB)")
     ap.add_argument("--no-secondary", action="store_true",
                     help="skip the short runs of the other workloads (minkunet_ms, --amp, nuscenes_ms --amp) that the "
-                         "default N=1 run appends as `secondary`")
+                         "default N=1 line appends as `secondary` under --full")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own after the timed steps: the CPU baseline and the `secondary` "
+                         "child runs (default N=1 line), the TIAF image-gather roofline and phase table, the evaluation "
+                         "roofline, the gradient all-reduce bandwidth (N > 1)")
     return ap.parse_args()
 
 
@@ -794,7 +802,7 @@ def secondary_runs(steps=30, warmup=8, only=None):
     for extra, steps, warmup in runs:
         note("secondary run: " + " ".join(extra))
         cmd = [sys.executable, os.path.abspath(__file__), "--steps", str(steps), "--warmup", str(warmup), "--no-cpu-baseline",
-               "--no-secondary"] + extra           # per-launch events on the first timed step: every entry has its roofline
+               "--no-secondary", "--full"] + extra     # per-launch events on the first timed step: every entry has its roofline
         entry = {"args": " ".join(extra)}
         try:
             r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
@@ -918,9 +926,9 @@ def eval_run(args):
     if args.dump_outputs:                        # (before the passes below: the arrays are views of the tail's host buffers)
         dump_outputs(args.dump_outputs, {k: np.concatenate(out[k]) for k in ("point_predict", "point_predict_logits", "point_labels")
                                          if out[k]})
-    # per-launch events around the convolution kernels of a few more passes AFTER the timed region (the roofline of the line)
+    # --full: per-launch events around the convolution kernels of a few more passes AFTER the timed region (the roofline of the line)
     roofline = None
-    if not args.no_kernel_events:
+    if args.full and not args.no_kernel_events:
         B.profile_begin(expected_launches=800)
         passes(3)
         torch.cuda.synchronize()
@@ -988,7 +996,7 @@ def main():
 
     B.set_conv_impl(args.conv_impl)
     if args.workload == "tiaf":
-        args.no_kernel_events = True      # (its roofline entry is the image gather's, measured after the timed steps)
+        args.no_kernel_events = True      # (its roofline entry is the image gather's, measured after the timed steps under --full)
     nusc = args.workload == "nuscenes_ms"
     tiaf = args.workload == "tiaf"
     kd = args.workload == "kd"
@@ -1252,7 +1260,7 @@ def main():
     ms_per_step = 1e3 * dt / args.steps
     value = args.batch * world * args.steps / dt
     bus = None
-    if dist is not None and world > 1:
+    if args.full and dist is not None and world > 1:
         # the achieved bus bandwidth of the step's one exchange, the gradient all-reduce, measured
         # on its own after the timed region (a flat fp32 buffer of the model's size, bus = 2 (n - 1) / n * bytes / t)
         n_par = sum(p.numel() for p in model.parameters())
@@ -1270,7 +1278,7 @@ def main():
                "bus_GBps": 2 * (world - 1) / world * 4 * n_par / float(t.item()) / 1e9}
         del buf
 
-    dog.stop()                                # what follows is rank 0's reporting (CPU baseline legs, side runs: minutes, own limits)
+    dog.stop()                                # what follows is rank 0's reporting (--full: CPU baseline legs, side runs: minutes, own limits)
     if rank == 0:
         prof = summarise_profile(records, profiled_steps)
         roofline = build_roofline(prof, args.amp, bracket_us)
@@ -1313,6 +1321,8 @@ def main():
             from taseg_amd.options import options as _opts
             line["config"]["fov_points_per_step_per_gpu"] = n_fov[0]
             line["config"]["image_layout"] = _opts.image_layout
+        if tiaf and args.full:
+            from taseg_amd.options import options as _opts
             # (a FRESH batch: the forward pass of a step overwrites the FOV cloud's feature matrix, pixel columns included)
             gat = tiaf_gather_roofline(model, make_batch(), _opts.image_layout, torch.float16 if args.amp else torch.float32)
             line["image_gather"] = gat
@@ -1329,13 +1339,14 @@ def main():
                 line["phases_ms"] = tiaf_phase_table(model, net, opt, make_batch, args.amp)
         if kd:
             line["config"]["teacher_voxels_per_step_per_gpu"] = nvox_gt[0]
-        if world == 1 and not args.no_cpu_baseline and not nusc and not tiaf and not kd:      # cpu_baseline is defined on the KITTI-shaped scan
+        # cpu_baseline is defined on the KITTI-shaped scan
+        if args.full and world == 1 and not args.no_cpu_baseline and not nusc and not tiaf and not kd:
             line["cpu_baseline"] = cpu_baseline(args, name, cfg.IN_FEATURE_DIM)
             if line["cpu_baseline"]["value"]:
                 line["gpu_over_cpu"] = value / line["cpu_baseline"]["value"]
-        plain = (world == 1 and not args.force_dist and args.workload == "minkunet" and not args.amp and args.conv_impl == 0
-                 and not args.torch_optim and args.batch == 2 and args.points == 120000)
-        if plain and not args.no_secondary:
+        default_line = (world == 1 and not args.force_dist and args.workload == "minkunet" and not args.amp and args.conv_impl == 0
+                        and not args.torch_optim and args.batch == 2 and args.points == 120000)
+        if args.full and default_line and not args.no_secondary:
             line["secondary"] = secondary_runs()
         import ctypes
         ctypes.CDLL(None).fflush(None)      # RCCL prints its version banner through C stdio: flush it BEFORE the line

@@ -178,11 +178,11 @@ def test_bench_gpus_flag():
 
 def test_bench_two_ranks_rehearsal_on_one_device():
     """`bench.py --gpus 2` starts its own two ranks and reports n_gpus 2 (gloo transport, both ranks on this card: a
-    rehearsal of the launch + reducer + SyncBatchNorm path, not a performance number)"""
+    rehearsal of the launch + reducer + SyncBatchNorm path, not a performance number); --full adds the all-reduce bandwidth"""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update(TASEG_BENCH_SHARE_DEVICE="1", TASEG_DIST_BACKEND="gloo")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                        "--points", "30000", "--no-cpu-baseline", "--no-kernel-events"], env=env, capture_output=True, text=True,
+                        "--points", "30000", "--no-cpu-baseline", "--no-kernel-events", "--full"], env=env, capture_output=True, text=True,
                        timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

@@ -10,14 +10,14 @@ export TMPDIR=/tmp
 say() { echo "[collect $(date +%H:%M:%S)] $*"; }
 if [ "$PART" != side ]; then
 say "default bench line"
-python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err
+python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err
 RP="rocprofv3 --kernel-trace --stats --output-format csv"
 echo "{" > $OUT/launches.json
 # one traced run: kernel statistics, per-queue busy time inside the timed steps, launches per step
 trace() {   # tag, launches key, marker regex, steps, bench arguments...
   tag=$1; key=$2; marker=$3; steps=$4; shift 4
   say "trace $tag"
-  $RP -d $OUT/trace_$tag -- python3 bench.py "$@" --no-cpu-baseline --no-secondary > $OUT/bench_${tag}_under_rocprof.json 2> $OUT/trace_$tag.err
+  $RP -d $OUT/trace_$tag -- python3 bench.py "$@" --full --no-cpu-baseline --no-secondary > $OUT/bench_${tag}_under_rocprof.json 2> $OUT/trace_$tag.err
   python tools/kstats.py $OUT/trace_$tag $steps 45 > $OUT/kstats_$tag.txt
   python tools/stream_busy.py $OUT/trace_$tag $steps "$marker" > $OUT/busy_$tag.txt
   python tools/fill_sources.py $OUT/trace_$tag $steps "$marker" > $OUT/fills_$tag.txt 2>&1 || true
@@ -62,7 +62,7 @@ fi
 if [ "$PART" = main ]; then exit 0; fi
 say "side lines"
 for w in "--eval" "--eval --amp" "--workload minkunet_ms" "--amp" "--workload nuscenes_ms --amp" "--workload nuscenes_ms" "--batch 8" "--batch 8 --amp" "--force-dist" "--workload kd" "--workload tiaf --amp" "--workload tiaf" "--batch 12 --amp" "--workload minkunet_ms --history 16 --batch 6 --amp"; do
-  tag=$(echo $w | tr -d ' -'); say "bench $w"; python bench.py --steps 30 --warmup 5 $w --no-cpu-baseline --no-secondary > $OUT/bench_$tag.json 2> /dev/null; done
+  tag=$(echo $w | tr -d ' -'); say "bench $w"; python bench.py --steps 30 --warmup 5 $w --full --no-cpu-baseline --no-secondary > $OUT/bench_$tag.json 2> /dev/null; done
 say "2-D convolution kernels: probe, per-layer table, SQ counters"
 python tools/conv2d_probe.py > $OUT/conv2d_probe.txt 2> /dev/null
 python tools/unet2d_layers.py > $OUT/unet2d_layers.txt 2> /dev/null || true
