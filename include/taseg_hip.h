@@ -902,6 +902,21 @@ int ts_stage_layout(const float *cur, const int64_t *cur_lab, const int64_t *cur
 int ts_stage_split_voxels(const int32_t *coords4, const int32_t *index, int64_t m, const int32_t *inverse,
                           const int64_t *row_sample, int64_t n, int32_t n_samples, int32_t *vox, int64_t *start, int32_t *offset,
                           int64_t *inverse_local, ts_stream_t stream);
+/* Point augmentation of the data stage (tools/utils/common/seg_utils.py:102-166 aug_points_ms, :43-100 aug_points; applied by
+ * semantickitti_voxel_ms.py:90-119 before the clamp and both voxelisations): the xyz columns of points [n, point_stride] float32,
+ * the other columns passed through; sample_idx [n] int32 or NULL (= 0) selects one of n_samples parameter records of
+ * TS_AUG_RECORD doubles { c, s, scale, tx, ty, tz, bits, flip } (c = cos theta, s = sin theta from the host):
+ *   bit 1   X = x*c + y*(-s) ; Y = x*s + y*c ; Z = z        (np.dot(xyz, rot_mat): dgemm's fused-multiply-add chain in k
+ *                                                             order, X = fma(z, 0, fma(y, -s, x*c)) ... as ts_fuse_sweeps)
+ *   bit 2   (X, Y, Z) *= scale                               (bit 16 too: in float32, numpy's float32 array * Python float when
+ *                                                             the cloud has not been rotated into float64 before)
+ *   bit 4   flip 1: X = -X ; 2: Y = -Y ; 3: both
+ *   bit 8   (X, Y, Z) += (tx, ty, tz)
+ * in float64 with ONE rounding to float32 at the end; a step whose bit is clear is skipped, a record without bits returns the
+ * input bit for bit.  out == points (in place) or a non-overlapping [n, point_stride] array. */
+#define TS_AUG_RECORD 8
+int ts_stage_augment(const float *points, int64_t n, int32_t point_stride, const int32_t *sample_idx, const double *params,
+                     int32_t n_samples, float *out, ts_stream_t stream);
 size_t ts_quantize_workspace_bytes(int64_t n);
 int ts_sparse_quantize(const int32_t *coords, int64_t n, int32_t *out_index, int32_t *out_inverse,
                        int32_t *out_count, void *ws, size_t ws_bytes, ts_stream_t stream);

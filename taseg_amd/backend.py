@@ -1237,6 +1237,34 @@ def stage_keep_flags(points, scan_idx, cls, table, sample_of_scan, lo, pre_keep=
     return keep, sample
 
 
+def stage_augment(points, params, sample_idx=None, out=None):
+    """csrc/stage.hip: rotate / scale / flip / translate the xyz columns of points [n, F >= 3] float32 (seg_utils.py:102-166) with
+    the record params[sample_idx[i]] (params [B, 8] float64 on the device, taseg_amd.data.augment.pack_params; sample_idx [n] int32
+    or None = record 0).  out: None (a new tensor), `points` itself (in place) or a contiguous tensor of the same shape."""
+    L.require_device(points, params, sample_idx, out)
+    if points.dtype != torch.float32 or points.ndim != 2 or points.shape[1] < 3:
+        raise TypeError("points must be a float32 [n, F >= 3] tensor")
+    if out is not None and not points.is_contiguous():
+        raise TypeError("points must be contiguous when out is given")
+    points = points.contiguous()
+    if params.dtype != torch.float64 or params.ndim != 2 or params.shape[1] != 8 or params.shape[0] < 1:
+        raise TypeError("params must be float64 [B, 8]")
+    params = params.contiguous()
+    n = points.shape[0]
+    if sample_idx is not None:
+        sample_idx = _i32(sample_idx, "sample_idx")
+        if sample_idx.shape != (n,):
+            raise ValueError("sample_idx must hold one index per point")
+    if out is None:
+        out = torch.empty_like(points)
+    elif out.dtype != torch.float32 or out.shape != points.shape or not out.is_contiguous():
+        raise TypeError("out must be a contiguous float32 tensor of points' shape")
+    if n:
+        L.check(L.load().ts_stage_augment(L.ptr(points), n, points.shape[1], L.ptr(sample_idx), L.ptr(params), params.shape[0],
+                                          L.ptr(out), L.stream()), "ts_stage_augment")
+    return out
+
+
 def stage_layout(cur, cur_lab, cur_b, hist, hist_lab, hist_b, idx, cur_start, kept_start):
     """csrc/stage.hip: the fused clouds of a batch sample-major, current scan first -> (pts [Nc + Nk, F], labels int64, sample
     int64, sample int32, is_current bool)."""

@@ -52,6 +52,105 @@ extern "C" int ts_stage_keep_flags(const float *points, int64_t n, int32_t point
   return TS_OK;
 }
 
+// Point augmentation (R/tools/utils/common/seg_utils.py:102-166 aug_points_ms, :43-100 aug_points): rotation about z, scale, x/y
+// flip, translation on the xyz columns, one parameter record of TS_AUG_RECORD doubles per sample:
+//   { c, s, scale, tx, ty, tz, bits, flip }   bits: 1 rotate, 2 scale, 4 flip, 8 translate, 16 scale in float32 ; flip: 0 .. 3
+// The reference multiplies the float32 cloud with a float64 matrix (np.dot), so everything after the rotation is float64 and the
+// store into its float32 array (semantickitti_voxel_ms.py:90) is the ONE rounding; a step that is switched off is skipped, not run
+// with identity values (-0.0 + 0.0 = +0.0), so a record without bits returns the input's bits.  Bit 16: without the rotation the
+// cloud is still float32 when it is scaled and numpy multiplies a float32 array by a Python float IN float32 - host-side choice
+// (taseg_amd/data/augment.py), the kernel only honours it.
+// One lane per point; VEC4: rows of 4 floats, 16-byte aligned -> one 16-byte load and one 16-byte store per lane.
+template <bool VEC4>
+__global__ __launch_bounds__(256) void stage_augment_kernel(const float *pts, int64_t n, int pstride,
+                                                            const int *__restrict__ sample, const double *__restrict__ params,
+                                                            int n_samples, float *out) {   // out may BE pts (in place)
+#pragma clang fp contract(off)
+  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t step = (int64_t)gridDim.x * blockDim.x;
+  for (; i < n; i += step) {
+    const int b = sample ? min(max(sample[i], 0), n_samples - 1) : 0;
+    const double *q = params + (int64_t)TS_AUG_RECORD * b;
+    const int bits = (int)q[6];
+    float4 p;
+    if (VEC4) {
+      p = reinterpret_cast<const float4 *>(pts)[i];
+    } else {
+      const float *r = pts + i * pstride;
+      p = make_float4(r[0], r[1], r[2], 0.f);
+    }
+    if (bits & 15) {
+      double X = p.x, Y = p.y, Z = p.z;
+      if (bits & 1) {
+        // np.dot(xyz, [[c, s, 0], [-s, c, 0], [0, 0, 1]]): dgemm's fused-multiply-add chain in k order, as in ts_fuse_sweeps.  The
+        // order matters where x*c and y*s cancel (a point at 45 degrees of azimuth under the TTA rotation pi/4): what is left is
+        // the rounding error of the first product, and it decides the float32 result.
+        const double c = q[0], s = q[1];
+        const double rx = fma(Z, 0.0, fma(Y, -s, X * c));
+        const double ry = fma(Z, 0.0, fma(Y, c, X * s));
+        const double rz = fma(Z, 1.0, fma(Y, 0.0, X * 0.0));
+        X = rx;
+        Y = ry;
+        Z = rz;
+      }
+      if (bits & 2) {
+        if (bits & 16) {
+          const float sc = (float)q[2];
+          X = (double)__fmul_rn((float)X, sc);
+          Y = (double)__fmul_rn((float)Y, sc);
+          Z = (double)__fmul_rn((float)Z, sc);
+        } else {
+          X *= q[2];
+          Y *= q[2];
+          Z *= q[2];
+        }
+      }
+      if (bits & 4) {
+        const int flip = (int)q[7];
+        if (flip & 1) X = -X;
+        if (flip & 2) Y = -Y;
+      }
+      if (bits & 8) {
+        X += q[3];
+        Y += q[4];
+        Z += q[5];
+      }
+      p.x = (float)X;
+      p.y = (float)Y;
+      p.z = (float)Z;
+    }
+    if (VEC4) {
+      reinterpret_cast<float4 *>(out)[i] = p;
+    } else {
+      float *w = out + i * pstride;
+      w[0] = p.x;
+      w[1] = p.y;
+      w[2] = p.z;
+      if (out != pts)
+        for (int k = 3; k < pstride; ++k) w[k] = pts[i * pstride + k];
+    }
+  }
+}
+
+extern "C" int ts_stage_augment(const float *points, int64_t n, int32_t point_stride, const int32_t *sample_idx,
+                                const double *params, int32_t n_samples, float *out, ts_stream_t stream) {
+  TS_REQUIRE(n >= 0 && point_stride >= 3 && n_samples > 0, TS_ERR_INVALID_ARGUMENT, "ts_stage_augment: bad sizes");
+  if (n == 0) return TS_OK;
+  TS_REQUIRE(points && params && out, TS_ERR_INVALID_ARGUMENT, "ts_stage_augment: null pointer");
+  if (out != points) {
+    const uintptr_t a = (uintptr_t)points, b = (uintptr_t)out, bytes = (uintptr_t)n * point_stride * sizeof(float);
+    TS_REQUIRE(a + bytes <= b || b + bytes <= a, TS_ERR_INVALID_ARGUMENT, "ts_stage_augment: out must be points or not overlap it");
+  }
+  const int grid = (int)std::min<int64_t>(ts_cdiv(n, 256), 2048);
+  if (point_stride == 4 && ((((uintptr_t)points) | ((uintptr_t)out)) & 15) == 0) {
+    stage_augment_kernel<true><<<grid, 256, 0, (hipStream_t)stream>>>(points, n, point_stride, sample_idx, params, n_samples, out);
+  } else {
+    stage_augment_kernel<false><<<grid, 256, 0, (hipStream_t)stream>>>(points, n, point_stride, sample_idx, params, n_samples, out);
+  }
+  TS_CHECK_LAUNCH("ts_stage_augment");
+  return TS_OK;
+}
+
 // The fused clouds of a batch, sample-major, current scan first, kept history behind it in its own order, written straight to
 // their rows: current point i of sample b goes to row i + kept_start[b] (kept_start[b] = kept history points of the samples
 // before b), kept history point j (= history row idx[j], sample hb) to row cur_start[hb + 1] + j.

@@ -15,6 +15,8 @@ Split between host and device the way the work splits:
                            float64 with numpy's rounding points, time delta column
       class-step mask      table lookup on the pseudo labels: keep class c of the sweep at position p iff
                            steps[c] != 0 and (p + 1) % steps[c] == 0 (:322-327)
+      augmentation (aug=)  ts_stage_augment on the current keyframes and on every fused sweep row (nuscenes_voxel_ms.py:90-120,
+                           data/augment.py), before the clamp and both voxelisations
       voxelisation         the same ts_voxel_coords / ts_sparse_quantize stage as SemanticKITTI (voxel 0.1 m,
                            IN_FEATURE_DIM 4: the time delta column is cut, nuscenes fsa yaml:16,28)
 
@@ -29,10 +31,11 @@ import numpy as np
 import torch
 
 from .. import backend as B
+from .augment import augment_points, draw_tta_params
 from .stage import collate_batch, voxelize_sample_ms
 
 __all__ = ["NuscSequence", "rotation_matrix", "relative_transform", "select_sweeps", "sweep_params", "fuse_sweeps",
-           "build_nuscenes_batch"]
+           "build_nuscenes_batch", "build_nuscenes_batch_per_sample", "build_tta_batch"]
 
 
 @dataclass
@@ -169,16 +172,18 @@ def fuse_sweeps(cur_pts, cur_lab, hist_pts: List[torch.Tensor], hist_lab: List[t
     return raw, lab, torch.cat([torch.ones(n_cur, dtype=torch.bool, device=dev), keep])
 
 
-def build_nuscenes_batch(samples: List[Dict], voxel_size: float, steps: Sequence[int], in_feature_dim: int = 4) -> Dict:
+def build_nuscenes_batch(samples: List[Dict], voxel_size: float, steps: Sequence[int], in_feature_dim: int = 4, aug=None) -> Dict:
     """samples[b] = dict(points [n,5], labels [n], hist_points [..], hist_labels [..], hist_pseudo [..],
     params [S,28] float64 tensor, name).  Returns the collated batch_dict MinkUNetMs consumes
     (nuscenes_voxel_ms.py:77-212 == the SemanticKITTI stage on the first `in_feature_dim` columns).
     The whole batch goes through ONE chain of launches: one ts_fuse_sweeps over every sweep point of every sample (ego box,
     sensor -> keyframe -> current-frame transforms, time delta), the class-step rule as one table lookup, then
-    stage.voxelize_batch_ms (one compaction, one batch-keyed voxelisation per cloud kind)."""
+    stage.voxelize_batch_ms (one compaction, one batch-keyed voxelisation per cloud kind).
+    aug: one AugParams per sample (data/augment.py) or None = the un-augmented path.  With it the current keyframes and all fused sweep
+    rows are augmented in place (one ts_stage_augment launch each, the sweep rows through their sweep index) before the clamp."""
     from . import stage as _stage
     if not _stage._BATCHED or not samples or len(samples) > 64:
-        return build_nuscenes_batch_per_sample(samples, voxel_size, steps, in_feature_dim)
+        return build_nuscenes_batch_per_sample(samples, voxel_size, steps, in_feature_dim, aug=aug)
     dev = samples[0]["points"].device
     f = in_feature_dim
     n_cls = len(steps)
@@ -186,6 +191,9 @@ def build_nuscenes_batch(samples: List[Dict], voxel_size: float, steps: Sequence
     cur_all[:, 4] = 0                                                 # time column of the current keyframe (:109)
     n_cur = [int(s["points"].shape[0]) for s in samples]
     cur_f = cur_all[:, :f].contiguous()
+    rec = None if aug is None else _stage._aug_records(aug, len(samples))
+    if rec is not None:
+        augment_points(cur_f, rec, _stage.rows_index32(n_cur, dev), out=cur_f)
     cuts = [0]
     for n in n_cur:
         cuts.append(cuts[-1] + n)
@@ -217,6 +225,8 @@ def build_nuscenes_batch(samples: List[Dict], voxel_size: float, steps: Sequence
         table, sample_of = hit
         fused, no_ego = B.fuse_sweeps(stack, sweep32, torch.cat(params, 0) if len(params) > 1 else params[0])
         hist_ms = fused[:, :f].contiguous()
+        if rec is not None:
+            augment_points(hist_ms, rec[np.asarray(sample_of_sweep, dtype=np.int64)], sweep32, out=hist_ms)
     else:
         hist_ms = torch.empty((0, f), dtype=cur_f.dtype, device=dev)
         lab_h = pseudo = torch.empty(0, dtype=torch.int64, device=dev)
@@ -228,14 +238,27 @@ def build_nuscenes_batch(samples: List[Dict], voxel_size: float, steps: Sequence
                                     [s.get("name", "") for s in samples], pre_keep=no_ego)
 
 
-def build_nuscenes_batch_per_sample(samples: List[Dict], voxel_size: float, steps: Sequence[int], in_feature_dim: int = 4) -> Dict:
+def build_nuscenes_batch_per_sample(samples: List[Dict], voxel_size: float, steps: Sequence[int], in_feature_dim: int = 4,
+                                    aug=None) -> Dict:
     """build_nuscenes_batch sample by sample (the form the batched stage replaced; its cross-check and TASEG_STAGE_BATCHED=0)"""
+    from . import stage as _stage
     out = []
-    for s in samples:
+    rec = None if aug is None else _stage._aug_records(aug, len(samples))
+    for b, s in enumerate(samples):
         raw, lab, keep = fuse_sweeps(s["points"], s["labels"], s["hist_points"], s["hist_labels"], s["hist_pseudo"],
                                      s["params"], steps)
         cur = s["points"].clone()
         cur[:, 4] = 0
         out.append(voxelize_sample_ms(cur[:, :in_feature_dim].contiguous(), s["labels"].long(),
-                                      raw[:, :in_feature_dim].contiguous(), lab, voxel_size, s.get("name", ""), keep=keep))
+                                      raw[:, :in_feature_dim].contiguous(), lab, voxel_size, s.get("name", ""), keep=keep,
+                                      aug=None if rec is None else rec[b:b + 1]))
     return collate_batch(out)
+
+
+def build_tta_batch(sample: Dict, votes_min: int, votes_max: int, rng, voxel_size: float, steps: Sequence[int],
+                    in_feature_dim: int = 4, scale_range: Sequence[float] = (0.9, 1.1)) -> Dict:
+    """nuscenes_voxel_ms.py:67-73, 103-120 + collate_batch_tta: the keyframe `votes_max - votes_min` times as batch entries, entry i
+    rotated by TTA_ANGLES[votes_min + i] * pi / 8 and scaled by a draw from `rng` (see stage.build_tta_batch)."""
+    votes = list(range(votes_min, votes_max))
+    aug = [draw_tta_params(rng, v, scale_range) for v in votes]
+    return build_nuscenes_batch([sample] * len(votes), voxel_size, steps, in_feature_dim, aug=aug)

@@ -25,8 +25,10 @@ Inputs, as the reference's dataset class finds them on disk:
     batch = build_nuscenes_batch([sample], 0.1, FLEXIBLE_STEPS_NUSC)
 
 Host work per sample = reading ~25 files and a few dozen 3x3 products (cached per keyframe like the reference's
-`token2samplelist`); everything per point runs on the device.  Augmentation (LaserMix / PolarMix, :132-213) and the Ceph
-client are outside the scope contract.
+`token2samplelist`); everything per point runs on the device.  The rotate / scale / flip / translate augmentation of the
+training recipe and the TTA views go in through the stage: `build_nuscenes_batch(samples, ..., aug=[draw_train_params(rng) for _
+in samples])` / `nuscenes.build_tta_batch` (taseg_amd/data/augment.py).  LaserMix / PolarMix (:132-213) and the Ceph client are
+outside the scope contract.
 """
 import json
 import os

@@ -12,7 +12,9 @@ filter and the voxelisation on the GPU.
     batch = build_multiscan_batch([sample], 0.05, FLEXIBLE_STEPS_KITTI)
 
 Host work per sample = reading ~17 files and one 4x4 product per pose; everything per point runs on the device.
-Augmentation (LaserMix / PolarMix / rotate-scale-flip) is outside the scope contract.
+The rotate / scale / flip / translate augmentation of the training recipe and the TTA views go in through the stage:
+`build_multiscan_batch(samples, ..., aug=[draw_train_params(rng) for _ in samples])` / `build_tta_batch` (taseg_amd/data/augment.py).
+LaserMix / PolarMix are outside the scope contract.
 """
 import os
 from typing import Dict, List, Optional, Sequence

@@ -7,6 +7,8 @@ semantickitti_voxel_ms.py:77-212); here the same steps run on the GPU on residen
   pose fuse            ts_fuse_scan        p' = ((p R_t^T + t_t) - t_0) R_0, float32, reference summation order
   class-step filter    lookup table        keep a history point iff steps[class] != 0 and |delta| % steps[class] == 0
   concat + time flag   torch.cat           current scan first (flag 1), kept history points after it (flag 0)
+  augmentation (aug=)  ts_stage_augment    rotate / scale / flip / translate of the current scan and every fused history row with the
+                                           sample's AugParams (data/augment.py), before the clamp and both voxelisations
   voxel coordinates    ts_voxel_coords     int32(round_half_even(xyz / voxel)) - min
   voxel grouping       ts_sparse_quantize  radix sort + first-occurrence representative + inverse map
 
@@ -15,14 +17,16 @@ for bit against the reference dataset code in tests (tests/golden/multiscan.npz)
 """
 from typing import Dict, List, Sequence
 
+import numpy as np
 import torch
 
 from .. import backend as B
+from .augment import augment_points, draw_tta_params, pack_params
 from ..torchsparse import SparseTensor
 from ..options import options
 
 __all__ = ["fuse_multiscan", "voxelize_sample_ms", "voxelize_sample", "collate_batch", "build_multiscan_batch",
-           "build_multiscan_batch_per_sample", "voxelize_batch_ms", "rows_index", "DevicePrefetcher"]
+           "build_multiscan_batch_per_sample", "build_tta_batch", "voxelize_batch_ms", "rows_index", "DevicePrefetcher"]
 
 
 _static_cache = {}
@@ -93,18 +97,33 @@ def _quantize(points, voxel_size, shift=None):
     return coords4[:, :3], mins, index.long(), inverse.long()
 
 
-def voxelize_sample(points, labels, voxel_size, name="") -> Dict:
-    """Single-frame sample (semantickitti_voxel.py:119-150)."""
+def _one_aug(aug):
+    """the single sample's record out of aug= (an AugParams or a list holding one)"""
+    rec = pack_params(aug)
+    if rec.shape[0] != 1:
+        raise ValueError("aug holds %d records for one sample" % rec.shape[0])
+    return rec
+
+
+def voxelize_sample(points, labels, voxel_size, name="", aug=None) -> Dict:
+    """Single-frame sample (semantickitti_voxel.py:119-150); aug: the sample's AugParams, applied first (:89-99)."""
+    if aug is not None:
+        points = augment_points(points, _one_aug(aug))
     pc, _, inds, inverse = _quantize(points, voxel_size)
     return {"name": name, "lidar": SparseTensor(points[inds], pc[inds]), "targets": SparseTensor(labels[inds], pc[inds]),
             "targets_mapped": SparseTensor(labels, pc), "inverse_map": SparseTensor(inverse, pc),
             "num_points": torch.tensor([points.shape[0]])}
 
 
-def voxelize_sample_ms(points, labels, points_ms, labels_ms, voxel_size, name="", keep=None, return_shift=False) -> Dict:
+def voxelize_sample_ms(points, labels, points_ms, labels_ms, voxel_size, name="", keep=None, return_shift=False, aug=None) -> Dict:
     """Multi-scan sample (semantickitti_voxel_ms.py:121-187): both clouds voxelised, the single-frame one
     shifted by the fused cloud's minimum.  `keep` (optional bool mask over points_ms) is AND-ed with the clamp
-    so the class-step filter and the clamp cost one compaction (one host read) instead of two."""
+    so the class-step filter and the clamp cost one compaction (one host read) instead of two.
+    aug: the sample's AugParams - both clouds go through the same kernel with the same record first (:90-119), so the current
+    scan's rows carry the same bits in both and the clamp, the voxel coordinates and the features see augmented coordinates."""
+    if aug is not None:
+        rec = torch.from_numpy(_one_aug(aug)).to(points.device, non_blocking=True)
+        points, points_ms = augment_points(points, rec), augment_points(points_ms, rec)
     # (min over dim 0 of the [n, 3] slice runs in one of torch's slow few-column reductions: 175 us for 35k points;
     #  the same minimum along the rows of the transposed copy takes ~10 us)
     lo = points[:, :3].t().contiguous().min(1).values
@@ -162,18 +181,27 @@ def collate_batch(samples: List[Dict]) -> Dict:
     return out
 
 
-def build_multiscan_batch_per_sample(scans: List[Dict], voxel_size: float, steps: Sequence[int]) -> Dict:
+def _aug_records(aug, n_samples):
+    """aug= of a batch -> float64 [B, 8] records, one per sample"""
+    rec = pack_params(aug)
+    if rec.shape[0] != n_samples:
+        raise ValueError("aug holds %d records for %d samples" % (rec.shape[0], n_samples))
+    return rec
+
+
+def build_multiscan_batch_per_sample(scans: List[Dict], voxel_size: float, steps: Sequence[int], aug=None) -> Dict:
     """build_multiscan_batch sample by sample (fuse, clamp, two voxelisations and ~55 launches per sample, then collate): the
     form the batched stage below replaced; kept as its cross-check (tests) and for TASEG_STAGE_BATCHED=0."""
     samples = []
-    for s in scans:
+    rec = None if aug is None else _aug_records(aug, len(scans))
+    for b, s in enumerate(scans):
         pts, lab, poses = s["points"], s["labels"], s["poses"]
         t = len(pts) - 1
         deltas = s.get("deltas") or [i - t for i in range(t)]
         raw_all, lab_all, keep = _fuse_history(pts[t], lab[t], pts[:t], lab[:t], poses[t], poses[:t], deltas, steps,
                                                s.get("pseudo"))
         samples.append(voxelize_sample_ms(pts[t], lab[t].long(), raw_all, lab_all, voxel_size, s.get("name", ""),
-                                          keep=keep))
+                                          keep=keep, aug=None if rec is None else rec[b:b + 1]))
     return collate_batch(samples)
 
 
@@ -269,14 +297,17 @@ def rows_index32(lengths: Sequence[int], device) -> torch.Tensor:
     return hit
 
 
-def build_multiscan_batch(scans: List[Dict], voxel_size: float, steps: Sequence[int]) -> Dict:
+def build_multiscan_batch(scans: List[Dict], voxel_size: float, steps: Sequence[int], aug=None) -> Dict:
     """scans[b] = dict(points=[T+1 tensors, current LAST], labels=[...], poses=[...], name=str
     [, deltas=[frame offsets of the history scans], pseudo=[pseudo classes of the history scans, see _fuse_history]]).
     Returns the collated batch_dict MinkUNetMs consumes.  The whole batch goes through ONE chain of launches: one pose-fuse
     launch over every history point of every sample (ts_fuse_scans_batch), the class-step rule as one table lookup, then
-    voxelize_batch_ms."""
+    voxelize_batch_ms.
+    aug: one AugParams per sample (data/augment.py) or None.  With it the current scans and ALL pose-fused history rows are
+    augmented in place, one ts_stage_augment launch each (the history rows pick their sample's record through their scan index),
+    before the clamp minima are taken - two launches and one small host-to-device copy more than aug=None, the un-augmented path."""
     if not _BATCHED or not scans or len(scans) > 64:
-        return build_multiscan_batch_per_sample(scans, voxel_size, steps)
+        return build_multiscan_batch_per_sample(scans, voxel_size, steps, aug=aug)
     dev = scans[0]["points"][-1].device
     n_cls = len(steps)
     cur_list, lab_list, hist_pts, hist_lab, hist_ps, lengths, scan_sample, pose0s, poses, rows = [], [], [], [], [], [], [], [], [], []
@@ -299,6 +330,15 @@ def build_multiscan_batch(scans: List[Dict], voxel_size: float, steps: Sequence[
             # |delta| % steps[c] == 0; last column: pseudo class -1 (no class's canonical raw id): never kept
             rows.append([bool(st) and abs(deltas[i]) % st == 0 for st in steps] + [False])
     cur4 = torch.cat(cur_list, 0)
+    cur_in = [s["points"][-1] for s in scans]
+    if aug is not None:
+        rec = _aug_records(aug, len(scans))
+        n_cur = [int(c.shape[0]) for c in cur_list]
+        # the records of the samples, then one per history scan (its sample's): ONE upload for both launches
+        rec_dev = torch.from_numpy(np.concatenate([rec, rec[np.asarray(scan_sample, dtype=np.int64)]], 0)).to(dev, non_blocking=True)
+        # (cur4 is torch.cat's fresh tensor: the resident scans stay untouched)
+        augment_points(cur4, rec_dev[:len(scans)], rows_index32(n_cur, dev), out=cur4)
+        cur_in = list(torch.split(cur4, n_cur))        # the single-frame clouds ARE the rows the fused clouds start with
     cur_ms = torch.cat([cur4, torch.ones((cur4.shape[0], 1), dtype=cur4.dtype, device=dev)], 1)      # append_time_flag (:253-257)
     if hist_pts:
         hp = torch.cat(hist_pts, 0).contiguous()
@@ -314,6 +354,8 @@ def build_multiscan_batch(scans: List[Dict], voxel_size: float, steps: Sequence[
         table, sample_of_scan = hit
         scan32 = rows_index32(lengths, dev)
         fused = B.fuse_scans_batch(hp, scan32, torch.stack(pose0s, 0), torch.stack(poses, 0))
+        if aug is not None:
+            augment_points(fused, rec_dev[len(scans):], scan32, out=fused)
         hist_ms = torch.cat([fused, torch.zeros((fused.shape[0], 1), dtype=fused.dtype, device=dev)], 1)
     else:
         hist_ms = torch.empty((0, 5), dtype=cur4.dtype, device=dev)
@@ -321,8 +363,18 @@ def build_multiscan_batch(scans: List[Dict], voxel_size: float, steps: Sequence[
         scan32 = torch.empty(0, dtype=torch.int32, device=dev)
         table = torch.zeros((1, n_cls + 1), dtype=torch.bool, device=dev)
         sample_of_scan = torch.zeros(1, dtype=torch.int64, device=dev)
-    return voxelize_batch_ms([s["points"][-1] for s in scans], lab_list, cur_ms, hist_ms, hl, scan32, hps, table, sample_of_scan,
+    return voxelize_batch_ms(cur_in, lab_list, cur_ms, hist_ms, hl, scan32, hps, table, sample_of_scan,
                              voxel_size, [s.get("name", "") for s in scans], neg_col=n_cls)
+
+
+def build_tta_batch(scan: Dict, votes_min: int, votes_max: int, rng, voxel_size: float, steps: Sequence[int],
+                    scale_range: Sequence[float] = (0.9, 1.1)) -> Dict:
+    """The reference's `__getitem__` under `TTA: True` + `collate_batch_tta` (semantickitti_voxel_ms.py:66-72, 102-119, 214-238): the
+    scan `votes_max - votes_min` times as batch entries, entry i rotated by TTA_ANGLES[votes_min + i] * pi / 8 and scaled by a draw
+    from `rng` (np.random.RandomState; SCALE_AUG_RANGE) - the batch whose eval dictionary `pcseg.eval.accumulate_votes` sums."""
+    votes = list(range(votes_min, votes_max))
+    aug = [draw_tta_params(rng, v, scale_range) for v in votes]
+    return build_multiscan_batch([scan] * len(votes), voxel_size, steps, aug=aug)
 
 
 class DevicePrefetcher:
