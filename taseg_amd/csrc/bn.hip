@@ -571,11 +571,12 @@ __global__ __launch_bounds__(256) void bn_act_fwd_h_kernel(const bn_h8 *__restri
     for (int i = 0; i < 8; ++i) {
       float v = ((float)x[i] - mean[q + i]) * invstd[q + i] * w[q + i] + b[q + i];
       if (RES) v += (float)r[i];
-      if (relu) {
-        mk |= (v > 0.f ? 1u : 0u) << i;
-        v = fmaxf(v, 0.f);
-      }
-      y[i] = (_Float16)v;
+      if (relu) v = fmaxf(v, 0.f);
+      const _Float16 h = (_Float16)v;
+      // the mask bit is the sign of the STORED value (what torch's ReLU backward looks at): a positive fp32 value below half's
+      // smallest subnormal rounds to zero and passes no gradient
+      if (relu) mk |= (h > (_Float16)0 ? 1u : 0u) << i;
+      y[i] = h;
     }
     if (relu && MASK) MASK[e] = (unsigned char)mk;
     OUT[e] = y;
