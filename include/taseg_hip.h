@@ -917,6 +917,33 @@ int ts_stage_split_voxels(const int32_t *coords4, const int32_t *index, int64_t 
 #define TS_AUG_RECORD 8
 int ts_stage_augment(const float *points, int64_t n, int32_t point_stride, const int32_t *sample_idx, const double *params,
                      int32_t n_samples, float *out, ts_stream_t stream);
+/* Scan mixing of the training recipe (csrc/mix.hip; taseg_amd/data/mix.py draws the parameters): PolarMix
+ * (semantickitti_ms.py:188-237 calling PolarMix_semantickitti.py:10-96; nuscenes_ms.py:168-214 calling PolarMix_nuscenes.py) and
+ * LaserMix (semantickitti_ms.py:153-186 calling LaserMix_semantickitti.py:11-114 `lasermix_aug`; :116-219 `lasermix_aug_`) as a
+ * stable partition of the rows of two clouds.  n_jobs jobs (samples), their rows concatenated job-major in points [n_rows,
+ * point_stride >= 3] / labels [n_rows], cloud 1 (n1 rows) before cloud 2 (n2 rows); every job owns ceil((n1 + n2) / 256) blocks
+ * of the grid (n_blocks in all).  keep [n_rows] bytes or NULL: a row whose byte is 0 does not exist (the class-step filter of the
+ * fused clouds, semantickitti_ms.py:143).  records [n_jobs, TS_MIX_RECORD] doubles:
+ *   0 kind (0 none: cloud 1 as it is, 1 LaserMix, 2 PolarMix)   1 alpha  2 beta  3 swap  4 paste   (PolarMix_semantickitti.py:61-91)
+ *   5 .. 8 cos / sin of Omega[0], cos / sin of Omega[1]          9 rotated copies carry all columns after xyz (SemanticKITTI
+ *   :54) or only column 3, zeros behind it (PolarMix_nuscenes.py:53)
+ *   10 inclination in degrees (lasermix_aug_)  11 number of band thresholds  12 .. 16 the thresholds, descending
+ *   17 n1  18 n2  19 first row  20 instance classes  21 first block  22 blocks
+ * classes [n_jobs, TS_MIX_MAX_CLASSES] int32: the job's instance classes in list order (PolarMix_semantickitti.py:37).
+ * Rules: yaw = (float)(-atan2((double)y, (double)x)); in the sector iff swap and (float)alpha < yaw < (float)beta.  PolarMix writes
+ * cloud 1 without its sector rows | cloud 2's sector rows | cloud 2's instance rows by class, file order within a class | that
+ * block rotated by Omega[0] | by Omega[1] (np.dot with [[c, s, 0], [-s, c, 0], [0, 0, 1]]: the ROTATE arithmetic of
+ * ts_stage_augment).  LaserMix: inc = atan2(z, sqrt(x*x + y*y)) in float64 (/ pi * 180 under field 10), band = number of
+ * thresholds with inc <= threshold; bands 0, 2, 4 come from cloud 1, bands 1, 3, 5 from cloud 2, written in band order.
+ * out [capacity, point_stride], out_labels, out_job (the job of every row): the jobs' results one after the other, job j at rows
+ * sum(totals[0 .. j)) ... ; totals [n_jobs] int64 the rows of every job (read them once per batch).  capacity bounds every store:
+ * n1 + n2 * (swap + 3 * paste) per PolarMix job, n1 + n2 per LaserMix job.  No atomics: the same bits every run. */
+#define TS_MIX_RECORD 24
+#define TS_MIX_MAX_CLASSES 16
+size_t ts_stage_mix_workspace_bytes(int64_t n_rows, int64_t n_blocks, int32_t n_jobs);
+int ts_stage_mix(const float *points, int64_t n_rows, int32_t point_stride, const int64_t *labels, const uint8_t *keep,
+                 const double *records, const int32_t *classes, int32_t n_jobs, int64_t n_blocks, float *out, int64_t *out_labels,
+                 int32_t *out_job, int64_t capacity, int64_t *totals, void *ws, size_t ws_bytes, ts_stream_t stream);
 size_t ts_quantize_workspace_bytes(int64_t n);
 int ts_sparse_quantize(const int32_t *coords, int64_t n, int32_t *out_index, int32_t *out_inverse,
                        int32_t *out_count, void *ws, size_t ws_bytes, ts_stream_t stream);

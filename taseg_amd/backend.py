@@ -1265,6 +1265,48 @@ def stage_augment(points, params, sample_idx=None, out=None):
     return out
 
 
+def stage_mix(points, labels, params, n1, n2, keep=None, totals=None):
+    """csrc/mix.hip: PolarMix / LaserMix of a batch of jobs in three launches (taseg_amd/data/mix.py).  points [N, F >= 3] float32
+    and labels [N] int64: the jobs' rows job-major, cloud 1 (n1[j] rows) before cloud 2 (n2[j] rows); params: one MixParams per job;
+    keep [N] bool / uint8 (optional): rows that do not exist.  Returns (out [capacity, F], out_labels, out_job int32, totals [J]
+    int64): job j's rows are out[sum(totals[:j]) : sum(totals[:j + 1])] - the caller reads totals (`totals=`: a [J] int64 device
+    tensor to write them to, so several calls share one read).  No host read here."""
+    from .data import mix as M
+    L.require_device(points, labels, keep, totals)
+    points = _f32(points, "points")
+    if points.ndim != 2 or points.shape[1] < 3:
+        raise TypeError("points must be a float32 [n, F >= 3] tensor")
+    if labels.dtype != torch.int64:
+        raise TypeError("labels must be int64")
+    labels = labels.contiguous()
+    n, f, nj = points.shape[0], points.shape[1], len(params)
+    if nj < 1 or nj > 1024 or len(n1) != nj or len(n2) != nj or sum(n1) + sum(n2) != n or labels.shape != (n,):
+        raise ValueError("stage_mix: 1 .. 1024 jobs whose rows add up to the points given")
+    if keep is not None:
+        keep = keep.contiguous()
+        if keep.dtype not in (torch.bool, torch.uint8) or keep.shape != (n,):
+            raise TypeError("keep must be bool / uint8, one per row")
+    rec, cls, n_blocks = M.pack_mix(params, n1, n2)
+    cap = M.mix_capacity(params, n1, n2)
+    dev = points.device
+    rec_dev = torch.from_numpy(rec).to(dev, non_blocking=True)
+    cls_dev = torch.from_numpy(cls).to(dev, non_blocking=True)
+    out = torch.empty((cap, f), dtype=torch.float32, device=dev)
+    out_lab = torch.empty(cap, dtype=torch.int64, device=dev)
+    out_job = torch.empty(cap, dtype=torch.int32, device=dev)
+    if totals is None:
+        totals = torch.empty(nj, dtype=torch.int64, device=dev)
+    elif totals.dtype != torch.int64 or totals.shape != (nj,) or not totals.is_contiguous():
+        raise TypeError("totals must be a contiguous int64 [J] tensor")
+    lib = L.load()
+    ws_bytes = lib.ts_stage_mix_workspace_bytes(n, n_blocks, nj)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    L.check(lib.ts_stage_mix(L.ptr(points), n, f, L.ptr(labels), L.ptr(keep), L.ptr(rec_dev), L.ptr(cls_dev), nj, n_blocks,
+                             L.ptr(out), L.ptr(out_lab), L.ptr(out_job), cap, L.ptr(totals), L.ptr(ws), ws_bytes, L.stream()),
+            "ts_stage_mix")
+    return out, out_lab, out_job, totals
+
+
 def stage_layout(cur, cur_lab, cur_b, hist, hist_lab, hist_b, idx, cur_start, kept_start):
     """csrc/stage.hip: the fused clouds of a batch sample-major, current scan first -> (pts [Nc + Nk, F], labels int64, sample
     int64, sample int32, is_current bool)."""

@@ -27,8 +27,9 @@ Inputs, as the reference's dataset class finds them on disk:
 Host work per sample = reading ~25 files and a few dozen 3x3 products (cached per keyframe like the reference's
 `token2samplelist`); everything per point runs on the device.  The rotate / scale / flip / translate augmentation of the
 training recipe and the TTA views go in through the stage: `build_nuscenes_batch(samples, ..., aug=[draw_train_params(rng) for _
-in samples])` / `nuscenes.build_tta_batch` (taseg_amd/data/augment.py).  LaserMix / PolarMix (:132-213) and the Ceph client are
-outside the scope contract.
+in samples])` / `nuscenes.build_tta_batch` (taseg_amd/data/augment.py).  LaserMix / PolarMix (:132-213) exist as
+`polarmix_points` / `lasermix_points` with the nuScenes class list and tail rule (taseg_amd/data/mix.py), not yet as a `mix=` of
+`build_nuscenes_batch`; the Ceph client is outside the scope contract.
 """
 import json
 import os

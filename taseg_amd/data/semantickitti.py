@@ -14,7 +14,7 @@ filter and the voxelisation on the GPU.
 Host work per sample = reading ~17 files and one 4x4 product per pose; everything per point runs on the device.
 The rotate / scale / flip / translate augmentation of the training recipe and the TTA views go in through the stage:
 `build_multiscan_batch(samples, ..., aug=[draw_train_params(rng) for _ in samples])` / `build_tta_batch` (taseg_amd/data/augment.py).
-LaserMix / PolarMix are outside the scope contract.
+LaserMix / PolarMix (:151-237) go in the same way: `mix=[draw_mix_params(rng, omega) ...]` and `partners=` (taseg_amd/data/mix.py).
 """
 import os
 from typing import Dict, List, Optional, Sequence

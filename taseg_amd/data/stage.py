@@ -7,6 +7,8 @@ semantickitti_voxel_ms.py:77-212); here the same steps run on the GPU on residen
   pose fuse            ts_fuse_scan        p' = ((p R_t^T + t_t) - t_0) R_0, float32, reference summation order
   class-step filter    lookup table        keep a history point iff steps[class] != 0 and |delta| % steps[class] == 0
   concat + time flag   torch.cat           current scan first (flag 1), kept history points after it (flag 0)
+  scan mixing (mix=)   ts_stage_mix        PolarMix / LaserMix with a partner scan (data/mix.py), on the single-frame pair and on the
+                                           fused pair, before the augmentation (semantickitti_ms.py:151-237)
   augmentation (aug=)  ts_stage_augment    rotate / scale / flip / translate of the current scan and every fused history row with the
                                            sample's AugParams (data/augment.py), before the clamp and both voxelisations
   voxel coordinates    ts_voxel_coords     int32(round_half_even(xyz / voxel)) - min
@@ -22,6 +24,7 @@ import torch
 
 from .. import backend as B
 from .augment import augment_points, draw_tta_params, pack_params
+from . import mix as M
 from ..torchsparse import SparseTensor
 from ..options import options
 
@@ -189,19 +192,59 @@ def _aug_records(aug, n_samples):
     return rec
 
 
-def build_multiscan_batch_per_sample(scans: List[Dict], voxel_size: float, steps: Sequence[int], aug=None) -> Dict:
+def _mix_records(mix, partners, n_samples):
+    """mix= / partners= of a batch, checked: one MixParams per sample, a partner scan for every sample whose mix moves rows of one"""
+    mix = list(mix)
+    if len(mix) != n_samples or not all(isinstance(p, M.MixParams) for p in mix):
+        raise ValueError("mix must hold one MixParams per sample")
+    partners = [None] * n_samples if partners is None else list(partners)
+    if len(partners) != n_samples:
+        raise ValueError("partners must hold one scan (or None) per sample")
+    for p, q in zip(mix, partners):
+        # (the reference's LaserMix branch is the identity: it needs no partner)
+        if q is None and (p.kind == M.POLAR or (p.kind == M.LASER and p.degrees)):
+            raise ValueError("a sample that is mixed needs its partner scan")
+    return mix, partners
+
+
+def _fused_cloud(s, steps):
+    """(current scan [n, 4], its labels, fused cloud [m, 5] after the class-step filter, its labels) of one scan dict: what the
+    reference's `__getitem__` holds when it reaches the mix (semantickitti_ms.py:140-149), for a sample and for its partner alike"""
+    pts, lab, poses = s["points"], s["labels"], s["poses"]
+    t = len(pts) - 1
+    deltas = s.get("deltas") or [i - t for i in range(t)]
+    raw_all, lab_all, keep = _fuse_history(pts[t], lab[t], pts[:t], lab[:t], poses[t], poses[:t], deltas, steps, s.get("pseudo"))
+    return pts[t][:, :4], lab[t].long(), raw_all[keep], lab_all[keep]
+
+
+def build_multiscan_batch_per_sample(scans: List[Dict], voxel_size: float, steps: Sequence[int], aug=None, mix=None,
+                                     partners=None) -> Dict:
     """build_multiscan_batch sample by sample (fuse, clamp, two voxelisations and ~55 launches per sample, then collate): the
     form the batched stage below replaced; kept as its cross-check (tests) and for TASEG_STAGE_BATCHED=0."""
     samples = []
     rec = None if aug is None else _aug_records(aug, len(scans))
+    if mix is not None:
+        mix, partners = _mix_records(mix, partners, len(scans))
     for b, s in enumerate(scans):
+        one = None if rec is None else rec[b:b + 1]
+        if mix is not None and mix[b].kind != M.NONE:
+            cur, lab, raw, lab_ms = _fused_cloud(s, steps)
+            if partners[b] is None:
+                pcur, plab, praw, plab_ms = cur[:0], lab[:0], raw[:0], lab_ms[:0]
+            else:
+                pcur, plab, praw, plab_ms = _fused_cloud(partners[b], steps)
+            # the same record on the single-frame pair and on the fused pair (semantickitti_ms.py:182-185, :221-234)
+            cur, lab = M.mix_points(cur, lab, pcur, plab, mix[b])
+            raw, lab_ms = M.mix_points(raw, lab_ms, praw, plab_ms, mix[b])
+            samples.append(voxelize_sample_ms(cur, lab, raw, lab_ms, voxel_size, s.get("name", ""), aug=one))
+            continue
         pts, lab, poses = s["points"], s["labels"], s["poses"]
         t = len(pts) - 1
         deltas = s.get("deltas") or [i - t for i in range(t)]
         raw_all, lab_all, keep = _fuse_history(pts[t], lab[t], pts[:t], lab[:t], poses[t], poses[:t], deltas, steps,
                                                s.get("pseudo"))
         samples.append(voxelize_sample_ms(pts[t], lab[t].long(), raw_all, lab_all, voxel_size, s.get("name", ""),
-                                          keep=keep, aug=None if rec is None else rec[b:b + 1]))
+                                          keep=keep, aug=one))
     return collate_batch(samples)
 
 
@@ -268,6 +311,13 @@ def voxelize_batch_ms(cur_list: List[torch.Tensor], lab_list: List[torch.Tensor]
         ms_b, ms_b32, ms_pts, ms_lab = cur_b, cur_b.int(), cur_ms.contiguous(), cur_lab
         point_mask = torch.ones(n_c, dtype=torch.bool, device=dev)
         n_ms = list(n_cur)
+    return _voxelize_layout(cur, cur_lab, cur_b, n_cur, ms_pts, ms_lab, ms_b, ms_b32, n_ms, point_mask, voxel_size, names)
+
+
+def _voxelize_layout(cur, cur_lab, cur_b, n_cur, ms_pts, ms_lab, ms_b, ms_b32, n_ms, point_mask, voxel_size, names) -> Dict:
+    """the two voxelisations and the batch_dict of voxelize_batch_ms, from the clouds laid out sample-major: cur [sum n_cur, F] with
+    labels and sample index (int64), the fused clouds ms_pts [sum n_ms, Fm] with labels and sample index (int64 and int32)"""
+    dev, nb = cur.device, len(n_cur)
     coords_ms, mins = B.voxel_coords(ms_pts, voxel_size, batch_idx=ms_b32, n_batch=nb)
     index_ms, inverse_ms = B.sparse_quantize(coords_ms)                 # host read 3 (voxels of the fused clouds)
     coords_c, _ = B.voxel_coords(cur, voxel_size, batch_idx=rows_index32(n_cur, dev), n_batch=nb, shift=mins)   # pc_ -= pc_ms_.min(0) (:130)
@@ -297,7 +347,108 @@ def rows_index32(lengths: Sequence[int], device) -> torch.Tensor:
     return hit
 
 
-def build_multiscan_batch(scans: List[Dict], voxel_size: float, steps: Sequence[int], aug=None) -> Dict:
+def _build_multiscan_batch_mix(scans, partners, mix, voxel_size, steps, aug) -> Dict:
+    """build_multiscan_batch with mix=: the samples' and the partners' history scans pose-fused in ONE launch, the class-step rule
+    as a keep byte per row (no compaction of its own), ts_stage_mix on the single-frame pairs and on the fused pairs of the whole
+    batch (three launches each, their row counts in one host read), the augmentation, the clamp of EVERY fused row against the
+    mixed single-frame cloud's minimum (after a mix the current scan is no prefix of the fused cloud any more;
+    semantickitti_voxel_ms.py:121-124), one compaction, both voxelisations.  point_mask stays what the reference's collate_batch
+    makes it: the first num_points rows of every fused cloud (:204-210)."""
+    dev = scans[0]["points"][-1].device
+    nb, n_cls = len(scans), len(steps)
+    hist_pts, hist_lab, hist_ps, lengths, pose0s, poses, rows = [], [], [], [], [], [], []
+    clouds = []                        # per sample: [own cloud, partner cloud or None]; a cloud = (cur4, labels, first history row, rows)
+    n_hist = 0
+    any_pseudo = any(c is not None and c.get("pseudo") is not None for c in list(scans) + list(partners))
+    for b, s in enumerate(scans):
+        pair = []
+        for c in (s, partners[b] if mix[b].kind != M.NONE else None):
+            if c is None:
+                pair.append(None)
+                continue
+            pts, lab, ps = c["points"], c["labels"], c["poses"]
+            t = len(pts) - 1
+            deltas = c.get("deltas") or [i - t for i in range(t)]
+            pseudo = c.get("pseudo")
+            first = n_hist
+            for i in range(t):
+                hist_pts.append(pts[i][:, :4])
+                hist_lab.append(lab[i])
+                hist_ps.append(lab[i] if pseudo is None else pseudo[i])
+                lengths.append(int(pts[i].shape[0]))
+                pose0s.append(ps[t])
+                poses.append(ps[i])
+                rows.append([bool(st) and abs(deltas[i]) % st == 0 for st in steps] + [False])   # semantickitti_ms.py:303-308
+                n_hist += lengths[-1]
+            pair.append((pts[t][:, :4], lab[t].long(), first, n_hist - first))
+        clouds.append(pair)
+    if hist_pts:
+        hp = torch.cat(hist_pts, 0).contiguous()
+        hl = torch.cat(hist_lab, 0).long()
+        hps = torch.cat(hist_ps, 0).long() if any_pseudo else hl
+        scan32 = rows_index32(lengths, dev)
+        table = torch.tensor(rows, dtype=torch.bool).to(dev, non_blocking=True)
+        fused = B.fuse_scans_batch(hp, scan32, torch.stack(pose0s, 0), torch.stack(poses, 0))
+        hps = torch.where(hps < 0, torch.full_like(hps, n_cls), hps)
+        hkeep = table.view(-1)[scan32.long() * (n_cls + 1) + hps]
+    else:
+        fused = torch.empty((0, 4), dtype=torch.float32, device=dev)
+        hl = torch.empty(0, dtype=torch.int64, device=dev)
+        hkeep = torch.empty(0, dtype=torch.bool, device=dev)
+    # job-major rows: [current | partner's current] for the single-frame mix, [current | history | partner's current | partner's
+    # history] for the fused one
+    s_pts, s_lab, s_n1, s_n2 = [], [], [], []
+    m_pts, m_lab, m_keep, m_len, m_n1, m_n2 = [], [], [], [], [], []
+    ones = torch.ones(max([c[0].shape[0] for pair in clouds for c in pair if c is not None] + [1]), dtype=torch.bool, device=dev)
+    for pair in clouds:
+        sizes = []
+        for c in pair:
+            if c is None:
+                sizes.append((0, 0))
+                m_len += [0, 0]
+                continue
+            cur4, lab, first, nh = c
+            n = int(cur4.shape[0])
+            s_pts.append(cur4)
+            s_lab.append(lab)
+            m_pts += [cur4, fused[first:first + nh]]
+            m_lab += [lab, hl[first:first + nh]]
+            m_keep += [ones[:n], hkeep[first:first + nh]]
+            m_len += [n, nh]
+            sizes.append((n, nh))
+        s_n1.append(sizes[0][0])
+        s_n2.append(sizes[1][0])
+        m_n1.append(sizes[0][0] + sizes[0][1])
+        m_n2.append(sizes[1][0] + sizes[1][1])
+    totals = torch.empty((2, nb), dtype=torch.int64, device=dev)
+    cur, cur_lab, cur_b32, _ = B.stage_mix(torch.cat(s_pts, 0), torch.cat(s_lab, 0), mix, s_n1, s_n2, totals=totals[0])
+    flag = (rows_index(m_len, dev) % 2 == 0).to(torch.float32)          # append_time_flag (:253-257): the pieces alternate
+    ms_in = torch.cat([torch.cat(m_pts, 0), flag.unsqueeze(1)], 1)
+    ms, ms_lab, ms_b32, _ = B.stage_mix(ms_in, torch.cat(m_lab, 0), mix, m_n1, m_n2, keep=torch.cat(m_keep, 0), totals=totals[1])
+    n_cur, n_mixed = totals.tolist()                                    # host read 1 (rows of both mixes, all samples)
+    cur, cur_lab, cur_b32 = cur[:sum(n_cur)], cur_lab[:sum(n_cur)], cur_b32[:sum(n_cur)]
+    ms, ms_lab, ms_b32 = ms[:sum(n_mixed)], ms_lab[:sum(n_mixed)], ms_b32[:sum(n_mixed)]
+    if aug is not None:
+        rec_dev = torch.from_numpy(_aug_records(aug, nb)).to(dev, non_blocking=True)
+        augment_points(cur, rec_dev, cur_b32, out=cur)
+        augment_points(ms, rec_dev, ms_b32, out=ms)
+    cur_b = cur_b32.long()
+    lo = B.segment_min3(cur, cur_b, nb)
+    ms_b = ms_b32.long()
+    idx = (ms[:, :3] >= lo[ms_b]).all(1).nonzero().squeeze(1)           # host read 2 (the compaction's size)
+    ms, ms_lab, ms_b, ms_b32 = ms[idx].contiguous(), ms_lab[idx], ms_b[idx], ms_b32[idx]
+    start = torch.searchsorted(ms_b, torch.arange(nb + 1, device=dev))
+    n_ms = (start[1:] - start[:-1]).tolist()                            # host read 3 (fused rows per sample)
+    point_mask = torch.zeros(sum(n_ms), dtype=torch.bool, device=dev)
+    at = 0
+    for a, m in zip(n_cur, n_ms):
+        point_mask[at:at + a] = True
+        at += m
+    return _voxelize_layout(cur, cur_lab, cur_b, n_cur, ms, ms_lab, ms_b, ms_b32, n_ms, point_mask, voxel_size,
+                            [s.get("name", "") for s in scans])
+
+
+def build_multiscan_batch(scans: List[Dict], voxel_size: float, steps: Sequence[int], aug=None, mix=None, partners=None) -> Dict:
     """scans[b] = dict(points=[T+1 tensors, current LAST], labels=[...], poses=[...], name=str
     [, deltas=[frame offsets of the history scans], pseudo=[pseudo classes of the history scans, see _fuse_history]]).
     Returns the collated batch_dict MinkUNetMs consumes.  The whole batch goes through ONE chain of launches: one pose-fuse
@@ -305,9 +456,16 @@ def build_multiscan_batch(scans: List[Dict], voxel_size: float, steps: Sequence[
     voxelize_batch_ms.
     aug: one AugParams per sample (data/augment.py) or None.  With it the current scans and ALL pose-fused history rows are
     augmented in place, one ts_stage_augment launch each (the history rows pick their sample's record through their scan index),
-    before the clamp minima are taken - two launches and one small host-to-device copy more than aug=None, the un-augmented path."""
+    before the clamp minima are taken - two launches and one small host-to-device copy more than aug=None, the un-augmented path.
+    mix: one MixParams per sample (data/mix.py) or None; partners[b]: the scan dict of sample b's partner (None where its mix needs
+    none).  With it every sample is mixed with its partner - PolarMix / LaserMix on the single-frame pair and on the fused pair,
+    semantickitti_ms.py:151-237 - before the augmentation (_build_multiscan_batch_mix); mix=None is the path without it, launch
+    for launch."""
     if not _BATCHED or not scans or len(scans) > 64:
-        return build_multiscan_batch_per_sample(scans, voxel_size, steps, aug=aug)
+        return build_multiscan_batch_per_sample(scans, voxel_size, steps, aug=aug, mix=mix, partners=partners)
+    if mix is not None:
+        mix, partners = _mix_records(mix, partners, len(scans))
+        return _build_multiscan_batch_mix(scans, partners, mix, voxel_size, steps, aug)
     dev = scans[0]["points"][-1].device
     n_cls = len(steps)
     cur_list, lab_list, hist_pts, hist_lab, hist_ps, lengths, scan_sample, pose0s, poses, rows = [], [], [], [], [], [], [], [], [], []
