@@ -13,8 +13,7 @@ Split between host and device the way the work splits:
   device (one launch per sample over all selected sweeps):
       ts_fuse_sweeps       ego-box filter on the raw coordinates, sensor -> keyframe -> current-frame transforms in
                            float64 with numpy's rounding points, time delta column
-      class-step mask      table lookup on the pseudo labels: keep class c of the sweep at position p iff
-                           steps[c] != 0 and (p + 1) % steps[c] == 0 (:322-327)
+      class-step mask      table lookup on the pseudo labels, one _nusc_row per selected sweep (:322-327)
       augmentation (aug=)  ts_stage_augment on the current keyframes and on every fused sweep row (nuscenes_voxel_ms.py:90-120,
                            data/augment.py), before the clamp and both voxelisations
       voxelisation         the same ts_voxel_coords / ts_sparse_quantize stage as SemanticKITTI (voxel 0.1 m,
@@ -31,8 +30,9 @@ import numpy as np
 import torch
 
 from .. import backend as B
+from . import stage as _stage          # (_stage._BATCHED is read at call time)
 from .augment import augment_points, draw_tta_params
-from .stage import collate_batch, voxelize_sample_ms
+from .stage import _aug_records, _cached, _step_table, collate_batch, rows_index32, voxelize_batch_ms, voxelize_sample_ms
 
 __all__ = ["NuscSequence", "rotation_matrix", "relative_transform", "select_sweeps", "sweep_params", "fuse_sweeps",
            "build_nuscenes_batch", "build_nuscenes_batch_per_sample", "build_tta_batch"]
@@ -133,21 +133,27 @@ def sweep_params(seq: NuscSequence, index: int, offsets: Sequence[int]) -> np.nd
     return out
 
 
-_tables = {}
+def _nusc_row(pos: int, steps: Sequence[int]) -> List[bool]:
+    """The nuScenes class-step rule (nuscenes_ms.py:320-328) for the selected sweep at position `pos` (0 = oldest): class c is kept
+    iff steps[c] != 0 and (pos + 1) % steps[c] == 0."""
+    return [bool(st) and (pos + 1) % st == 0 for st in steps]
+
+
+def _current_keyframe(points, in_feature_dim=None):
+    """The current keyframe as both clouds hold it: a fresh tensor with the time column 0 (nuscenes_ms.py:109), cut to the first
+    `in_feature_dim` columns if given.  points: one keyframe [n, 5], or a list of them (concatenated)."""
+    cur = torch.cat(points, 0) if isinstance(points, (list, tuple)) else points.clone()
+    cur[:, 4] = 0
+    return cur if in_feature_dim is None else cur[:, :in_feature_dim].contiguous()
 
 
 def _layout(lengths, steps, device):
-    key = (tuple(lengths), tuple(steps), str(device))
-    hit = _tables.get(key)
-    if hit is None:
-        if len(_tables) >= 64:
-            _tables.pop(next(iter(_tables)))
+    """per-layout helpers of one sample, cached (stage._cached): sweep index (int32) of every concatenated sweep point and the
+    [S, C] table of _nusc_row per sweep"""
+    def make():
         idx = torch.repeat_interleave(torch.arange(len(lengths), dtype=torch.int32), torch.tensor(list(lengths))).to(device)
-        table = torch.tensor([[bool(st) and (pos + 1) % st == 0 for st in steps] for pos in range(len(lengths))],
-                             dtype=torch.bool, device=device)
-        hit = (idx, table)
-        _tables[key] = hit
-    return hit
+        return idx, torch.tensor([_nusc_row(pos, steps) for pos in range(len(lengths))], dtype=torch.bool, device=device)
+    return _cached(("nusc-layout", tuple(lengths), tuple(steps), str(device)), make)
 
 
 def fuse_sweeps(cur_pts, cur_lab, hist_pts: List[torch.Tensor], hist_lab: List[torch.Tensor],
@@ -157,8 +163,7 @@ def fuse_sweeps(cur_pts, cur_lab, hist_pts: List[torch.Tensor], hist_lab: List[t
     column 0, :109), then the sweeps oldest first, each without its ego-box points and filtered by the class-step rule.
     hist_lab[i]: mapped labels of a keyframe, zeros for a sweep (:297, :318); hist_pseudo[i]: pseudo labels (:323)."""
     dev = cur_pts.device
-    cur = cur_pts.clone()
-    cur[:, 4] = 0
+    cur = _current_keyframe(cur_pts)
     n_cur = cur.shape[0]
     if not hist_pts:
         return cur, cur_lab.long(), torch.ones(n_cur, dtype=torch.bool, device=dev)
@@ -177,27 +182,21 @@ def build_nuscenes_batch(samples: List[Dict], voxel_size: float, steps: Sequence
     params [S,28] float64 tensor, name).  Returns the collated batch_dict MinkUNetMs consumes
     (nuscenes_voxel_ms.py:77-212 == the SemanticKITTI stage on the first `in_feature_dim` columns).
     The whole batch goes through ONE chain of launches: one ts_fuse_sweeps over every sweep point of every sample (ego box,
-    sensor -> keyframe -> current-frame transforms, time delta), the class-step rule as one table lookup, then
-    stage.voxelize_batch_ms (one compaction, one batch-keyed voxelisation per cloud kind).
+    sensor -> keyframe -> current-frame transforms, time delta), the class-step rule (_nusc_row, stage._step_table) as one table
+    lookup, then stage.voxelize_batch_ms (one compaction, one batch-keyed voxelisation per cloud kind).
     aug: one AugParams per sample (data/augment.py) or None = the un-augmented path.  With it the current keyframes and all fused sweep
     rows are augmented in place (one ts_stage_augment launch each, the sweep rows through their sweep index) before the clamp."""
-    from . import stage as _stage
     if not _stage._BATCHED or not samples or len(samples) > 64:
         return build_nuscenes_batch_per_sample(samples, voxel_size, steps, in_feature_dim, aug=aug)
     dev = samples[0]["points"].device
     f = in_feature_dim
     n_cls = len(steps)
-    cur_all = torch.cat([s["points"] for s in samples], 0)          # (a fresh tensor: the resident scans stay untouched)
-    cur_all[:, 4] = 0                                                 # time column of the current keyframe (:109)
+    cur_f = _current_keyframe([s["points"] for s in samples], f)     # (one fresh tensor: the resident scans stay untouched)
     n_cur = [int(s["points"].shape[0]) for s in samples]
-    cur_f = cur_all[:, :f].contiguous()
-    rec = None if aug is None else _stage._aug_records(aug, len(samples))
+    rec = None if aug is None else _aug_records(aug, len(samples))
     if rec is not None:
-        augment_points(cur_f, rec, _stage.rows_index32(n_cur, dev), out=cur_f)
-    cuts = [0]
-    for n in n_cur:
-        cuts.append(cuts[-1] + n)
-    cur_list = [cur_f[a:b] for a, b in zip(cuts[:-1], cuts[1:])]
+        augment_points(cur_f, rec, rows_index32(n_cur, dev), out=cur_f)
+    cur_list = list(torch.split(cur_f, n_cur))
     lab_list = [s["labels"].long() for s in samples]
     hp, hl, hs, lengths, sample_of_sweep, rows, params = [], [], [], [], [], [], []
     for b, s in enumerate(samples):
@@ -205,7 +204,7 @@ def build_nuscenes_batch(samples: List[Dict], voxel_size: float, steps: Sequence
             hp.append(p)
             lengths.append(int(p.shape[0]))
             sample_of_sweep.append(b)
-            rows.append([bool(st) and (pos + 1) % st == 0 for st in steps])           # nuscenes_ms.py:320-328
+            rows.append(_nusc_row(pos, steps))
         hl += list(s["hist_labels"])
         hs += list(s["hist_pseudo"])
         if len(s["hist_points"]):
@@ -214,15 +213,8 @@ def build_nuscenes_batch(samples: List[Dict], voxel_size: float, steps: Sequence
         stack = torch.cat(hp, 0).contiguous()
         pseudo = torch.cat(hs, 0).long()
         lab_h = torch.cat(hl, 0).long()
-        sweep32 = _stage.rows_index32(lengths, dev)
-        key = ("nusc-table", tuple(map(tuple, rows)), tuple(sample_of_sweep), str(dev))
-        hit = _tables.get(key)
-        if hit is None:
-            if len(_tables) >= 64:
-                _tables.pop(next(iter(_tables)))
-            hit = (torch.tensor(rows, dtype=torch.bool).to(dev), torch.tensor(sample_of_sweep, dtype=torch.int64).to(dev))
-            _tables[key] = hit
-        table, sample_of = hit
+        sweep32 = rows_index32(lengths, dev)
+        table, sample_of = _step_table("nusc-table", rows, sample_of_sweep, dev)
         fused, no_ego = B.fuse_sweeps(stack, sweep32, torch.cat(params, 0) if len(params) > 1 else params[0])
         hist_ms = fused[:, :f].contiguous()
         if rec is not None:
@@ -234,22 +226,19 @@ def build_nuscenes_batch(samples: List[Dict], voxel_size: float, steps: Sequence
         no_ego = None
         table = torch.zeros((1, n_cls), dtype=torch.bool, device=dev)
         sample_of = torch.zeros(1, dtype=torch.int64, device=dev)
-    return _stage.voxelize_batch_ms(cur_list, lab_list, cur_f, hist_ms, lab_h, sweep32, pseudo, table, sample_of, voxel_size,
-                                    [s.get("name", "") for s in samples], pre_keep=no_ego)
+    return voxelize_batch_ms(cur_list, lab_list, cur_f, hist_ms, lab_h, sweep32, pseudo, table, sample_of, voxel_size,
+                             [s.get("name", "") for s in samples], pre_keep=no_ego)
 
 
 def build_nuscenes_batch_per_sample(samples: List[Dict], voxel_size: float, steps: Sequence[int], in_feature_dim: int = 4,
                                     aug=None) -> Dict:
     """build_nuscenes_batch sample by sample (the form the batched stage replaced; its cross-check and TASEG_STAGE_BATCHED=0)"""
-    from . import stage as _stage
     out = []
-    rec = None if aug is None else _stage._aug_records(aug, len(samples))
+    rec = None if aug is None else _aug_records(aug, len(samples))
     for b, s in enumerate(samples):
         raw, lab, keep = fuse_sweeps(s["points"], s["labels"], s["hist_points"], s["hist_labels"], s["hist_pseudo"],
                                      s["params"], steps)
-        cur = s["points"].clone()
-        cur[:, 4] = 0
-        out.append(voxelize_sample_ms(cur[:, :in_feature_dim].contiguous(), s["labels"].long(),
+        out.append(voxelize_sample_ms(_current_keyframe(s["points"], in_feature_dim), s["labels"].long(),
                                       raw[:, :in_feature_dim].contiguous(), lab, voxel_size, s.get("name", ""), keep=keep,
                                       aug=None if rec is None else rec[b:b + 1]))
     return collate_batch(out)

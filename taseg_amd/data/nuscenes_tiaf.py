@@ -16,7 +16,8 @@ nuscenes_voxel_ms_mm.py:77-262, next to the nuScenes FSA stage of taseg_amd.data
       ts_fuse_sweeps           the kept points into the current lidar frame (:305; float64 product rounded once)
       image                    half-resolution uint8 RGB -> float32 BGR / 255, the two top rows cut (:381-386)
   sample / batch               the three clouds (current, fused, FOV) voxelised with ONE coordinate shift, the FOV cloud
-                               clamped to the current cloud's corner; sparse collate + image stacks as NCHW + offset_img
+                               clamped to the current cloud's corner (stage.voxelize_fov); sparse collate + image stacks
+                               as NCHW + offset_img
 
 File decoding (JPEG, .npy semantic maps) and PIL's bilinear half-size resize (:380) stay on the host, as in the reference:
 the stage starts from resident half-resolution uint8 images.  Bit-exact against the reference's dataset code:
@@ -29,8 +30,9 @@ import torch
 
 from .. import backend as B
 from ..torchsparse import SparseTensor
-from .nuscenes import NuscSequence, fuse_sweeps, relative_transform, rotation_matrix
-from .stage import _quantize, collate_batch, voxelize_sample_ms
+from .nuscenes import NuscSequence, _current_keyframe, fuse_sweeps, relative_transform, rotation_matrix
+from .stage import collate_batch, voxelize_fov, voxelize_sample_ms
+from .tiaf import bgr_unit
 
 __all__ = ["select_image_keyframes", "camera_chain", "frame_cloud", "fov_points", "half_image", "build_nusc_tiaf_sample",
            "build_nusc_tiaf_batch"]
@@ -133,18 +135,9 @@ def fov_points(cloud: torch.Tensor, labels: torch.Tensor, cam: torch.Tensor, ima
     return torch.cat([pts[keep], pix[keep]], 1), labels[keep]
 
 
-_lut = {}
-
-
 def half_image(image_u8: torch.Tensor, crop_top: int = 2) -> torch.Tensor:
-    """[h, w, 3] uint8 RGB at half resolution -> float32 BGR / 255 without the top rows (:381-386); the 256 quotients come
-    from a table of correctly rounded float32 divisions (see taseg_amd.data.tiaf.crop_image)."""
-    if image_u8.dtype != torch.uint8:
-        raise TypeError("camera images must be uint8")
-    lut = _lut.get(image_u8.device)
-    if lut is None:
-        lut = _lut[image_u8.device] = torch.from_numpy(np.arange(256, dtype=np.float32) / 255.).to(image_u8.device)
-    return lut[image_u8.flip(2).long()][crop_top:].contiguous()
+    """[h, w, 3] uint8 RGB at half resolution -> float32 BGR / 255 (taseg_amd.data.tiaf.bgr_unit) without the top rows (:381-386)"""
+    return bgr_unit(image_u8)[crop_top:].contiguous()
 
 
 def build_nusc_tiaf_sample(fsa: Dict, seq: NuscSequence, index: int, key_points: Dict[int, torch.Tensor],
@@ -193,19 +186,12 @@ def build_nusc_tiaf_sample(fsa: Dict, seq: NuscSequence, index: int, key_points:
     # the single-frame and fused clouds: the FSA stage (voxel_ms_mm.py:80-87, 127-186 == nuscenes_voxel_ms.py)
     raw, lab_all, keep = fuse_sweeps(fsa["points"], fsa["labels"], fsa["hist_points"], fsa["hist_labels"], fsa["hist_pseudo"],
                                      fsa["params"], steps)
-    cur = fsa["points"].clone()
-    cur[:, 4] = 0
-    point = cur[:, :in_feature_dim].contiguous()
+    point = _current_keyframe(fsa["points"], in_feature_dim)
     sample = voxelize_sample_ms(point, fsa["labels"].long(), raw[:, :in_feature_dim].contiguous(), lab_all, voxel_size, name,
                                 keep=keep, return_shift=True)
-    lo = point[:, :3].t().contiguous().min(1).values
-    inside = (fov[:, :3] >= lo).all(1)                                   # clamp_fov_mask (:133-135)
-    fov, fov_lab = fov[inside].contiguous(), fov_lab[inside]
-    shift = sample.pop("_shift")
-    pc_fov, _, inds_fov, _ = _quantize(fov, voxel_size, shift=shift)
-    sample["lidar_fov_ms"] = SparseTensor(fov[inds_fov], pc_fov[inds_fov])
+    fov_lab = voxelize_fov(sample, point, fov, voxel_size, fov_lab)     # clamp_fov_mask (:133-135), lidar_fov_ms
     # (the reference pairs the FOV labels with the FUSED cloud's coordinates, :204 - kept as it is)
-    sample["targets_fov_ms"] = SparseTensor(fov_lab[inds_fov], sample["lidar_ms"].C)
+    sample["targets_fov_ms"] = SparseTensor(fov_lab, sample["lidar_ms"].C)
     sample["image_ms"] = torch.stack(images, 0)
     sample["semantic_map_ms"] = torch.stack(semantic, 0)
     n_img = len(images)

@@ -5,7 +5,7 @@ The reference does this in numpy inside DataLoader workers
 semantickitti_voxel_ms.py:77-212); here the same steps run on the GPU on resident scans:
 
   pose fuse            ts_fuse_scan        p' = ((p R_t^T + t_t) - t_0) R_0, float32, reference summation order
-  class-step filter    lookup table        keep a history point iff steps[class] != 0 and |delta| % steps[class] == 0
+  class-step filter    lookup table        one _kitti_row per history scan, looked up with the point's (pseudo) class
   concat + time flag   torch.cat           current scan first (flag 1), kept history points after it (flag 0)
   scan mixing (mix=)   ts_stage_mix        PolarMix / LaserMix with a partner scan (data/mix.py), on the single-frame pair and on the
                                            fused pair, before the augmentation (semantickitti_ms.py:151-237)
@@ -17,6 +17,7 @@ semantickitti_voxel_ms.py:77-212); here the same steps run on the GPU on residen
 Outputs have the reference's exact layout and ORDER (batch_dict schema of SURVEY.md appendix C), checked bit
 for bit against the reference dataset code in tests (tests/golden/multiscan.npz).
 """
+from itertools import accumulate
 from typing import Dict, List, Sequence
 
 import numpy as np
@@ -31,26 +32,60 @@ from ..options import options
 __all__ = ["fuse_multiscan", "voxelize_sample_ms", "voxelize_sample", "collate_batch", "build_multiscan_batch",
            "build_multiscan_batch_per_sample", "build_tta_batch", "voxelize_batch_ms", "rows_index", "DevicePrefetcher"]
 
+_BATCHED = options.stage_batched
+_cache = {}
 
-_static_cache = {}
+
+def _cached(key, make):
+    """make() once per key: the device tensors that depend only on a batch's layout (scan lengths, schedule), for every dataset's
+    stage.  The last 64 are kept, the oldest dropped - resident synthetic scans repeat their layout every step, so theirs cost
+    no upload after the first."""
+    hit = _cache.get(key)
+    if hit is None:
+        hit = make()                   # (may itself go through _cached: the size is checked after it)
+        if len(_cache) >= 64:
+            _cache.pop(next(iter(_cache)))
+        _cache[key] = hit
+    return hit
+
+
+def rows_index(lengths: Sequence[int], device) -> torch.Tensor:
+    """int64 [sum(lengths)]: the index of the segment every concatenated row belongs to (built on the device from the lengths,
+    cached per layout)"""
+    def make():
+        lens = torch.tensor(list(lengths), dtype=torch.int64).to(device, non_blocking=True)
+        return torch.repeat_interleave(torch.arange(len(lengths), dtype=torch.int64, device=device), lens,
+                                       output_size=int(sum(lengths)))
+    return _cached((tuple(lengths), str(device)), make)
+
+
+def rows_index32(lengths: Sequence[int], device) -> torch.Tensor:
+    """rows_index as int32 (what ts_voxel_coords takes), cached beside it"""
+    return _cached(("i32", tuple(lengths), str(device)), lambda: rows_index(lengths, device).int())
+
+
+def _kitti_row(delta: int, steps: Sequence[int]) -> List[bool]:
+    """The SemanticKITTI class-step rule (semantickitti_ms.py:303-308) for one history scan: class c is aggregated from the scan
+    `delta` frames away iff steps[c] != 0 and |delta| % steps[c] == 0.  Last column: pseudo class -1 = a label that is no class's
+    canonical raw id (e.g. a moving-object id): never kept."""
+    return [bool(st) and abs(delta) % st == 0 for st in steps] + [False]
+
+
+def _step_table(tag: str, rows, owner, device):
+    """(table bool [S, C], owner int64 [S]) on the device, cached: rows[s] = the class-step row of history scan / sweep s (either
+    dataset's rule; `tag` keeps their keys apart), owner[s] = the sample it belongs to"""
+    return _cached((tag, tuple(map(tuple, rows)), tuple(owner), str(device)),
+                   lambda: (torch.tensor(rows, dtype=torch.bool).to(device), torch.tensor(owner, dtype=torch.int64).to(device)))
 
 
 def _history_index(lengths: Sequence[int], deltas: Sequence[int], steps: Sequence[int], device):
-    """Per-layout helpers that depend only on the scan lengths and the schedule, cached: scan index of every
-    concatenated history point, and the [T, C] table "is class c aggregated from the scan delta frames away"
-    (semantickitti_ms.py:303-308: steps[c] != 0 and |delta| % steps[c] == 0)."""
-    key = (tuple(lengths), tuple(deltas), tuple(steps), str(device))
-    hit = _static_cache.get(key)
-    if hit is None:
-        if len(_static_cache) >= 64:
-            _static_cache.pop(next(iter(_static_cache)))
+    """Per-layout helpers of one sample, cached: scan index (int32) of every concatenated history point, and the [T, C + 1] table of
+    _kitti_row per history scan."""
+    def make():
         scan_idx = torch.repeat_interleave(torch.arange(len(lengths), dtype=torch.int32),
                                            torch.tensor(list(lengths), dtype=torch.int64)).to(device)
-        # last column: pseudo class -1 = a label that is no class's canonical raw id (e.g. a moving-object id): never kept
-        table = torch.tensor([[bool(st) and abs(d) % st == 0 for st in steps] + [False] for d in deltas], dtype=torch.bool)
-        hit = (scan_idx, table.to(device))
-        _static_cache[key] = hit
-    return hit
+        return scan_idx, torch.tensor([_kitti_row(d, steps) for d in deltas], dtype=torch.bool).to(device)
+    return _cached(("history", tuple(lengths), tuple(deltas), tuple(steps), str(device)), make)
 
 
 def _fuse_history(cur_pts, cur_lab, hist_pts, hist_lab, pose0, hist_poses, deltas, steps, hist_pseudo=None):
@@ -150,10 +185,36 @@ def voxelize_sample_ms(points, labels, points_ms, labels_ms, voxel_size, name=""
     }
 
 
+def voxelize_fov(sample: Dict, point, fov, voxel_size, fov_labels=None):
+    """The camera samples' third cloud (semantickitti_voxel_ms_mm.py:124-204 / nuscenes_voxel_ms_mm.py:133-204): `fov` [m, 6] clamped
+    to the corner of the single-frame cloud `point`, rounded and shifted like the other two - `sample` is voxelize_sample_ms's with
+    return_shift=True, whose "_shift" is taken out - and grouped per voxel into sample["lidar_fov_ms"].  Returns fov_labels of the
+    voxels' representatives (None without labels)."""
+    lo = point[:, :3].t().contiguous().min(1).values       # (row-wise minimum of the transposed copy: see voxelize_sample_ms)
+    inside = (fov[:, :3] >= lo).all(1)
+    fov = fov[inside].contiguous()
+    if fov_labels is not None:
+        fov_labels = fov_labels[inside]
+    pc_fov, _, inds_fov, _ = _quantize(fov, voxel_size, shift=sample.pop("_shift"))
+    sample["lidar_fov_ms"] = SparseTensor(fov[inds_fov], pc_fov[inds_fov])
+    return None if fov_labels is None else fov_labels[inds_fov]
+
+
 def _stack_sparse(items: List[SparseTensor]) -> SparseTensor:
     coords = [torch.cat([t.coords, torch.full((t.coords.shape[0], 1), b, dtype=torch.int32, device=t.coords.device)], 1)
               for b, t in enumerate(items)]
     return SparseTensor(torch.cat([t.feats for t in items], 0), torch.cat(coords, 0).contiguous(), items[0].stride)
+
+
+def _prefix_mask(n_cur: Sequence[int], n_ms: Sequence[int], device) -> torch.Tensor:
+    """point_mask (semantickitti_voxel_ms.py:204-210): bool [sum(n_ms)], true on the first n_cur[b] rows of every fused cloud - the
+    current frame where it is the fused cloud's prefix"""
+    mask = torch.zeros(sum(n_ms), dtype=torch.bool, device=device)
+    at = 0
+    for a, m in zip(n_cur, n_ms):
+        mask[at:at + a] = True
+        at += m
+    return mask
 
 
 def collate_batch(samples: List[Dict]) -> Dict:
@@ -173,14 +234,7 @@ def collate_batch(samples: List[Dict]) -> Dict:
             sizes = torch.tensor([s["lidar" + sfx].coords.shape[0] for s in samples])
             out["offset" + sfx] = torch.cumsum(sizes, 0).int().to(dev)
     if "num_points_ms" in out:
-        n_ms = [int(s["num_points_ms"]) for s in samples]
-        n_cur = [int(s["num_points"]) for s in samples]
-        mask = torch.zeros(sum(n_ms), dtype=torch.bool, device=dev)
-        cur = 0
-        for a, b in zip(n_cur, n_ms):
-            mask[cur:cur + a] = True          # the current frame is the prefix of every fused cloud
-            cur += b
-        out["point_mask"] = mask
+        out["point_mask"] = _prefix_mask([int(s["num_points"]) for s in samples], [int(s["num_points_ms"]) for s in samples], dev)
     return out
 
 
@@ -208,13 +262,14 @@ def _mix_records(mix, partners, n_samples):
 
 
 def _fused_cloud(s, steps):
-    """(current scan [n, 4], its labels, fused cloud [m, 5] after the class-step filter, its labels) of one scan dict: what the
-    reference's `__getitem__` holds when it reaches the mix (semantickitti_ms.py:140-149), for a sample and for its partner alike"""
+    """(current scan, its labels, un-filtered stack [current | history] [m, 5], its labels, keep mask) of one scan dict;
+    stack[keep] is the fused cloud the reference's `__getitem__` holds when it reaches the mix (semantickitti_ms.py:140-149), for a
+    sample and for its partner alike"""
     pts, lab, poses = s["points"], s["labels"], s["poses"]
     t = len(pts) - 1
     deltas = s.get("deltas") or [i - t for i in range(t)]
     raw_all, lab_all, keep = _fuse_history(pts[t], lab[t], pts[:t], lab[:t], poses[t], poses[:t], deltas, steps, s.get("pseudo"))
-    return pts[t][:, :4], lab[t].long(), raw_all[keep], lab_all[keep]
+    return pts[t], lab[t].long(), raw_all, lab_all, keep
 
 
 def build_multiscan_batch_per_sample(scans: List[Dict], voxel_size: float, steps: Sequence[int], aug=None, mix=None,
@@ -227,46 +282,22 @@ def build_multiscan_batch_per_sample(scans: List[Dict], voxel_size: float, steps
         mix, partners = _mix_records(mix, partners, len(scans))
     for b, s in enumerate(scans):
         one = None if rec is None else rec[b:b + 1]
-        if mix is not None and mix[b].kind != M.NONE:
-            cur, lab, raw, lab_ms = _fused_cloud(s, steps)
-            if partners[b] is None:
-                pcur, plab, praw, plab_ms = cur[:0], lab[:0], raw[:0], lab_ms[:0]
-            else:
-                pcur, plab, praw, plab_ms = _fused_cloud(partners[b], steps)
-            # the same record on the single-frame pair and on the fused pair (semantickitti_ms.py:182-185, :221-234)
-            cur, lab = M.mix_points(cur, lab, pcur, plab, mix[b])
-            raw, lab_ms = M.mix_points(raw, lab_ms, praw, plab_ms, mix[b])
-            samples.append(voxelize_sample_ms(cur, lab, raw, lab_ms, voxel_size, s.get("name", ""), aug=one))
+        cur, lab, raw, lab_ms, keep = _fused_cloud(s, steps)
+        if mix is None or mix[b].kind == M.NONE:
+            # (the class-step filter rides on the clamp's compaction)
+            samples.append(voxelize_sample_ms(cur, lab, raw, lab_ms, voxel_size, s.get("name", ""), keep=keep, aug=one))
             continue
-        pts, lab, poses = s["points"], s["labels"], s["poses"]
-        t = len(pts) - 1
-        deltas = s.get("deltas") or [i - t for i in range(t)]
-        raw_all, lab_all, keep = _fuse_history(pts[t], lab[t], pts[:t], lab[:t], poses[t], poses[:t], deltas, steps,
-                                               s.get("pseudo"))
-        samples.append(voxelize_sample_ms(pts[t], lab[t].long(), raw_all, lab_all, voxel_size, s.get("name", ""),
-                                          keep=keep, aug=one))
+        cur, raw, lab_ms = cur[:, :4], raw[keep], lab_ms[keep]
+        if partners[b] is None:
+            pcur, plab, praw, plab_ms = cur[:0], lab[:0], raw[:0], lab_ms[:0]
+        else:
+            pcur, plab, praw, plab_ms, pkeep = _fused_cloud(partners[b], steps)
+            pcur, praw, plab_ms = pcur[:, :4], praw[pkeep], plab_ms[pkeep]
+        # the same record on the single-frame pair and on the fused pair (semantickitti_ms.py:182-185, :221-234)
+        cur, lab = M.mix_points(cur, lab, pcur, plab, mix[b])
+        raw, lab_ms = M.mix_points(raw, lab_ms, praw, plab_ms, mix[b])
+        samples.append(voxelize_sample_ms(cur, lab, raw, lab_ms, voxel_size, s.get("name", ""), aug=one))
     return collate_batch(samples)
-
-
-import os as _os
-
-_BATCHED = options.stage_batched
-_rows_cache = {}
-
-
-def rows_index(lengths: Sequence[int], device) -> torch.Tensor:
-    """int64 [sum(lengths)]: the index of the segment every concatenated row belongs to (built on the device from the lengths;
-    a few layouts are kept - resident synthetic scans repeat theirs every step)"""
-    key = (tuple(lengths), str(device))
-    hit = _rows_cache.get(key)
-    if hit is None:
-        if len(_rows_cache) >= 64:
-            _rows_cache.pop(next(iter(_rows_cache)))
-        total = int(sum(lengths))
-        lens = torch.tensor(list(lengths), dtype=torch.int64).to(device, non_blocking=True)
-        hit = torch.repeat_interleave(torch.arange(len(lengths), dtype=torch.int64, device=device), lens, output_size=total)
-        _rows_cache[key] = hit
-    return hit
 
 
 def voxelize_batch_ms(cur_list: List[torch.Tensor], lab_list: List[torch.Tensor], cur_ms: torch.Tensor, hist_pts: torch.Tensor,
@@ -298,10 +329,7 @@ def voxelize_batch_ms(cur_list: List[torch.Tensor], lab_list: List[torch.Tensor]
         lo = B.segment_min3(cur, cur_b, nb)        # minimum of every current scan: the fused cloud is clamped to it (:121-124)
         keep, hist_b = B.stage_keep_flags(hist_pts, hist_scan, hist_cls, table, sample_of_scan, lo, pre_keep=pre_keep, neg_col=neg_col)
         idx = keep.nonzero().squeeze(1)                                 # host read 1 (the compaction's size)
-        cuts = [0]
-        for n in n_cur:
-            cuts.append(cuts[-1] + n)
-        cur_start = torch.tensor(cuts, dtype=torch.int64).to(dev, non_blocking=True)
+        cur_start = torch.tensor(list(accumulate(n_cur, initial=0)), dtype=torch.int64).to(dev, non_blocking=True)
         kept_start = torch.searchsorted(hist_b[idx], torch.arange(nb + 1, device=dev))
         ms_pts, ms_lab, ms_b, ms_b32, point_mask = B.stage_layout(cur_ms, cur_lab, cur_b, hist_pts, hist_lab, hist_b, idx, cur_start,
                                                                   kept_start)
@@ -337,51 +365,47 @@ def _voxelize_layout(cur, cur_lab, cur_b, n_cur, ms_pts, ms_lab, ms_b, ms_b32, n
     }
 
 
-def rows_index32(lengths: Sequence[int], device) -> torch.Tensor:
-    """rows_index as int32 (what ts_voxel_coords takes), cached beside it"""
-    key = ("i32", tuple(lengths), str(device))
-    hit = _rows_cache.get(key)
-    if hit is None:
-        hit = rows_index(lengths, device).int()
-        _rows_cache[key] = hit
-    return hit
+def _walk_scans(clouds: List[Dict], steps: Sequence[int]):
+    """One pass over scan dicts (build_multiscan_batch's `scans[b]`).  Returns the history scans of all of them, flat and in order -
+    (points [:, :4], labels, pseudo classes or the labels where a dict has none, lengths, owner = index of the dict in `clouds`,
+    the owner's current pose per scan, pose, _kitti_row) - and per dict (current scan as stored, its labels int64, first history
+    row, history rows)."""
+    hist_pts, hist_lab, hist_ps, lengths, owner, pose0s, poses, rows = hist = [], [], [], [], [], [], [], []
+    current, n_hist = [], 0
+    for b, s in enumerate(clouds):
+        pts, lab, ps = s["points"], s["labels"], s["poses"]
+        t = len(pts) - 1
+        deltas = s.get("deltas") or [i - t for i in range(t)]
+        pseudo = s.get("pseudo")
+        first = n_hist
+        for i in range(t):
+            hist_pts.append(pts[i][:, :4])
+            hist_lab.append(lab[i])
+            hist_ps.append(lab[i] if pseudo is None else pseudo[i])
+            lengths.append(int(pts[i].shape[0]))
+            owner.append(b)
+            pose0s.append(ps[t])
+            poses.append(ps[i])
+            rows.append(_kitti_row(deltas[i], steps))
+            n_hist += lengths[-1]
+        current.append((pts[t], lab[t].long(), first, n_hist - first))
+    return hist, current
 
 
 def _build_multiscan_batch_mix(scans, partners, mix, voxel_size, steps, aug) -> Dict:
-    """build_multiscan_batch with mix=: the samples' and the partners' history scans pose-fused in ONE launch, the class-step rule
+    """build_multiscan_batch with mix=: the samples' and the partners' history scans (_walk_scans) pose-fused in ONE launch, the class-step rule
     as a keep byte per row (no compaction of its own), ts_stage_mix on the single-frame pairs and on the fused pairs of the whole
     batch (three launches each, their row counts in one host read), the augmentation, the clamp of EVERY fused row against the
     mixed single-frame cloud's minimum (after a mix the current scan is no prefix of the fused cloud any more;
     semantickitti_voxel_ms.py:121-124), one compaction, both voxelisations.  point_mask stays what the reference's collate_batch
-    makes it: the first num_points rows of every fused cloud (:204-210)."""
+    makes it (_prefix_mask)."""
     dev = scans[0]["points"][-1].device
     nb, n_cls = len(scans), len(steps)
-    hist_pts, hist_lab, hist_ps, lengths, pose0s, poses, rows = [], [], [], [], [], [], []
-    clouds = []                        # per sample: [own cloud, partner cloud or None]; a cloud = (cur4, labels, first history row, rows)
-    n_hist = 0
     any_pseudo = any(c is not None and c.get("pseudo") is not None for c in list(scans) + list(partners))
-    for b, s in enumerate(scans):
-        pair = []
-        for c in (s, partners[b] if mix[b].kind != M.NONE else None):
-            if c is None:
-                pair.append(None)
-                continue
-            pts, lab, ps = c["points"], c["labels"], c["poses"]
-            t = len(pts) - 1
-            deltas = c.get("deltas") or [i - t for i in range(t)]
-            pseudo = c.get("pseudo")
-            first = n_hist
-            for i in range(t):
-                hist_pts.append(pts[i][:, :4])
-                hist_lab.append(lab[i])
-                hist_ps.append(lab[i] if pseudo is None else pseudo[i])
-                lengths.append(int(pts[i].shape[0]))
-                pose0s.append(ps[t])
-                poses.append(ps[i])
-                rows.append([bool(st) and abs(deltas[i]) % st == 0 for st in steps] + [False])   # semantickitti_ms.py:303-308
-                n_hist += lengths[-1]
-            pair.append((pts[t][:, :4], lab[t].long(), first, n_hist - first))
-        clouds.append(pair)
+    # the clouds that take part, in order: every sample's own, then its partner's where its mix moves rows of one
+    used = [[s, partners[b] if mix[b].kind != M.NONE else None] for b, s in enumerate(scans)]
+    (hist_pts, hist_lab, hist_ps, lengths, _, pose0s, poses, rows), current = _walk_scans(
+        [c for pair in used for c in pair if c is not None], steps)
     if hist_pts:
         hp = torch.cat(hist_pts, 0).contiguous()
         hl = torch.cat(hist_lab, 0).long()
@@ -399,15 +423,17 @@ def _build_multiscan_batch_mix(scans, partners, mix, voxel_size, steps, aug) -> 
     # history] for the fused one
     s_pts, s_lab, s_n1, s_n2 = [], [], [], []
     m_pts, m_lab, m_keep, m_len, m_n1, m_n2 = [], [], [], [], [], []
-    ones = torch.ones(max([c[0].shape[0] for pair in clouds for c in pair if c is not None] + [1]), dtype=torch.bool, device=dev)
-    for pair in clouds:
+    ones = torch.ones(max([c[0].shape[0] for c in current] + [1]), dtype=torch.bool, device=dev)
+    current = iter(current)
+    for pair in used:
         sizes = []
         for c in pair:
             if c is None:
                 sizes.append((0, 0))
                 m_len += [0, 0]
                 continue
-            cur4, lab, first, nh = c
+            scan, lab, first, nh = next(current)
+            cur4 = scan[:, :4]
             n = int(cur4.shape[0])
             s_pts.append(cur4)
             s_lab.append(lab)
@@ -439,12 +465,7 @@ def _build_multiscan_batch_mix(scans, partners, mix, voxel_size, steps, aug) -> 
     ms, ms_lab, ms_b, ms_b32 = ms[idx].contiguous(), ms_lab[idx], ms_b[idx], ms_b32[idx]
     start = torch.searchsorted(ms_b, torch.arange(nb + 1, device=dev))
     n_ms = (start[1:] - start[:-1]).tolist()                            # host read 3 (fused rows per sample)
-    point_mask = torch.zeros(sum(n_ms), dtype=torch.bool, device=dev)
-    at = 0
-    for a, m in zip(n_cur, n_ms):
-        point_mask[at:at + a] = True
-        at += m
-    return _voxelize_layout(cur, cur_lab, cur_b, n_cur, ms, ms_lab, ms_b, ms_b32, n_ms, point_mask, voxel_size,
+    return _voxelize_layout(cur, cur_lab, cur_b, n_cur, ms, ms_lab, ms_b, ms_b32, n_ms, _prefix_mask(n_cur, n_ms, dev), voxel_size,
                             [s.get("name", "") for s in scans])
 
 
@@ -452,8 +473,8 @@ def build_multiscan_batch(scans: List[Dict], voxel_size: float, steps: Sequence[
     """scans[b] = dict(points=[T+1 tensors, current LAST], labels=[...], poses=[...], name=str
     [, deltas=[frame offsets of the history scans], pseudo=[pseudo classes of the history scans, see _fuse_history]]).
     Returns the collated batch_dict MinkUNetMs consumes.  The whole batch goes through ONE chain of launches: one pose-fuse
-    launch over every history point of every sample (ts_fuse_scans_batch), the class-step rule as one table lookup, then
-    voxelize_batch_ms.
+    launch over every history point of every sample of _walk_scans (ts_fuse_scans_batch), the class-step rule as one table
+    lookup (_step_table), then voxelize_batch_ms.
     aug: one AugParams per sample (data/augment.py) or None.  With it the current scans and ALL pose-fused history rows are
     augmented in place, one ts_stage_augment launch each (the history rows pick their sample's record through their scan index),
     before the clamp minima are taken - two launches and one small host-to-device copy more than aug=None, the un-augmented path.
@@ -468,30 +489,13 @@ def build_multiscan_batch(scans: List[Dict], voxel_size: float, steps: Sequence[
         return _build_multiscan_batch_mix(scans, partners, mix, voxel_size, steps, aug)
     dev = scans[0]["points"][-1].device
     n_cls = len(steps)
-    cur_list, lab_list, hist_pts, hist_lab, hist_ps, lengths, scan_sample, pose0s, poses, rows = [], [], [], [], [], [], [], [], [], []
-    for b, s in enumerate(scans):
-        pts, lab, ps = s["points"], s["labels"], s["poses"]
-        t = len(pts) - 1
-        deltas = s.get("deltas") or [i - t for i in range(t)]
-        cur_list.append(pts[t][:, :4] if pts[t].shape[1] != 4 else pts[t])
-        lab_list.append(lab[t].long())
-        pseudo = s.get("pseudo")
-        for i in range(t):
-            hist_pts.append(pts[i][:, :4])
-            hist_lab.append(lab[i])
-            hist_ps.append(lab[i] if pseudo is None else pseudo[i])
-            lengths.append(int(pts[i].shape[0]))
-            scan_sample.append(b)
-            pose0s.append(ps[t])
-            poses.append(ps[i])
-            # semantickitti_ms.py:303-308: class c is aggregated from the scan delta frames away iff steps[c] != 0 and
-            # |delta| % steps[c] == 0; last column: pseudo class -1 (no class's canonical raw id): never kept
-            rows.append([bool(st) and abs(deltas[i]) % st == 0 for st in steps] + [False])
-    cur4 = torch.cat(cur_list, 0)
-    cur_in = [s["points"][-1] for s in scans]
+    (hist_pts, hist_lab, hist_ps, lengths, scan_sample, pose0s, poses, rows), current = _walk_scans(scans, steps)
+    cur_in = [c[0] for c in current]                   # the resident current scans, with all their columns
+    lab_list = [c[1] for c in current]
+    cur4 = torch.cat([c[:, :4] for c in cur_in], 0)
     if aug is not None:
         rec = _aug_records(aug, len(scans))
-        n_cur = [int(c.shape[0]) for c in cur_list]
+        n_cur = [int(c.shape[0]) for c in cur_in]
         # the records of the samples, then one per history scan (its sample's): ONE upload for both launches
         rec_dev = torch.from_numpy(np.concatenate([rec, rec[np.asarray(scan_sample, dtype=np.int64)]], 0)).to(dev, non_blocking=True)
         # (cur4 is torch.cat's fresh tensor: the resident scans stay untouched)
@@ -502,14 +506,7 @@ def build_multiscan_batch(scans: List[Dict], voxel_size: float, steps: Sequence[
         hp = torch.cat(hist_pts, 0).contiguous()
         hl = torch.cat(hist_lab, 0).long()
         hps = hl if all(s.get("pseudo") is None for s in scans) else torch.cat(hist_ps, 0).long()
-        key = ("kitti-table", tuple(map(tuple, rows)), tuple(scan_sample), str(dev))
-        hit = _static_cache.get(key)
-        if hit is None:
-            if len(_static_cache) >= 64:
-                _static_cache.pop(next(iter(_static_cache)))
-            hit = (torch.tensor(rows, dtype=torch.bool).to(dev), torch.tensor(scan_sample, dtype=torch.int64).to(dev))
-            _static_cache[key] = hit
-        table, sample_of_scan = hit
+        table, sample_of_scan = _step_table("kitti-table", rows, scan_sample, dev)
         scan32 = rows_index32(lengths, dev)
         fused = B.fuse_scans_batch(hp, scan32, torch.stack(pose0s, 0), torch.stack(poses, 0))
         if aug is not None:

@@ -9,19 +9,20 @@ semantickitti_voxel_ms_mm.py:79-266, next to the LiDAR multi-scan stage of taseg
       image             uint8 RGB -> float32 BGR / 255, top-left crop, zero padded to HEIGHT x WIDTH (:432-447)
   sample                ring id column of the single-frame cloud (:131-141), the three clouds (current, fused, FOV)
                         voxelised with ONE coordinate shift (the fused cloud's minimum), FOV cloud clamped to the current
-                        cloud's corner like the fused one                                       (voxel_ms_mm.py:124-204)
+                        cloud's corner like the fused one (stage.voxelize_fov)                  (voxel_ms_mm.py:124-204)
   batch                 sparse collate + image stacks concatenated along the frame axis as NCHW + offset_img (:223-266)
 
 File decoding (PNG, .npy semantic maps) and the optional colour jitter / flips are outside the scope contract; the stage
 starts from resident uint8 images.  Bit-exact against the reference's dataset code: tests/golden/tiaf_data.npz.
 """
+from functools import lru_cache
 from typing import Dict, List, Sequence
 
+import numpy as np
 import torch
 
 from .. import backend as B
-from ..torchsparse import SparseTensor
-from .stage import _fuse_history, _quantize, collate_batch, voxelize_sample_ms
+from .stage import _fuse_history, collate_batch, voxelize_fov, voxelize_sample_ms
 
 __all__ = ["ring_id", "fov_points", "crop_image", "build_tiaf_sample", "build_tiaf_batch"]
 
@@ -42,20 +43,31 @@ def fov_points(points: torch.Tensor, proj: torch.Tensor, image_size, crop, img_b
     return torch.cat([pts[keep], pix[keep]], 1)
 
 
-_lut = {}
+@lru_cache(maxsize=None)
+def _unit_table(device) -> torch.Tensor:
+    """float32 [256] on `device`: the 256 quotients i / 255 as numpy rounds them (correctly), kept per device"""
+    return torch.from_numpy(np.arange(256, dtype=np.float32) / 255.).to(device)
+
+
+def bgr_unit(image_u8: torch.Tensor) -> torch.Tensor:
+    """[h, w, 3] uint8 RGB -> float32 BGR / 255 (numpy's `image[:, :, ::-1] / 255.`).  The 256 possible quotients come from a table
+    of correctly rounded float32 divisions: the device's division by a scalar is a multiplication by the reciprocal and differs
+    in the last bit."""
+    if image_u8.dtype != torch.uint8:
+        raise TypeError("camera images must be uint8")
+    return _unit_table(image_u8.device)[image_u8.flip(2).long()]
+
+
+def _pad(t: torch.Tensor, crop) -> torch.Tensor:
+    out = torch.zeros((crop[0], crop[1], t.shape[2]), dtype=torch.float32, device=t.device)
+    r, c = min(crop[0], t.shape[0]), min(crop[1], t.shape[1])
+    out[:r, :c] = t[:r, :c]
+    return out
 
 
 def crop_image(image_u8: torch.Tensor, crop) -> torch.Tensor:
-    """[h, w, 3] uint8 RGB -> float32 [HEIGHT, WIDTH, 3] BGR / 255, zero padded (semantickitti_ms_mm.py:432-447).  The 256
-    possible quotients come from a table of correctly rounded float32 divisions (numpy's `image / 255.`): the device's
-    division by a scalar is a multiplication by the reciprocal and differs in the last bit."""
-    if image_u8.dtype != torch.uint8:
-        raise TypeError("camera images must be uint8")
-    lut = _lut.get(image_u8.device)
-    if lut is None:
-        import numpy as np
-        lut = _lut[image_u8.device] = torch.from_numpy(np.arange(256, dtype=np.float32) / 255.).to(image_u8.device)
-    return _pad(lut[image_u8.flip(2).long()], crop)
+    """[h, w, 3] uint8 RGB -> float32 [HEIGHT, WIDTH, 3] BGR / 255 (bgr_unit), zero padded (semantickitti_ms_mm.py:432-447)"""
+    return _pad(bgr_unit(image_u8), crop)
 
 
 def build_tiaf_sample(frames: Dict[int, Dict], steps: Sequence[int], multiscan: int, step_image: int, proj: torch.Tensor,
@@ -87,23 +99,10 @@ def build_tiaf_sample(frames: Dict[int, Dict], steps: Sequence[int], multiscan: 
         fov.append(pts)
         images.append(crop_image(f["image"], crop))
         semantic.append(_pad(f["semantic"].float(), crop))
-    fov = torch.cat(fov, 0)
-    # FOV cloud: clamped to the current cloud's corner, rounded and shifted like the other two, grouped per voxel
-    lo = point[:, :3].t().contiguous().min(1).values       # (row-wise minimum of the transposed copy: see data/stage.py)
-    fov = fov[(fov[:, :3] >= lo).all(1)].contiguous()
-    shift = sample.pop("_shift")
-    pc_fov, _, inds_fov, _ = _quantize(fov, voxel_size, shift=shift)
-    sample["lidar_fov_ms"] = SparseTensor(fov[inds_fov], pc_fov[inds_fov])
+    voxelize_fov(sample, point, torch.cat(fov, 0), voxel_size)           # lidar_fov_ms
     sample["image_ms"] = torch.stack(images, 0)
     sample["semantic_map_ms"] = torch.stack(semantic, 0)
     return sample
-
-
-def _pad(t: torch.Tensor, crop) -> torch.Tensor:
-    out = torch.zeros((crop[0], crop[1], t.shape[2]), dtype=torch.float32, device=t.device)
-    r, c = min(crop[0], t.shape[0]), min(crop[1], t.shape[1])
-    out[:r, :c] = t[:r, :c]
-    return out
 
 
 def build_tiaf_batch(samples: List[Dict]) -> Dict:
