@@ -944,6 +944,50 @@ size_t ts_stage_mix_workspace_bytes(int64_t n_rows, int64_t n_blocks, int32_t n_
 int ts_stage_mix(const float *points, int64_t n_rows, int32_t point_stride, const int64_t *labels, const uint8_t *keep,
                  const double *records, const int32_t *classes, int32_t n_jobs, int64_t n_blocks, float *out, int64_t *out_labels,
                  int32_t *out_job, int64_t capacity, int64_t *totals, void *ws, size_t ws_bytes, ts_stream_t stream);
+/* Moving-object augmentation of the SMSA recipe (csrc/moving.hip; taseg_amd/data/moving.py draws the parameters):
+ * semantickitti_ms_ms.py:305-351 `static2moving` and :353-384 `moving2static`, called at :152-163 for the sample and at :198-207 /
+ * :248-257 for its mix partner, on the current scan and the pose-fused UN-FILTERED history rows, before the class-step mask
+ * (:165), the mix and the augmentation.  Rows of a call, for any number of clouds (samples and partners): points [n_rows,
+ * point_stride >= 2], the n_cur current rows of all clouds first, the history rows behind them; labels [n_rows] the FULL uint32
+ * labels (instance << 16 | raw class) as int64; cloud [n_rows] int32; delta [n_rows] int32 the frame offset of a history row
+ * (time_flag_ms, -1 = the previous frame; not read for current rows).
+ * ts_stage_moving_stats: cand [>= cap] int64 = the candidates, i.e. the distinct full labels of a cloud's current rows with raw
+ * class 18, 20, 253 or 255 (np.unique at :306-307 / :354-355), ascending per cloud, the clouds' tables one after the other;
+ * cand_start [n_clouds + 1] int32 on the DEVICE (nothing about the tables is read on the host; at most cap <=
+ * TS_MOVING_MAX_CANDIDATES are used).  Per candidate k:
+ *   counts [cap, 3] int32   rows of the instance in the current scan (:362), in the history (:315), at delta -1 (:368)
+ *   stats  [cap, TS_MOVING_STATS] float32
+ *          0 .. 3  min x, max x, min y, max y over the history rows (:320; +inf / -inf without one)
+ *          4       mean of the history y (:321)          5, 6  mean x, y of the history rows at delta -1 (:368-370)
+ *          7, 8    mean x, y of the current rows (:367-370)
+ * Every mean is numpy's `column.mean()` of a strided float32 column over the instance's rows IN ROW ORDER: pieces of 8192 terms,
+ * each summed by numpy's pairwise rule in float32 (fewer than 8 terms sequentially from 0; up to 128 eight running sums over groups
+ * of 8 combined ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7)), the remainder sequentially; above, split at n / 2 rounded down
+ * to a multiple of 8), the pieces' sums added in order to 0, / (float)n; 0.f / 0.f = NaN without a row, as numpy.
+ * matched [1] int64: the rows that belong to a candidate; when it exceeds cap_rows (the capacity of the ordered list the means are
+ * taken from) the means are NaN and the caller must enlarge cap_rows.  Counts and min / max use integer atomics (exact); no float
+ * atomics: the same bits every run.
+ * ts_stage_moving_apply (in place on `points`, a copy the caller owns): rec_labels [R] int64 the full labels of the instances
+ * that move, ascending per cloud, rec_start [n_clouds + 1] int32, records [R, TS_MOVING_RECORD] doubles:
+ *   0 kind   1 static2moving along x (:320-336)  2 static2moving along y (:338-344)  3 moving2static (:367-377)  0 nothing
+ *   1 centre shift, signed (-center_shift for center_y > 4, +center_shift for center_y < -2, 0 none): y = y + (float)field
+ *     on the history and the current rows (kind 1)
+ *   2 shift_x / shift_y of kinds 1 / 2 (double): history x (kind 1) or y (kind 2) += (float)((double)delta * field)
+ *   3, 4 shift_x, shift_y of kind 3 (float32 values): history x += (float)delta * shift_x, y likewise, float32 products
+ *   5 the raw class the instance's rows get (258 / 259, :346-349; 31 / 32, :379-382)
+ * out_labels [n_rows] int64 = lut[raw class after the rewrite] for EVERY row (lut: 260 entries, the 26-class map; 0 for a raw
+ * class past the table). */
+#define TS_MOVING_STATS 9
+#define TS_MOVING_RECORD 8
+#define TS_MOVING_MAX_CANDIDATES 1024
+size_t ts_stage_moving_workspace_bytes(int64_t n_rows, int32_t cap, int64_t cap_rows);
+int ts_stage_moving_stats(const float *points, int64_t n_rows, int64_t n_cur, int32_t point_stride, const int64_t *labels,
+                          const int32_t *cloud, const int32_t *delta, const int64_t *cand, const int32_t *cand_start,
+                          int32_t n_clouds, int32_t cap, int64_t cap_rows, int32_t *counts, float *stats, int64_t *matched, void *ws,
+                          size_t ws_bytes, ts_stream_t stream);
+int ts_stage_moving_apply(float *points, int64_t n_rows, int64_t n_cur, int32_t point_stride, const int64_t *labels,
+                          const int32_t *cloud, const int32_t *delta, const int64_t *rec_labels, const int32_t *rec_start,
+                          int32_t n_clouds, const double *records, const int64_t *lut, int64_t *out_labels, ts_stream_t stream);
 size_t ts_quantize_workspace_bytes(int64_t n);
 int ts_sparse_quantize(const int32_t *coords, int64_t n, int32_t *out_index, int32_t *out_inverse,
                        int32_t *out_count, void *ws, size_t ws_bytes, ts_stream_t stream);

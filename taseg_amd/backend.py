@@ -1307,6 +1307,66 @@ def stage_mix(points, labels, params, n1, n2, keep=None, totals=None):
     return out, out_lab, out_job, totals
 
 
+def stage_moving_stats(points, n_cur, labels, cloud, delta, cand, cand_start, cap_rows=None):
+    """csrc/moving.hip: the per-instance statistics of the moving-object augmentation (taseg_amd/data/moving.py) for the clouds of a
+    batch in six launches.  points [N, F >= 2] float32: the n_cur current rows of all clouds, then their pose-fused history rows;
+    labels [N] int64 the FULL labels; cloud, delta [N] int32 (delta: the frame offset of a history row); cand [>= cap] int64 the
+    sorted candidate tables of the clouds one after the other (cap = min(len(cand), 1024)), cand_start [C + 1] int32 on the
+    device.  Returns (counts [cap, 3] int32, stats [cap, 9] float32, matched [1] int64): include/taseg_hip.h.  No host read here:
+    the caller reads cand_start, the tables and `matched` (<= cap_rows, default min(N, 2^20), or the means are not valid) at once."""
+    L.require_device(points, labels, cloud, delta, cand, cand_start)
+    points = _f32(points, "points")
+    if points.ndim != 2 or points.shape[1] < 2:
+        raise TypeError("points must be a float32 [n, F >= 2] tensor")
+    n, f = points.shape
+    cloud, delta, cand_start = _i32(cloud, "cloud"), _i32(delta, "delta"), _i32(cand_start, "cand_start")
+    if labels.dtype != torch.int64 or cand.dtype != torch.int64:
+        raise TypeError("labels and cand must be int64")
+    labels, cand = labels.contiguous(), cand.contiguous()
+    if labels.shape != (n,) or cloud.shape != (n,) or delta.shape != (n,) or not 0 <= int(n_cur) <= n:
+        raise ValueError("stage_moving_stats: one label, cloud and delta per row")
+    cap = min(int(cand.shape[0]), 1024)
+    n_clouds = int(cand_start.shape[0]) - 1
+    if cap < 1 or n_clouds < 1:
+        raise ValueError("stage_moving_stats: cand needs room for a candidate, cand_start one cloud")
+    cap_rows = min(n, 1 << 20) if cap_rows is None else int(cap_rows)
+    dev = points.device
+    counts = torch.empty((cap, 3), dtype=torch.int32, device=dev)
+    stats = torch.empty((cap, 9), dtype=torch.float32, device=dev)
+    matched = torch.empty(1, dtype=torch.int64, device=dev)
+    lib = L.load()
+    ws_bytes = lib.ts_stage_moving_workspace_bytes(n, cap, cap_rows)
+    ws = torch.empty(max(ws_bytes, 256), dtype=torch.uint8, device=dev)
+    L.check(lib.ts_stage_moving_stats(L.ptr(points), n, int(n_cur), f, L.ptr(labels), L.ptr(cloud), L.ptr(delta), L.ptr(cand),
+                                      L.ptr(cand_start), n_clouds, cap, cap_rows, L.ptr(counts), L.ptr(stats), L.ptr(matched),
+                                      L.ptr(ws), ws_bytes, L.stream()), "ts_stage_moving_stats")
+    return counts, stats, matched
+
+
+def stage_moving_apply(points, n_cur, labels, cloud, delta, rec_labels, rec_start, records, lut):
+    """csrc/moving.hip: shift and relabel the rows of the instances that move, IN PLACE on points [N, F >= 2] float32 (a copy the
+    caller owns; rows as in stage_moving_stats), with the uploaded records of taseg_amd.data.moving.pack_moving: rec_labels [R]
+    int64, rec_start [C + 1] int32, records [R, 8] float64; lut [260] int64 the raw class -> class table.  Returns the mapped
+    labels [N] int64 of every row, after the raw-class rewrite.  One launch, no host read."""
+    L.require_device(points, labels, cloud, delta, rec_labels, rec_start, records, lut)
+    if points.dtype != torch.float32 or points.ndim != 2 or points.shape[1] < 2 or not points.is_contiguous():
+        raise TypeError("points must be a contiguous float32 [n, F >= 2] tensor")
+    n, f = points.shape
+    cloud, delta, rec_start = _i32(cloud, "cloud"), _i32(delta, "delta"), _i32(rec_start, "rec_start")
+    if labels.dtype != torch.int64 or rec_labels.dtype != torch.int64 or lut.dtype != torch.int64 or lut.shape != (260,):
+        raise TypeError("labels, rec_labels and lut [260] must be int64")
+    if records.dtype != torch.float64 or records.ndim != 2 or records.shape[1] != 8 or records.shape[0] != rec_labels.shape[0]:
+        raise TypeError("records must be float64 [R, 8], one per record label")
+    labels, rec_labels, records, lut = labels.contiguous(), rec_labels.contiguous(), records.contiguous(), lut.contiguous()
+    if labels.shape != (n,) or cloud.shape != (n,) or delta.shape != (n,) or not 0 <= int(n_cur) <= n:
+        raise ValueError("stage_moving_apply: one label, cloud and delta per row")
+    out = torch.empty(n, dtype=torch.int64, device=points.device)
+    L.check(L.load().ts_stage_moving_apply(L.ptr(points), n, int(n_cur), f, L.ptr(labels), L.ptr(cloud), L.ptr(delta),
+                                           L.ptr(rec_labels), L.ptr(rec_start), int(rec_start.shape[0]) - 1, L.ptr(records),
+                                           L.ptr(lut), L.ptr(out), L.stream()), "ts_stage_moving_apply")
+    return out
+
+
 def stage_layout(cur, cur_lab, cur_b, hist, hist_lab, hist_b, idx, cur_start, kept_start):
     """csrc/stage.hip: the fused clouds of a batch sample-major, current scan first -> (pts [Nc + Nk, F], labels int64, sample
     int64, sample int32, is_current bool)."""

@@ -33,15 +33,16 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 __all__ = ["MixParams", "NONE", "LASER", "POLAR", "STRATEGIES", "LASER_THRESHOLDS", "INSTANCE_CLASSES", "MAX_CLASSES", "RECORD",
-           "draw_omega", "draw_mix_params", "laser_thresholds", "pack_mix", "mix_capacity", "mix_points", "polarmix_points",
-           "lasermix_points"]
+           "draw_omega", "draw_mix_params", "draw_coin", "draw_mix_after_coin", "laser_thresholds", "pack_mix", "mix_capacity",
+           "mix_points", "polarmix_points", "lasermix_points"]
 
 NONE, LASER, POLAR = 0, 1, 2
 # LaserMix_semantickitti.py:29 - the list np.random.choice draws from - and the band thresholds of each strategy (:34-107)
 STRATEGIES = ("inc3phi1", "inc4phi1", "inc5phi1", "inc6phi1")
 LASER_THRESHOLDS = ((-6.7, -13.4), (-5.0, -10.0, -15.0), (-4.0, -8.0, -12.0, -16.0), (-3.3, -6.6, -9.9, -13.2, -16.5))
-# semantickitti_ms.py:13, nuscenes_ms.py:15
-INSTANCE_CLASSES = {"semantickitti": tuple(range(1, 9)), "nuscenes": tuple(range(1, 11))}
+# semantickitti_ms.py:13, nuscenes_ms.py:15, semantickitti_ms_ms.py:15 (the SMSA recipe: the six moving classes too)
+INSTANCE_CLASSES = {"semantickitti": tuple(range(1, 9)), "nuscenes": tuple(range(1, 11)),
+                    "semantickitti_ms_ms": tuple(range(1, 9)) + tuple(range(20, 26))}
 MAX_CLASSES = 16          # TS_MIX_MAX_CLASSES of include/taseg_hip.h
 RECORD = 24               # TS_MIX_RECORD
 
@@ -90,7 +91,21 @@ def draw_mix_params(rng: np.random.RandomState, omega: Sequence[float], augment:
     pass `n_partners=len(infos)` to replay that draw (None: not drawn).  Follow with `draw_train_params` on the same `rng`."""
     if dataset not in INSTANCE_CLASSES:
         raise ValueError("dataset must be one of %s" % sorted(INSTANCE_CLASSES))
-    prob = int(rng.choice(2, 1)[0])
+    return draw_mix_after_coin(rng, draw_coin(rng), omega, augment, training, dataset, degrees, n_partners)
+
+
+def draw_coin(rng: np.random.RandomState) -> int:
+    """`prob = np.random.choice(2, 1)`, drawn for every sample (semantickitti_ms.py:151)"""
+    return int(rng.choice(2, 1)[0])
+
+
+def draw_mix_after_coin(rng: np.random.RandomState, prob: int, omega: Sequence[float], augment: str = "GlobalAugment_LP",
+                        training: bool = True, dataset: str = "semantickitti", degrees: bool = False,
+                        n_partners: Optional[int] = None) -> MixParams:
+    """draw_mix_params from the coin on: the SMSA recipe draws its partner's moving-object augmentation between the coin and the
+    rest (data/moving.py `draw_smsa_sample`)"""
+    if dataset not in INSTANCE_CLASSES:
+        raise ValueError("dataset must be one of %s" % sorted(INSTANCE_CLASSES))
     partner = None
     if dataset == "nuscenes":
         if n_partners is not None:
@@ -99,7 +114,7 @@ def draw_mix_params(rng: np.random.RandomState, omega: Sequence[float], augment:
     else:
         laser_on = polar_on = augment == "GlobalAugment_LP"
     common = dict(prob=prob, partner=partner, omega=tuple(omega), instance_classes=INSTANCE_CLASSES[dataset],
-                  tail_all=dataset == "semantickitti")
+                  tail_all=dataset != "nuscenes")
     if training and laser_on and prob == 1:
         return MixParams(kind=LASER, strategy=int(rng.choice(len(STRATEGIES), 1)[0]), degrees=bool(degrees), **common)
     if training and polar_on and prob == 0:

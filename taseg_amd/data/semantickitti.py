@@ -15,6 +15,8 @@ Host work per sample = reading ~17 files and one 4x4 product per pose; everythin
 The rotate / scale / flip / translate augmentation of the training recipe and the TTA views go in through the stage:
 `build_multiscan_batch(samples, ..., aug=[draw_train_params(rng) for _ in samples])` / `build_tta_batch` (taseg_amd/data/augment.py).
 LaserMix / PolarMix (:151-237) go in the same way: `mix=[draw_mix_params(rng, omega) ...]` and `partners=` (taseg_amd/data/mix.py).
+The SMSA recipe (semantickitti_ms_ms.py: 26 classes, the moving-object augmentation) reads the full labels:
+`multiscan_sample(..., full_labels=True)` adds `raw_labels`, which `moving_tables` and `moving=` take (taseg_amd/data/moving.py).
 """
 import os
 from typing import Dict, List, Optional, Sequence
@@ -96,22 +98,36 @@ class KittiSequence:
         path = os.path.join(self.dir, subdir, str(frame).zfill(6) + ".label")
         return (np.fromfile(path, dtype=np.uint32) & 0xFFFF).astype(np.int64)
 
+    def full_labels(self, frame: int) -> np.ndarray:
+        """the whole uint32 words of a .label file, (instance << 16) | semantic id, as int64: the `instance_id` of
+        semantickitti_ms_ms.py:143, :429"""
+        path = os.path.join(self.dir, "labels", str(frame).zfill(6) + ".label")
+        return np.fromfile(path, dtype=np.uint32).astype(np.int64)
+
 
 def multiscan_sample(seq: KittiSequence, frame: int, multiscan: int, steps: Sequence[int], device="cuda",
-                     pseudo_subdir: Optional[str] = None) -> Dict:
+                     pseudo_subdir: Optional[str] = None, full_labels: bool = False) -> Dict:
     """Frame `frame` and its up-to-`multiscan` history frames (ONLY_HISTORY, oldest first; frames before the start of
     the sequence are skipped like the reference's try/except, :285-291) as resident tensors for build_multiscan_batch.
-    Pseudo labels: the annotations themselves (PSEUDO_MASK 'gt') or the .label files under `pseudo_subdir`."""
+    Pseudo labels: the annotations themselves (PSEUDO_MASK 'gt') or the .label files under `pseudo_subdir`.
+    full_labels=True adds `raw_labels`: the full uint32 label words of every scan (int64), for the SMSA recipe's stage (`moving=`);
+    with `pseudo_subdir` the pseudo classes are then those of the 26-class map."""
     dev = torch.device(device)
     frames = [frame + d for d in range(-multiscan, 0) if frame + d >= 0] + [frame]
-    pts, labs, poses, pseudo = [], [], [], []
+    pts, labs, poses, pseudo, full = [], [], [], [], []
+    canon = _CANON
+    if full_labels:
+        from .moving import CANONICAL_CLASS as canon
     for f in frames:
         raw = seq.raw_labels(f) if seq.has_labels else np.zeros(len(seq.points(f)), dtype=np.int64)
+        if full_labels:
+            full.append(torch.from_numpy(seq.full_labels(f) if seq.has_labels else raw).to(dev))
         pts.append(torch.from_numpy(seq.points(f)).to(dev))
         labs.append(torch.from_numpy(_LUT[raw]).to(dev))
         poses.append(torch.from_numpy(seq.poses[f]).to(dev))
         if f != frame:
             praw = raw if pseudo_subdir is None else seq.raw_labels(f, pseudo_subdir)
-            pseudo.append(torch.from_numpy(_CANON[praw]).to(dev))
+            pseudo.append(torch.from_numpy(canon[praw]).to(dev))
+    extra = {"raw_labels": full} if full_labels else {}
     return {"points": pts, "labels": labs, "poses": poses, "pseudo": pseudo, "deltas": [f - frame for f in frames[:-1]],
-            "name": seq.scan_path(frame)}
+            "name": seq.scan_path(frame), **extra}

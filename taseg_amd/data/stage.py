@@ -7,6 +7,8 @@ semantickitti_voxel_ms.py:77-212); here the same steps run on the GPU on residen
   pose fuse            ts_fuse_scan        p' = ((p R_t^T + t_t) - t_0) R_0, float32, reference summation order
   class-step filter    lookup table        one _kitti_row per history scan, looked up with the point's (pseudo) class
   concat + time flag   torch.cat           current scan first (flag 1), kept history points after it (flag 0)
+  moving objects       ts_stage_moving_*   (moving=) the SMSA recipe's static2moving / moving2static on the current scan and the
+                                           un-filtered fused history (data/moving.py), before everything below
   scan mixing (mix=)   ts_stage_mix        PolarMix / LaserMix with a partner scan (data/mix.py), on the single-frame pair and on the
                                            fused pair, before the augmentation (semantickitti_ms.py:151-237)
   augmentation (aug=)  ts_stage_augment    rotate / scale / flip / translate of the current scan and every fused history row with the
@@ -26,11 +28,12 @@ import torch
 from .. import backend as B
 from .augment import augment_points, draw_tta_params, pack_params
 from . import mix as M
+from . import moving as MV
 from ..torchsparse import SparseTensor
 from ..options import options
 
 __all__ = ["fuse_multiscan", "voxelize_sample_ms", "voxelize_sample", "collate_batch", "build_multiscan_batch",
-           "build_multiscan_batch_per_sample", "build_tta_batch", "voxelize_batch_ms", "rows_index", "DevicePrefetcher"]
+           "build_multiscan_batch_per_sample", "build_tta_batch", "moving_tables", "voxelize_batch_ms", "rows_index", "DevicePrefetcher"]
 
 _BATCHED = options.stage_batched
 _cache = {}
@@ -272,17 +275,154 @@ def _fused_cloud(s, steps):
     return pts[t], lab[t].long(), raw_all, lab_all, keep
 
 
+def _moving_rows(clouds: List[Dict]):
+    """The rows ts_stage_moving_* work on, for scan dicts with `raw_labels`: (points [N, 4] - a fresh tensor: the current scans of
+    all clouds, then their history scans pose-fused in one launch -, full labels [N] int64, cloud [N] int32, frame offset [N] int32
+    (0 on the current rows), current rows per cloud, history rows per cloud, the walk)."""
+    if any(c.get("raw_labels") is None for c in clouds):
+        raise ValueError("moving= needs the full labels of every scan: scan dicts with `raw_labels`")
+    dev = clouds[0]["points"][-1].device
+    walk = _walk_scans(clouds, ())
+    (hist_pts, _, _, lengths, owner, pose0s, poses, _), current = walk
+    deltas = []
+    for c in clouds:
+        t = len(c["points"]) - 1
+        deltas += list(c.get("deltas") or [i - t for i in range(t)])
+    n_cur = [int(c[0].shape[0]) for c in current]
+    n_hist = [c[3] for c in current]
+    parts = [c[0][:, :4] for c in current]
+    if hist_pts:
+        parts.append(B.fuse_scans_batch(torch.cat(hist_pts, 0).contiguous(), rows_index32(lengths, dev), torch.stack(pose0s, 0),
+                                        torch.stack(poses, 0)))
+    pts = torch.cat(parts, 0)                          # (torch.cat's fresh tensor: the resident scans stay untouched)
+    raw = torch.cat([c["raw_labels"][-1].reshape(-1) for c in clouds] +
+                    [r.reshape(-1) for c in clouds for r in c["raw_labels"][:-1]], 0).long()
+    if raw.shape[0] != pts.shape[0]:
+        raise ValueError("raw_labels must hold one label per point of every scan")
+
+    def make():
+        seg = rows_index(n_cur + lengths, dev)
+        cloud = torch.tensor(list(range(len(clouds))) + owner, dtype=torch.int32).to(dev)[seg]
+        delta = torch.tensor([0] * len(clouds) + deltas, dtype=torch.int32).to(dev)[seg]
+        return cloud.contiguous(), delta.contiguous()
+    cloud32, delta32 = _cached(("moving-rows", tuple(n_cur), tuple(lengths), tuple(owner), tuple(deltas), str(dev)), make)
+    return pts, raw, cloud32, delta32, n_cur, n_hist, walk
+
+
+_MOVING_CAP = 1024         # TS_MOVING_MAX_CANDIDATES: candidates of one call, all clouds together
+_SENTINEL = 1 << 62
+
+
+def moving_tables(scans: List[Dict], partners=None):
+    """[(MovingTable of scans[b], MovingTable of partners[b] or None)]: the per-instance statistics the draws of the SMSA recipe's
+    moving-object augmentation depend on (data/moving.py `draw_smsa_sample`), for the samples of a batch and their mix partners in
+    one go: one pose-fuse launch, the candidates of every cloud - the distinct full labels of its current rows with raw class 18,
+    20, 253 or 255 - by a sort of the current rows' (cloud, label) keys, ts_stage_moving_stats (six launches), and ONE host read:
+    table sizes, candidates, counts and statistics in one copy."""
+    partners = [None] * len(scans) if partners is None else list(partners)
+    if len(partners) != len(scans):
+        raise ValueError("partners must hold one scan (or None) per sample")
+    clouds = list(scans) + [p for p in partners if p is not None]
+    pts, raw, cloud32, delta32, n_cur, n_hist, _ = _moving_rows(clouds)
+    dev, nc, ncl, cap = pts.device, sum(n_cur), len(clouds), _MOVING_CAP
+    cur_raw = raw[:nc]
+    cls = cur_raw & 0xFFFF
+    cand_row = (cls == 18) | (cls == 20) | (cls == 253) | (cls == 255)
+    key = torch.where(cand_row, (cloud32[:nc].long() << 32) | cur_raw, torch.full_like(cur_raw, _SENTINEL))
+    key = torch.sort(key).values
+    first = key != _SENTINEL
+    first[1:] &= key[1:] != key[:-1]
+    pos = torch.cumsum(first, 0) - 1
+    # candidate i of the batch -> cand[i]; everything else -> the spare cell behind them
+    cand = torch.zeros(cap + 1, dtype=torch.int64, device=dev)
+    cand.scatter_(0, torch.where(first & (pos < cap), pos, torch.full_like(pos, cap)), key & 0xFFFFFFFF)
+    per = torch.zeros(ncl + 1, dtype=torch.int64, device=dev)
+    per.scatter_add_(0, torch.where(first, key >> 32, torch.full_like(key, ncl)), torch.ones_like(key))
+    start = torch.cat([per.new_zeros(1), torch.cumsum(per[:ncl], 0)])
+    cap_rows = min(int(pts.shape[0]), 1 << 20)
+    counts, stats, matched = B.stage_moving_stats(pts, nc, raw, cloud32, delta32, cand[:cap], start.int(), cap_rows=cap_rows)
+    host = torch.cat([start, matched, cand[:cap], counts.view(-1).long(), stats.view(torch.int32).view(-1).long()]).cpu().numpy()
+    start, matched, host = host[:ncl + 1], int(host[ncl + 1]), host[ncl + 2:]                   # the host read
+    if int(start[-1]) > cap or matched > cap_rows:
+        raise ValueError("moving_tables: %d candidates (at most %d), %d of their rows (at most %d) in one call"
+                         % (int(start[-1]), cap, matched, cap_rows))
+    labels, counts = host[:cap], host[cap:4 * cap].astype(np.int32).reshape(cap, 3)
+    stats = host[4 * cap:].astype(np.int32).view(np.float32).reshape(cap, 9)
+    tables = [MV.MovingTable(labels[a:b].copy(), counts[a:b].copy(), stats[a:b].copy(), int(nh))
+              for a, b, nh in zip(start[:-1], start[1:], n_hist)]
+    theirs = iter(tables[len(scans):])
+    return [(tables[b], None if p is None else next(theirs)) for b, p in enumerate(partners)]
+
+
+def _moving_records(moving, partner_moving, n_samples):
+    """moving= / partner_moving= of a batch, checked: one MovingParams (or None: nothing moves) per sample"""
+    moving = list(moving)
+    partner_moving = [None] * n_samples if partner_moving is None else list(partner_moving)
+    if len(moving) != n_samples or len(partner_moving) != n_samples or \
+            not all(p is None or isinstance(p, MV.MovingParams) for p in moving + partner_moving):
+        raise ValueError("moving / partner_moving must hold one MovingParams (or None) per sample")
+    return moving, partner_moving
+
+
+def _moved_clouds(clouds: List[Dict], params):
+    """The moving-object augmentation of scan dicts with `raw_labels` (params[i]: the MovingParams of clouds[i] or None): the rows of
+    _moving_rows shifted and relabelled by ONE ts_stage_moving_apply launch with the uploaded records.  Returns (current rows of all
+    clouds [Nc, 4], their classes int64 - the 26-class map of the rewritten raw classes -, fused history rows [Nh, 4], their
+    classes, their pseudo classes - the class whose canonical raw id the ORIGINAL raw class is, else -1: the class-step mask is
+    computed before the augmentation, semantickitti_ms_ms.py:440-445 -, the walk)."""
+    pts, raw, cloud32, delta32, n_cur, _, walk = _moving_rows(clouds)
+    dev, nc = pts.device, sum(n_cur)
+    rec_lab, rec_start, rec = MV.pack_moving(params)
+    def make():
+        canon = np.full(1 << 16, -1, dtype=np.int64)           # every 16-bit raw class: one past the label definition is no class's
+        canon[:len(MV.CANONICAL_CLASS)] = MV.CANONICAL_CLASS
+        return torch.from_numpy(MV.LABEL_TABLE).to(dev), torch.from_numpy(canon).to(dev)
+    lut, canon = _cached(("moving-lut", str(dev)), make)
+    lab = B.stage_moving_apply(pts, nc, raw, cloud32, delta32, torch.from_numpy(rec_lab).to(dev, non_blocking=True),
+                               torch.from_numpy(rec_start).to(dev, non_blocking=True),
+                               torch.from_numpy(rec).to(dev, non_blocking=True), lut)
+    if all(c.get("pseudo") is None for c in clouds):
+        pseudo = canon[raw[nc:] & 0xFFFF]
+    else:
+        pseudo = torch.cat([(canon[r.reshape(-1).long() & 0xFFFF] if c.get("pseudo") is None else c["pseudo"][i].long())
+                            for c in clouds for i, r in enumerate(c["raw_labels"][:-1])] +
+                           [torch.empty(0, dtype=torch.int64, device=dev)], 0)
+    return pts[:nc], lab[:nc], pts[nc:], lab[nc:], pseudo, walk
+
+
+def _fused_cloud_moved(s, steps, params):
+    """_fused_cloud of one scan dict after its moving-object augmentation (steps: all 26 classes')"""
+    cur, lab, fused, hl, ps, ((_, _, _, lengths, _, _, _, _), _) = _moved_clouds([s], [params])
+    dev, n_cur = cur.device, cur.shape[0]
+    t = len(s["points"]) - 1
+    flag = torch.zeros((n_cur + fused.shape[0], 1), dtype=cur.dtype, device=dev)
+    flag[:n_cur] = 1
+    raw_all = torch.cat([torch.cat([cur, fused], 0), flag], 1)
+    keep = torch.ones(n_cur, dtype=torch.bool, device=dev)
+    if t:
+        scan_idx, table = _history_index(lengths, s.get("deltas") or [i - t for i in range(t)], steps, dev)
+        ps = torch.where(ps < 0, torch.full_like(ps, table.shape[1] - 1), ps)
+        keep = torch.cat([keep, table.view(-1)[scan_idx.long() * table.shape[1] + ps]])
+    return cur, lab, raw_all, torch.cat([lab, hl]), keep
+
+
 def build_multiscan_batch_per_sample(scans: List[Dict], voxel_size: float, steps: Sequence[int], aug=None, mix=None,
-                                     partners=None) -> Dict:
+                                     partners=None, moving=None, partner_moving=None) -> Dict:
     """build_multiscan_batch sample by sample (fuse, clamp, two voxelisations and ~55 launches per sample, then collate): the
-    form the batched stage below replaced; kept as its cross-check (tests) and for TASEG_STAGE_BATCHED=0."""
+    form the batched stage below replaced; kept as its cross-check (tests) and for TASEG_STAGE_BATCHED=0.  moving= /
+    partner_moving=: one ts_stage_moving_apply launch per cloud, no host read of its own."""
     samples = []
+    fused_cloud = _fused_cloud
+    if moving is not None:
+        moving, partner_moving = _moving_records(moving, partner_moving, len(scans))
+        steps = MV.pad_steps(steps)
+        fused_cloud = None
     rec = None if aug is None else _aug_records(aug, len(scans))
     if mix is not None:
         mix, partners = _mix_records(mix, partners, len(scans))
     for b, s in enumerate(scans):
         one = None if rec is None else rec[b:b + 1]
-        cur, lab, raw, lab_ms, keep = _fused_cloud(s, steps)
+        cur, lab, raw, lab_ms, keep = _fused_cloud(s, steps) if fused_cloud else _fused_cloud_moved(s, steps, moving[b])
         if mix is None or mix[b].kind == M.NONE:
             # (the class-step filter rides on the clamp's compaction)
             samples.append(voxelize_sample_ms(cur, lab, raw, lab_ms, voxel_size, s.get("name", ""), keep=keep, aug=one))
@@ -291,7 +431,8 @@ def build_multiscan_batch_per_sample(scans: List[Dict], voxel_size: float, steps
         if partners[b] is None:
             pcur, plab, praw, plab_ms = cur[:0], lab[:0], raw[:0], lab_ms[:0]
         else:
-            pcur, plab, praw, plab_ms, pkeep = _fused_cloud(partners[b], steps)
+            pcur, plab, praw, plab_ms, pkeep = _fused_cloud(partners[b], steps) if fused_cloud else \
+                _fused_cloud_moved(partners[b], steps, partner_moving[b])
             pcur, praw, plab_ms = pcur[:, :4], praw[pkeep], plab_ms[pkeep]
         # the same record on the single-frame pair and on the fused pair (semantickitti_ms.py:182-185, :221-234)
         cur, lab = M.mix_points(cur, lab, pcur, plab, mix[b])
@@ -373,7 +514,8 @@ def _walk_scans(clouds: List[Dict], steps: Sequence[int]):
     hist_pts, hist_lab, hist_ps, lengths, owner, pose0s, poses, rows = hist = [], [], [], [], [], [], [], []
     current, n_hist = [], 0
     for b, s in enumerate(clouds):
-        pts, lab, ps = s["points"], s["labels"], s["poses"]
+        pts, ps = s["points"], s["poses"]
+        lab = s["labels"] if s.get("labels") is not None else s["raw_labels"]      # (moving=: the classes come from raw_labels)
         t = len(pts) - 1
         deltas = s.get("deltas") or [i - t for i in range(t)]
         pseudo = s.get("pseudo")
@@ -392,21 +534,34 @@ def _walk_scans(clouds: List[Dict], steps: Sequence[int]):
     return hist, current
 
 
-def _build_multiscan_batch_mix(scans, partners, mix, voxel_size, steps, aug) -> Dict:
+def _build_multiscan_batch_mix(scans, partners, mix, voxel_size, steps, aug, moving=None, partner_moving=None) -> Dict:
     """build_multiscan_batch with mix=: the samples' and the partners' history scans (_walk_scans) pose-fused in ONE launch, the class-step rule
     as a keep byte per row (no compaction of its own), ts_stage_mix on the single-frame pairs and on the fused pairs of the whole
     batch (three launches each, their row counts in one host read), the augmentation, the clamp of EVERY fused row against the
     mixed single-frame cloud's minimum (after a mix the current scan is no prefix of the fused cloud any more;
     semantickitti_voxel_ms.py:121-124), one compaction, both voxelisations.  point_mask stays what the reference's collate_batch
-    makes it (_prefix_mask)."""
+    makes it (_prefix_mask).  moving= / partner_moving=: the samples' and the partners' moving-object augmentation first, one
+    ts_stage_moving_apply launch for all of them (_moved_clouds)."""
     dev = scans[0]["points"][-1].device
     nb, n_cls = len(scans), len(steps)
     any_pseudo = any(c is not None and c.get("pseudo") is not None for c in list(scans) + list(partners))
     # the clouds that take part, in order: every sample's own, then its partner's where its mix moves rows of one
     used = [[s, partners[b] if mix[b].kind != M.NONE else None] for b, s in enumerate(scans)]
-    (hist_pts, hist_lab, hist_ps, lengths, _, pose0s, poses, rows), current = _walk_scans(
-        [c for pair in used for c in pair if c is not None], steps)
-    if hist_pts:
+    clouds = [c for pair in used for c in pair if c is not None]
+    (hist_pts, hist_lab, hist_ps, lengths, _, pose0s, poses, rows), current = _walk_scans(clouds, steps)
+    if moving is not None:
+        params = [q for b, pair in enumerate(used) for c, q in zip(pair, (moving[b], partner_moving[b])) if c is not None]
+        cur_all, cur_lab_all, fused, hl, hps, _ = _moved_clouds(clouds, params)
+        at = list(accumulate([int(c[0].shape[0]) for c in current], initial=0))
+        current = [(cur_all[a:b], cur_lab_all[a:b], c[2], c[3]) for a, b, c in zip(at[:-1], at[1:], current)]
+        if hist_pts:
+            scan32 = rows_index32(lengths, dev)
+            table = torch.tensor(rows, dtype=torch.bool).to(dev, non_blocking=True)
+            hps = torch.where(hps < 0, torch.full_like(hps, n_cls), hps)
+            hkeep = table.view(-1)[scan32.long() * (n_cls + 1) + hps]
+        else:
+            hkeep = torch.empty(0, dtype=torch.bool, device=dev)
+    elif hist_pts:
         hp = torch.cat(hist_pts, 0).contiguous()
         hl = torch.cat(hist_lab, 0).long()
         hps = torch.cat(hist_ps, 0).long() if any_pseudo else hl
@@ -469,7 +624,8 @@ def _build_multiscan_batch_mix(scans, partners, mix, voxel_size, steps, aug) -> 
                             [s.get("name", "") for s in scans])
 
 
-def build_multiscan_batch(scans: List[Dict], voxel_size: float, steps: Sequence[int], aug=None, mix=None, partners=None) -> Dict:
+def build_multiscan_batch(scans: List[Dict], voxel_size: float, steps: Sequence[int], aug=None, mix=None, partners=None,
+                          moving=None, partner_moving=None) -> Dict:
     """scans[b] = dict(points=[T+1 tensors, current LAST], labels=[...], poses=[...], name=str
     [, deltas=[frame offsets of the history scans], pseudo=[pseudo classes of the history scans, see _fuse_history]]).
     Returns the collated batch_dict MinkUNetMs consumes.  The whole batch goes through ONE chain of launches: one pose-fuse
@@ -481,18 +637,41 @@ def build_multiscan_batch(scans: List[Dict], voxel_size: float, steps: Sequence[
     mix: one MixParams per sample (data/mix.py) or None; partners[b]: the scan dict of sample b's partner (None where its mix needs
     none).  With it every sample is mixed with its partner - PolarMix / LaserMix on the single-frame pair and on the fused pair,
     semantickitti_ms.py:151-237 - before the augmentation (_build_multiscan_batch_mix); mix=None is the path without it, launch
-    for launch."""
+    for launch.
+    moving: one MovingParams per sample (data/moving.py; None in the list: nothing moves) or None; partner_moving[b]: the
+    MovingParams of sample b's partner.  The SMSA recipe (semantickitti_ms_ms.py): scan dicts then carry `raw_labels` - one tensor
+    of FULL uint32 labels (any integer dtype wide enough) per scan, parallel to `points` - and `labels` is not read: the classes are
+    the 26-class map of the raw classes (data/moving.py LABEL_TABLE), `steps` shorter than 26 counts as 0 for the rest.  The
+    instances of the records are shifted and relabelled on the current scans and on the UN-FILTERED fused history - one
+    ts_stage_moving_apply launch and three small host-to-device copies for all clouds of the batch, samples and partners, no host
+    read - before the keep bytes of the class-step rule (computed from the raw classes as they were) take effect, before the mix
+    and the augmentation.  The statistics its draws need come from `moving_tables` before this call (one host read per batch):
+
+        tables = moving_tables(scans, partners)
+        mv, mix, pmv = zip(*[draw_smsa_sample(rng, omega, t, pt) for t, pt in tables])
+
+    moving=None is the path without it, launch for launch."""
     if not _BATCHED or not scans or len(scans) > 64:
-        return build_multiscan_batch_per_sample(scans, voxel_size, steps, aug=aug, mix=mix, partners=partners)
+        return build_multiscan_batch_per_sample(scans, voxel_size, steps, aug=aug, mix=mix, partners=partners, moving=moving,
+                                                partner_moving=partner_moving)
+    if moving is not None:
+        moving, partner_moving = _moving_records(moving, partner_moving, len(scans))
+        steps = MV.pad_steps(steps)
     if mix is not None:
         mix, partners = _mix_records(mix, partners, len(scans))
-        return _build_multiscan_batch_mix(scans, partners, mix, voxel_size, steps, aug)
+        return _build_multiscan_batch_mix(scans, partners, mix, voxel_size, steps, aug, moving, partner_moving)
     dev = scans[0]["points"][-1].device
     n_cls = len(steps)
     (hist_pts, hist_lab, hist_ps, lengths, scan_sample, pose0s, poses, rows), current = _walk_scans(scans, steps)
     cur_in = [c[0] for c in current]                   # the resident current scans, with all their columns
     lab_list = [c[1] for c in current]
-    cur4 = torch.cat([c[:, :4] for c in cur_in], 0)
+    moved = None
+    if moving is not None:
+        cur4, cur_lab_all, *moved = _moved_clouds(scans, moving)[:5]
+        n_cur = [int(c.shape[0]) for c in cur_in]
+        cur_in, lab_list = list(torch.split(cur4, n_cur)), list(torch.split(cur_lab_all, n_cur))
+    else:
+        cur4 = torch.cat([c[:, :4] for c in cur_in], 0)
     if aug is not None:
         rec = _aug_records(aug, len(scans))
         n_cur = [int(c.shape[0]) for c in cur_in]
@@ -503,12 +682,15 @@ def build_multiscan_batch(scans: List[Dict], voxel_size: float, steps: Sequence[
         cur_in = list(torch.split(cur4, n_cur))        # the single-frame clouds ARE the rows the fused clouds start with
     cur_ms = torch.cat([cur4, torch.ones((cur4.shape[0], 1), dtype=cur4.dtype, device=dev)], 1)      # append_time_flag (:253-257)
     if hist_pts:
-        hp = torch.cat(hist_pts, 0).contiguous()
-        hl = torch.cat(hist_lab, 0).long()
-        hps = hl if all(s.get("pseudo") is None for s in scans) else torch.cat(hist_ps, 0).long()
         table, sample_of_scan = _step_table("kitti-table", rows, scan_sample, dev)
         scan32 = rows_index32(lengths, dev)
-        fused = B.fuse_scans_batch(hp, scan32, torch.stack(pose0s, 0), torch.stack(poses, 0))
+        if moved is not None:
+            fused, hl, hps = moved
+        else:
+            hp = torch.cat(hist_pts, 0).contiguous()
+            hl = torch.cat(hist_lab, 0).long()
+            hps = hl if all(s.get("pseudo") is None for s in scans) else torch.cat(hist_ps, 0).long()
+            fused = B.fuse_scans_batch(hp, scan32, torch.stack(pose0s, 0), torch.stack(poses, 0))
         if aug is not None:
             augment_points(fused, rec_dev[len(scans):], scan32, out=fused)
         hist_ms = torch.cat([fused, torch.zeros((fused.shape[0], 1), dtype=fused.dtype, device=dev)], 1)
