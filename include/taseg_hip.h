@@ -944,6 +944,21 @@ size_t ts_stage_mix_workspace_bytes(int64_t n_rows, int64_t n_blocks, int32_t n_
 int ts_stage_mix(const float *points, int64_t n_rows, int32_t point_stride, const int64_t *labels, const uint8_t *keep,
                  const double *records, const int32_t *classes, int32_t n_jobs, int64_t n_blocks, float *out, int64_t *out_labels,
                  int32_t *out_job, int64_t capacity, int64_t *totals, void *ws, size_t ws_bytes, ts_stream_t stream);
+/* The clamp of the fused clouds as one stable compaction for a whole batch (csrc/compact.hip): nuscenes_voxel_ms.py:122-125 /
+ * semantickitti_voxel_ms.py:121-124, `point_ms[(point_ms[:, :3] >= point[:, :3].min(0)).all(1)]`, where the current scan is no
+ * prefix of the fused cloud (after ts_stage_mix) and ts_stage_keep_flags / ts_stage_layout do not apply.  points [n, point_stride
+ * >= 3] float32, labels [n] int64, sample [n] int32 ASCENDING (the out_job of ts_stage_mix), lo [n_samples, 3] float32 (the
+ * minimum of every sample's single-frame cloud, ts_segment_min3), 1 <= n_samples <= TS_CLAMP_MAX_SAMPLES.  Row i survives iff
+ * x >= lo[s][0] && y >= lo[s][1] && z >= lo[s][2] with s = sample[i] - a NaN on either side fails, as numpy's `>=`; a row whose
+ * sample is outside [0, n_samples) does not survive.  out [n, point_stride], out_labels [n], out_sample [n] int64, out_sample32
+ * [n] int32: the surviving rows in input order (the rows behind them are not written); counts [n_samples] int64 the survivors of
+ * every sample - the caller reads them once per batch, the output holds sum(counts) rows.  Three launches (counts per block of 256
+ * rows from wave ballots, a one-block scan, the scatter by rank); no atomics: the same bits every run. */
+#define TS_CLAMP_MAX_SAMPLES 64
+size_t ts_stage_clamp_compact_workspace_bytes(int64_t n, int32_t n_samples);
+int ts_stage_clamp_compact(const float *points, int64_t n, int32_t point_stride, const int64_t *labels, const int32_t *sample,
+                           const float *lo, int32_t n_samples, float *out, int64_t *out_labels, int64_t *out_sample,
+                           int32_t *out_sample32, int64_t *counts, void *ws, size_t ws_bytes, ts_stream_t stream);
 /* Moving-object augmentation of the SMSA recipe (csrc/moving.hip; taseg_amd/data/moving.py draws the parameters):
  * semantickitti_ms_ms.py:305-351 `static2moving` and :353-384 `moving2static`, called at :152-163 for the sample and at :198-207 /
  * :248-257 for its mix partner, on the current scan and the pose-fused UN-FILTERED history rows, before the class-step mask

@@ -1307,6 +1307,39 @@ def stage_mix(points, labels, params, n1, n2, keep=None, totals=None):
     return out, out_lab, out_job, totals
 
 
+def stage_clamp_compact(points, labels, sample32, lo):
+    """csrc/compact.hip: the clamp of the fused clouds of a batch as one stable compaction in three launches.  points [n, F >= 3]
+    float32, labels [n] int64, sample32 [n] int32 ascending (the out_job of stage_mix), lo [B <= 64, 3] float32 (segment_min3 of the
+    single-frame clouds).  Row i survives iff points[i, :3] >= lo[sample32[i]] in every column (NaN fails).  Returns (out [n, F],
+    out_labels [n] int64, out_sample [n] int64, out_sample32 [n] int32, counts [B] int64): the survivors in input order in the
+    first sum(counts) rows - the caller reads counts, the survivors of every sample.  No host read here."""
+    L.require_device(points, labels, sample32, lo)
+    points, sample32, lo = _f32(points, "points"), _i32(sample32, "sample32"), _f32(lo, "lo")
+    if points.ndim != 2 or points.shape[1] < 3:
+        raise TypeError("points must be a float32 [n, F >= 3] tensor")
+    if labels.dtype != torch.int64:
+        raise TypeError("labels must be int64")
+    labels = labels.contiguous()
+    n, f = points.shape
+    if labels.shape != (n,) or sample32.shape != (n,):
+        raise ValueError("stage_clamp_compact: one label and one sample index per row")
+    if lo.ndim != 2 or lo.shape[1] != 3 or not 1 <= lo.shape[0] <= 64:
+        raise ValueError("stage_clamp_compact: lo must be [1 .. 64, 3]")
+    dev, nb = points.device, lo.shape[0]
+    out = torch.empty((n, f), dtype=torch.float32, device=dev)
+    out_lab = torch.empty(n, dtype=torch.int64, device=dev)
+    out_sample = torch.empty(n, dtype=torch.int64, device=dev)
+    out_sample32 = torch.empty(n, dtype=torch.int32, device=dev)
+    counts = torch.empty(nb, dtype=torch.int64, device=dev)
+    lib = L.load()
+    ws_bytes = lib.ts_stage_clamp_compact_workspace_bytes(n, nb)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    L.check(lib.ts_stage_clamp_compact(L.ptr(points), n, f, L.ptr(labels), L.ptr(sample32), L.ptr(lo), nb, L.ptr(out), L.ptr(out_lab),
+                                       L.ptr(out_sample), L.ptr(out_sample32), L.ptr(counts), L.ptr(ws), ws_bytes, L.stream()),
+            "ts_stage_clamp_compact")
+    return out, out_lab, out_sample, out_sample32, counts
+
+
 def stage_moving_stats(points, n_cur, labels, cloud, delta, cand, cand_start, cap_rows=None):
     """csrc/moving.hip: the per-instance statistics of the moving-object augmentation (taseg_amd/data/moving.py) for the clouds of a
     batch in six launches.  points [N, F >= 2] float32: the n_cur current rows of all clouds, then their pose-fused history rows;

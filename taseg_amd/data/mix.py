@@ -32,7 +32,7 @@ from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
-__all__ = ["MixParams", "NONE", "LASER", "POLAR", "STRATEGIES", "LASER_THRESHOLDS", "INSTANCE_CLASSES", "MAX_CLASSES", "RECORD",
+__all__ = ["MixParams", "NONE", "LASER", "POLAR", "STRATEGIES", "LASER_THRESHOLDS", "LASER_THRESHOLDS_NUSCENES", "INSTANCE_CLASSES", "MAX_CLASSES", "RECORD",
            "draw_omega", "draw_mix_params", "draw_coin", "draw_mix_after_coin", "laser_thresholds", "pack_mix", "mix_capacity",
            "mix_points", "polarmix_points", "lasermix_points"]
 
@@ -40,6 +40,10 @@ NONE, LASER, POLAR = 0, 1, 2
 # LaserMix_semantickitti.py:29 - the list np.random.choice draws from - and the band thresholds of each strategy (:34-107)
 STRATEGIES = ("inc3phi1", "inc4phi1", "inc5phi1", "inc6phi1")
 LASER_THRESHOLDS = ((-6.7, -13.4), (-5.0, -10.0, -15.0), (-4.0, -8.0, -12.0, -16.0), (-3.3, -6.6, -9.9, -13.2, -16.5))
+# LaserMix_nuscenes.py:116-201: the nuScenes file's `lasermix_aug_` has its own bands, no inc6phi1, and draws its strategy from the
+# one-element list ['inc3phi1'] (:135); its `lasermix_aug` (:11-114) is the SemanticKITTI file's
+LASER_THRESHOLDS_NUSCENES = ((0.0, -10.0), (4.0, -2.0, -10.0), (4.0, 0.0, -4.0, -12.0))
+STRATEGIES_NUSCENES_DEGREES = ("inc3phi1",)
 # semantickitti_ms.py:13, nuscenes_ms.py:15, semantickitti_ms_ms.py:15 (the SMSA recipe: the six moving classes too)
 INSTANCE_CLASSES = {"semantickitti": tuple(range(1, 9)), "nuscenes": tuple(range(1, 11)),
                     "semantickitti_ms_ms": tuple(range(1, 9)) + tuple(range(20, 26))}
@@ -53,7 +57,8 @@ class MixParams:
     `lasermix_aug`, the identity; True: `lasermix_aug_`) for LASER; alpha, beta, swap, paste, omega (the two paste angles),
     instance_classes and tail_all (True: the rotated copies carry every column after xyz, SemanticKITTI; False: only column 3,
     nuScenes) for POLAR.  prob is the drawn coin, partner the drawn partner index (nuScenes draws it, SemanticKITTI shuffles a
-    list once)."""
+    list once).  dataset picks the band thresholds of a LASER record with `degrees` (`laser_thresholds`): "nuscenes" takes
+    LaserMix_nuscenes.py's, which has no inc6phi1 (ValueError); everything else SemanticKITTI's."""
     kind: int = NONE
     strategy: int = 0
     degrees: bool = False
@@ -66,10 +71,15 @@ class MixParams:
     tail_all: bool = True
     prob: int = -1
     partner: Optional[int] = None
+    dataset: str = "semantickitti"
 
     def __post_init__(self):
         if self.kind not in (NONE, LASER, POLAR) or not 0 <= self.strategy < len(STRATEGIES):
             raise ValueError("MixParams: bad kind / strategy")
+        if self.dataset not in INSTANCE_CLASSES:
+            raise ValueError("MixParams: dataset must be one of %s" % sorted(INSTANCE_CLASSES))
+        if self.kind == LASER:
+            laser_thresholds(self.strategy, self.degrees, self.dataset)      # (inc6phi1 under the nuScenes `lasermix_aug_`)
         cls = tuple(int(c) for c in self.instance_classes)
         if len(cls) > MAX_CLASSES or len(set(cls)) != len(cls):
             raise ValueError("MixParams: at most %d instance classes, each once" % MAX_CLASSES)
@@ -86,7 +96,8 @@ def draw_mix_params(rng: np.random.RandomState, omega: Sequence[float], augment:
                     dataset: str = "semantickitti", degrees: bool = False, n_partners: Optional[int] = None) -> MixParams:
     """The mix of one sample, consuming `rng` exactly as the reference's `__getitem__` consumes numpy's global generator
     (semantickitti_ms.py:151-237, nuscenes_ms.py:132-214): `choice(2, 1)` always; LaserMix (prob 1): `choice(strategies, size=1)`;
-    PolarMix (prob 0): `random()` for alpha, `random()` for the swap, `random()` for the paste.  nuScenes honours
+    PolarMix (prob 0): `random()` for alpha, `random()` for the swap, `random()` for the paste.  Under `degrees=True,
+    dataset="nuscenes"` the strategy draw is LaserMix_nuscenes.py:135-136's `choice(['inc3phi1'], size=1)`.  nuScenes honours
     GlobalAugment_L / GlobalAugment_P (:135,:168) and draws the partner with `choice(len(infos))` right after the coin (:133) -
     pass `n_partners=len(infos)` to replay that draw (None: not drawn).  Follow with `draw_train_params` on the same `rng`."""
     if dataset not in INSTANCE_CLASSES:
@@ -114,9 +125,10 @@ def draw_mix_after_coin(rng: np.random.RandomState, prob: int, omega: Sequence[f
     else:
         laser_on = polar_on = augment == "GlobalAugment_LP"
     common = dict(prob=prob, partner=partner, omega=tuple(omega), instance_classes=INSTANCE_CLASSES[dataset],
-                  tail_all=dataset != "nuscenes")
+                  tail_all=dataset != "nuscenes", dataset=dataset)
     if training and laser_on and prob == 1:
-        return MixParams(kind=LASER, strategy=int(rng.choice(len(STRATEGIES), 1)[0]), degrees=bool(degrees), **common)
+        pool = STRATEGIES_NUSCENES_DEGREES if dataset == "nuscenes" and degrees else STRATEGIES
+        return MixParams(kind=LASER, strategy=int(rng.choice(len(pool), 1)[0]), degrees=bool(degrees), **common)
     if training and polar_on and prob == 0:
         alpha = float((rng.random_sample() - 1) * np.pi)
         swap = bool(rng.random_sample() < 0.5)
@@ -125,9 +137,14 @@ def draw_mix_after_coin(rng: np.random.RandomState, prob: int, omega: Sequence[f
     return MixParams(kind=NONE, **common)
 
 
-def laser_thresholds(strategy: int, degrees: bool) -> List[float]:
+def laser_thresholds(strategy: int, degrees: bool, dataset: str = "semantickitti") -> List[float]:
     """the band thresholds as the reference writes them: `-6.7` against degrees (`lasermix_aug_`), `-6.7 / np.pi * 180` against
-    radians (`lasermix_aug`, LaserMix_semantickitti.py:34)"""
+    radians (`lasermix_aug`, LaserMix_semantickitti.py:34).  dataset="nuscenes": `lasermix_aug_` of LaserMix_nuscenes.py:138-194
+    has bands of its own (LASER_THRESHOLDS_NUSCENES) and no inc6phi1; its `lasermix_aug` is the SemanticKITTI file's."""
+    if dataset == "nuscenes" and degrees:
+        if strategy >= len(LASER_THRESHOLDS_NUSCENES):
+            raise ValueError("%s does not exist in the nuScenes lasermix_aug_" % STRATEGIES[strategy])
+        return [float(t) for t in LASER_THRESHOLDS_NUSCENES[strategy]]
     return [float(t) if degrees else float(t / np.pi * 180) for t in LASER_THRESHOLDS[strategy]]
 
 
@@ -144,7 +161,7 @@ def pack_mix(params: Sequence[MixParams], n1: Sequence[int], n2: Sequence[int]):
         r[5], r[6], r[7], r[8] = np.cos(p.omega[0]), np.sin(p.omega[0]), np.cos(p.omega[1]), np.sin(p.omega[1])
         r[9], r[10] = p.tail_all, p.degrees
         if p.kind == LASER:
-            thr = laser_thresholds(p.strategy, p.degrees)
+            thr = laser_thresholds(p.strategy, p.degrees, p.dataset)
             r[11] = len(thr)
             r[12:12 + len(thr)] = thr
         r[17], r[18], r[19] = a, b, row
@@ -189,11 +206,12 @@ def polarmix_points(pts1, lab1, pts2, lab2, params: MixParams):
     return mix_points(pts1, lab1, pts2, lab2, params)
 
 
-def lasermix_points(pts1, lab1, pts2, lab2, strategy, degrees: bool = False):
+def lasermix_points(pts1, lab1, pts2, lab2, strategy, degrees: bool = False, dataset: str = "semantickitti"):
     """LaserMix_semantickitti.py on the device.  strategy: 0 .. 3 or its name.  degrees=False is `lasermix_aug` as both datasets
     call it (:11-114) - the identity, see the module docstring; degrees=True is `lasermix_aug_` (:116-219): inclination bands
-    alternate between the clouds, concat(band 1 of cloud 1, band 2 of cloud 2, band 3 of cloud 1, ...)."""
+    alternate between the clouds, concat(band 1 of cloud 1, band 2 of cloud 2, band 3 of cloud 1, ...).  dataset="nuscenes":
+    `lasermix_aug_` of LaserMix_nuscenes.py (:116-201) with its own bands; inc6phi1 is a ValueError there."""
     if isinstance(strategy, str):
         strategy = STRATEGIES.index(strategy)
-    return mix_points(pts1, lab1, pts2, lab2, MixParams(kind=LASER, strategy=int(strategy), degrees=bool(degrees)))
+    return mix_points(pts1, lab1, pts2, lab2, MixParams(kind=LASER, strategy=int(strategy), degrees=bool(degrees), dataset=dataset))
 

@@ -14,6 +14,9 @@ Split between host and device the way the work splits:
       ts_fuse_sweeps       ego-box filter on the raw coordinates, sensor -> keyframe -> current-frame transforms in
                            float64 with numpy's rounding points, time delta column
       class-step mask      table lookup on the pseudo labels, one _nusc_row per selected sweep (:322-327)
+      scan mixing (mix=)   ts_stage_mix on the single-frame pair and on the fused pair of every sample and its partner keyframe
+                           (nuscenes_ms.py:132-214, data/mix.py), before the augmentation; then the clamp of every fused row as one
+                           stable compaction (ts_stage_clamp_compact, csrc/compact.hip)
       augmentation (aug=)  ts_stage_augment on the current keyframes and on every fused sweep row (nuscenes_voxel_ms.py:90-120,
                            data/augment.py), before the clamp and both voxelisations
       voxelisation         the same ts_voxel_coords / ts_sparse_quantize stage as SemanticKITTI (voxel 0.1 m,
@@ -31,8 +34,10 @@ import torch
 
 from .. import backend as B
 from . import stage as _stage          # (_stage._BATCHED is read at call time)
+from . import mix as M
 from .augment import augment_points, draw_tta_params
-from .stage import _aug_records, _cached, _step_table, collate_batch, rows_index32, voxelize_batch_ms, voxelize_sample_ms
+from .stage import (_aug_records, _cached, _mix_records, _prefix_mask, _step_table, _voxelize_layout, collate_batch, rows_index32,
+                    voxelize_batch_ms, voxelize_sample_ms)
 
 __all__ = ["NuscSequence", "rotation_matrix", "relative_transform", "select_sweeps", "sweep_params", "fuse_sweeps",
            "build_nuscenes_batch", "build_nuscenes_batch_per_sample", "build_tta_batch"]
@@ -177,7 +182,105 @@ def fuse_sweeps(cur_pts, cur_lab, hist_pts: List[torch.Tensor], hist_lab: List[t
     return raw, lab, torch.cat([torch.ones(n_cur, dtype=torch.bool, device=dev), keep])
 
 
-def build_nuscenes_batch(samples: List[Dict], voxel_size: float, steps: Sequence[int], in_feature_dim: int = 4, aug=None) -> Dict:
+def _used_mix(mix, partners, n_samples):
+    """mix= / partners= of a batch, checked (stage._mix_records); None where no record mixes: that batch takes the path without"""
+    if mix is None:
+        return None, None
+    mix, partners = _mix_records(mix, partners, n_samples)
+    if all(p.kind == M.NONE for p in mix):
+        return None, None
+    return mix, partners
+
+
+def _build_nuscenes_batch_mix(samples, partners, mix, voxel_size, steps, in_feature_dim, aug) -> Dict:
+    """build_nuscenes_batch with mix= (modelled on stage._build_multiscan_batch_mix): the sweeps of every sample and of every
+    partner that is used in ONE ts_fuse_sweeps launch; the ego box AND the class-step rule (_nusc_row by the sweep's position in
+    ITS cloud) as the keep byte of the fused mix - no compaction before it; ts_stage_mix on the single-frame pairs and on the fused
+    pairs, their row counts in one host read; the augmentation of both clouds through the mix's out_job; the minima of the mixed
+    single-frame clouds (ts_segment_min3); the clamp of EVERY fused row as one stable compaction (ts_stage_clamp_compact) with the
+    second host read, the survivors per sample; both voxelisations.  point_mask is what the reference's collate_batch makes it
+    (_prefix_mask).  The mix works on the first `in_feature_dim` columns of the 5-column rows: the sample's keyframe with column 4
+    set to 0, the partner's as the file holds it, the sweep rows of both with their time lag (see build_nuscenes_batch)."""
+    dev = samples[0]["points"].device
+    f, nb, n_cls = in_feature_dim, len(samples), len(steps)
+    # the clouds that take part, in order: every sample's own, then its partner's where its mix moves rows of one
+    used = [[s, partners[b] if mix[b].kind != M.NONE else None] for b, s in enumerate(samples)]
+    hp, hl, hs, lengths, rows, params = [], [], [], [], [], []
+    for pair in used:
+        for c in pair:
+            if c is None:
+                continue
+            for pos, p in enumerate(c["hist_points"]):
+                hp.append(p)
+                lengths.append(int(p.shape[0]))
+                rows.append(_nusc_row(pos, steps))
+            hl += list(c["hist_labels"])
+            hs += list(c["hist_pseudo"])
+            if len(c["hist_points"]):
+                params.append(c["params"])
+    if hp:
+        stack = torch.cat(hp, 0).contiguous()
+        pseudo = torch.cat(hs, 0).long()
+        lab_h = torch.cat(hl, 0).long()
+        sweep32 = rows_index32(lengths, dev)
+        table, _ = _step_table("nusc-table", rows, [0] * len(rows), dev)
+        fused, no_ego = B.fuse_sweeps(stack, sweep32, torch.cat(params, 0) if len(params) > 1 else params[0])
+        fused = fused[:, :f]
+        hkeep = no_ego & table.view(-1)[sweep32.long() * n_cls + pseudo]
+    else:
+        fused = torch.empty((0, f), dtype=torch.float32, device=dev)
+        lab_h = torch.empty(0, dtype=torch.int64, device=dev)
+        hkeep = torch.empty(0, dtype=torch.bool, device=dev)
+    # job-major rows: [keyframe | partner's keyframe] for the single-frame mix, [keyframe | sweeps | partner's keyframe | partner's
+    # sweeps] for the fused one
+    s_pts, s_lab, s_n1, s_n2 = [], [], [], []
+    m_pts, m_lab, m_keep, m_n1, m_n2 = [], [], [], [], []
+    ones = torch.ones(max(int(c["points"].shape[0]) for pair in used for c in pair if c is not None), dtype=torch.bool, device=dev)
+    first = 0
+    for pair in used:
+        sizes = []
+        for k, c in enumerate(pair):
+            if c is None:
+                sizes.append((0, 0))
+                continue
+            # column 4: 0 on the sample's keyframe (nuscenes_ms.py:109), the file's on the partner's (:136-141)
+            key = (_current_keyframe(c["points"], f) if k == 0 else c["points"][:, :f])
+            n, nh = int(key.shape[0]), sum(int(p.shape[0]) for p in c["hist_points"])
+            lab = c["labels"].reshape(-1).long()
+            s_pts.append(key)
+            s_lab.append(lab)
+            m_pts += [key, fused[first:first + nh]]
+            m_lab += [lab, lab_h[first:first + nh]]
+            m_keep += [ones[:n], hkeep[first:first + nh]]
+            first += nh
+            sizes.append((n, nh))
+        s_n1.append(sizes[0][0])
+        s_n2.append(sizes[1][0])
+        m_n1.append(sizes[0][0] + sizes[0][1])
+        m_n2.append(sizes[1][0] + sizes[1][1])
+    totals = torch.empty((2, nb), dtype=torch.int64, device=dev)
+    cur, cur_lab, cur_b32, _ = B.stage_mix(torch.cat(s_pts, 0), torch.cat(s_lab, 0), mix, s_n1, s_n2, totals=totals[0])
+    ms, ms_lab, ms_b32, _ = B.stage_mix(torch.cat(m_pts, 0), torch.cat(m_lab, 0), mix, m_n1, m_n2, keep=torch.cat(m_keep, 0),
+                                        totals=totals[1])
+    n_cur, n_mixed = totals.tolist()                                    # host read 1 (rows of both mixes, all samples)
+    cur, cur_lab, cur_b32 = cur[:sum(n_cur)], cur_lab[:sum(n_cur)], cur_b32[:sum(n_cur)]
+    ms, ms_lab, ms_b32 = ms[:sum(n_mixed)], ms_lab[:sum(n_mixed)], ms_b32[:sum(n_mixed)]
+    if aug is not None:
+        rec_dev = torch.from_numpy(_aug_records(aug, nb)).to(dev, non_blocking=True)
+        augment_points(cur, rec_dev, cur_b32, out=cur)
+        augment_points(ms, rec_dev, ms_b32, out=ms)
+    cur_b = cur_b32.long()
+    lo = B.segment_min3(cur, cur_b, nb)
+    ms, ms_lab, ms_b, ms_b32, counts = B.stage_clamp_compact(ms, ms_lab, ms_b32, lo)
+    n_ms = counts.tolist()                                              # host read 2 (fused rows per sample)
+    kept = sum(n_ms)
+    ms, ms_lab, ms_b, ms_b32 = ms[:kept], ms_lab[:kept], ms_b[:kept], ms_b32[:kept]
+    return _voxelize_layout(cur, cur_lab, cur_b, n_cur, ms, ms_lab, ms_b, ms_b32, n_ms, _prefix_mask(n_cur, n_ms, dev), voxel_size,
+                            [s.get("name", "") for s in samples])
+
+
+def build_nuscenes_batch(samples: List[Dict], voxel_size: float, steps: Sequence[int], in_feature_dim: int = 4, aug=None, mix=None,
+                         partners=None) -> Dict:
     """samples[b] = dict(points [n,5], labels [n], hist_points [..], hist_labels [..], hist_pseudo [..],
     params [S,28] float64 tensor, name).  Returns the collated batch_dict MinkUNetMs consumes
     (nuscenes_voxel_ms.py:77-212 == the SemanticKITTI stage on the first `in_feature_dim` columns).
@@ -185,9 +288,27 @@ def build_nuscenes_batch(samples: List[Dict], voxel_size: float, steps: Sequence
     sensor -> keyframe -> current-frame transforms, time delta), the class-step rule (_nusc_row, stage._step_table) as one table
     lookup, then stage.voxelize_batch_ms (one compaction, one batch-keyed voxelisation per cloud kind).
     aug: one AugParams per sample (data/augment.py) or None = the un-augmented path.  With it the current keyframes and all fused sweep
-    rows are augmented in place (one ts_stage_augment launch each, the sweep rows through their sweep index) before the clamp."""
+    rows are augmented in place (one ts_stage_augment launch each, the sweep rows through their sweep index) before the clamp.
+    mix: one MixParams per sample (data/mix.py, `draw_mix_params(rng, omega, dataset="nuscenes", n_partners=len(reader))`) or None;
+    partners[b]: the sample dict of sample b's partner keyframe - what `NuscInfoReader.sample(p.partner, ...)` returns - or None
+    where its record needs none.  With it every sample is mixed with its partner - PolarMix / LaserMix on the single-frame pair and
+    on the fused pair, nuscenes_ms.py:132-214 - before the augmentation (_build_nuscenes_batch_mix).  mix=None, and a list whose
+    records are all NONE, is the path without it, launch for launch and bit for bit.  What the reference does there is reproduced,
+    not repaired:
+      * column 4 (:109, :136-141): the sample's keyframe has column 4 set to 0; the partner's keyframe keeps column 4 as the file
+        holds it (the ring index), alone and as the head of its fused cloud; the sweep rows of both carry the time lag.  The mix
+        runs on the first `in_feature_dim` columns of these 5-column rows: nothing of it shows with 4, all of it with 5;
+      * the rotated copies of PolarMix_nuscenes.py:53 carry column 3 only, zeros behind it (`tail_all=False`);
+      * a sample or a partner without history (the first keyframe of its scene: `hist_points == []`, :122-131, :151-159) has its
+        fused cloud equal to its keyframe;
+      * the partner is drawn with `choice(len(infos))` (:133) and may be the sample itself;
+      * the recipe's LaserMix branch calls `lasermix_aug` (:161), the identity, and still consumes its strategy draw;
+      * nothing mixes outside training: `draw_mix_params(training=False)` returns NONE."""
+    mix, partners = _used_mix(mix, partners, len(samples))
     if not _stage._BATCHED or not samples or len(samples) > 64:
-        return build_nuscenes_batch_per_sample(samples, voxel_size, steps, in_feature_dim, aug=aug)
+        return build_nuscenes_batch_per_sample(samples, voxel_size, steps, in_feature_dim, aug=aug, mix=mix, partners=partners)
+    if mix is not None:
+        return _build_nuscenes_batch_mix(samples, partners, mix, voxel_size, steps, in_feature_dim, aug)
     dev = samples[0]["points"].device
     f = in_feature_dim
     n_cls = len(steps)
@@ -230,17 +351,41 @@ def build_nuscenes_batch(samples: List[Dict], voxel_size: float, steps: Sequence
                              [s.get("name", "") for s in samples], pre_keep=no_ego)
 
 
+def _partner_clouds(s, steps, in_feature_dim):
+    """(keyframe, labels, fused cloud, its labels) of a mix partner, on `in_feature_dim` columns: as the sample's, but column 4 of
+    the keyframe stays what the file holds (nuscenes_ms.py:136-141, :155)"""
+    raw, lab, keep = fuse_sweeps(s["points"], s["labels"], s["hist_points"], s["hist_labels"], s["hist_pseudo"], s["params"], steps)
+    n = s["points"].shape[0]
+    raw[:n, 4] = s["points"][:, 4]                     # (fuse_sweeps hands out a fresh tensor)
+    return s["points"][:, :in_feature_dim].contiguous(), s["labels"].reshape(-1).long(), raw[keep][:, :in_feature_dim].contiguous(), lab[keep]
+
+
 def build_nuscenes_batch_per_sample(samples: List[Dict], voxel_size: float, steps: Sequence[int], in_feature_dim: int = 4,
-                                    aug=None) -> Dict:
-    """build_nuscenes_batch sample by sample (the form the batched stage replaced; its cross-check and TASEG_STAGE_BATCHED=0)"""
+                                    aug=None, mix=None, partners=None) -> Dict:
+    """build_nuscenes_batch sample by sample (the form the batched stage replaced; its cross-check and TASEG_STAGE_BATCHED=0).
+    mix= / partners= as there: `mix_points` on the single-frame pair and on the fused pair of every sample that is mixed (three
+    launches and a host read each), then voxelize_sample_ms; the same reproduced-not-repaired points hold."""
     out = []
     rec = None if aug is None else _aug_records(aug, len(samples))
+    mix, partners = _used_mix(mix, partners, len(samples))
+    f = in_feature_dim
     for b, s in enumerate(samples):
+        one = None if rec is None else rec[b:b + 1]
         raw, lab, keep = fuse_sweeps(s["points"], s["labels"], s["hist_points"], s["hist_labels"], s["hist_pseudo"],
                                      s["params"], steps)
-        out.append(voxelize_sample_ms(_current_keyframe(s["points"], in_feature_dim), s["labels"].long(),
-                                      raw[:, :in_feature_dim].contiguous(), lab, voxel_size, s.get("name", ""), keep=keep,
-                                      aug=None if rec is None else rec[b:b + 1]))
+        cur, cur_lab = _current_keyframe(s["points"], f), s["labels"].reshape(-1).long()
+        if mix is None or mix[b].kind == M.NONE:
+            out.append(voxelize_sample_ms(cur, cur_lab, raw[:, :f].contiguous(), lab, voxel_size, s.get("name", ""), keep=keep, aug=one))
+            continue
+        raw, lab = raw[keep][:, :f].contiguous(), lab[keep]
+        if partners[b] is None:
+            pcur, plab, praw, plab_ms = cur[:0], cur_lab[:0], raw[:0], lab[:0]
+        else:
+            pcur, plab, praw, plab_ms = _partner_clouds(partners[b], steps, f)
+        # the same record on the single-frame pair and on the fused pair (nuscenes_ms.py:161-164, :198-211)
+        cur, cur_lab = M.mix_points(cur, cur_lab, pcur, plab, mix[b])
+        raw, lab = M.mix_points(raw, lab, praw, plab_ms, mix[b])
+        out.append(voxelize_sample_ms(cur, cur_lab, raw, lab, voxel_size, s.get("name", ""), aug=one))
     return collate_batch(out)
 
 

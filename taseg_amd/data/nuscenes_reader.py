@@ -27,9 +27,15 @@ Inputs, as the reference's dataset class finds them on disk:
 Host work per sample = reading ~25 files and a few dozen 3x3 products (cached per keyframe like the reference's
 `token2samplelist`); everything per point runs on the device.  The rotate / scale / flip / translate augmentation of the
 training recipe and the TTA views go in through the stage: `build_nuscenes_batch(samples, ..., aug=[draw_train_params(rng) for _
-in samples])` / `nuscenes.build_tta_batch` (taseg_amd/data/augment.py).  LaserMix / PolarMix (:132-213) exist as
-`polarmix_points` / `lasermix_points` with the nuScenes class list and tail rule (taseg_amd/data/mix.py), not yet as a `mix=` of
-`build_nuscenes_batch`; the Ceph client is outside the scope contract.
+in samples])` / `nuscenes.build_tta_batch` (taseg_amd/data/augment.py).  LaserMix / PolarMix (:132-213) go in the same way:
+the draws name the partner keyframe, the reader reads it like any sample, the stage mixes on the device (taseg_amd/data/mix.py):
+
+    mix = [draw_mix_params(rng, omega, dataset="nuscenes", n_partners=len(reader)) for _ in indexes]   # then draw_train_params
+    partners = [None if p.kind == NONE else reader.sample(p.partner, multiscan=15, step=1.0) for p in mix]
+    batch = build_nuscenes_batch(samples, 0.1, FLEXIBLE_STEPS_NUSC, aug=aug, mix=mix, partners=partners)
+
+(the stage sets column 4 of the sample's keyframe to 0 and leaves the partner's as the file holds it, nuscenes_ms.py:109, :136-141);
+the Ceph client is outside the scope contract.
 """
 import json
 import os
