@@ -16,7 +16,8 @@ Split between host and device the way the work splits:
       class-step mask      table lookup on the pseudo labels, one _nusc_row per selected sweep (:322-327)
       scan mixing (mix=)   ts_stage_mix on the single-frame pair and on the fused pair of every sample and its partner keyframe
                            (nuscenes_ms.py:132-214, data/mix.py), before the augmentation; then the clamp of every fused row as one
-                           stable compaction (ts_stage_clamp_compact, csrc/compact.hip)
+                           stable compaction (ts_stage_clamp_compact, csrc/compact.hip) - stage._mix_and_voxelize, the tail shared
+                           with SemanticKITTI
       augmentation (aug=)  ts_stage_augment on the current keyframes and on every fused sweep row (nuscenes_voxel_ms.py:90-120,
                            data/augment.py), before the clamp and both voxelisations
       voxelisation         the same ts_voxel_coords / ts_sparse_quantize stage as SemanticKITTI (voxel 0.1 m,
@@ -36,7 +37,7 @@ from .. import backend as B
 from . import stage as _stage          # (_stage._BATCHED is read at call time)
 from . import mix as M
 from .augment import augment_points, draw_tta_params
-from .stage import (_aug_records, _cached, _mix_records, _prefix_mask, _step_table, _voxelize_layout, collate_batch, rows_index32,
+from .stage import (_aug_records, _cached, _mix_and_voxelize, _mix_records, _step_keep, _step_table, collate_batch, rows_index32,
                     voxelize_batch_ms, voxelize_sample_ms)
 
 __all__ = ["NuscSequence", "rotation_matrix", "relative_transform", "select_sweeps", "sweep_params", "fuse_sweeps",
@@ -173,10 +174,8 @@ def fuse_sweeps(cur_pts, cur_lab, hist_pts: List[torch.Tensor], hist_lab: List[t
     if not hist_pts:
         return cur, cur_lab.long(), torch.ones(n_cur, dtype=torch.bool, device=dev)
     sweep_idx, table = _layout([p.shape[0] for p in hist_pts], steps, dev)
-    stack = torch.cat(hist_pts, 0).contiguous()
-    pseudo = torch.cat(hist_pseudo, 0).long()
-    fused, no_ego = B.fuse_sweeps(stack, sweep_idx, params)
-    keep = no_ego & table.view(-1)[sweep_idx.long() * table.shape[1] + pseudo]
+    fused, no_ego = B.fuse_sweeps(torch.cat(hist_pts, 0).contiguous(), sweep_idx, params)
+    keep = no_ego & _step_keep(table, sweep_idx, torch.cat(hist_pseudo, 0).long())
     raw = torch.cat([cur, fused], 0)
     lab = torch.cat([cur_lab.long(), torch.cat(hist_lab, 0).long()])
     return raw, lab, torch.cat([torch.ones(n_cur, dtype=torch.bool, device=dev), keep])
@@ -192,91 +191,67 @@ def _used_mix(mix, partners, n_samples):
     return mix, partners
 
 
+def _walk_sweeps(clouds: List[Dict], steps: Sequence[int]):
+    """One pass over sample dicts (build_nuscenes_batch's `samples[b]`), the counterpart of stage._walk_scans.  Returns the selected
+    sweeps of all of them, flat and in order: (points, labels, pseudo labels, lengths, owner = index of the dict in `clouds`,
+    _nusc_row by the sweep's position in ITS cloud, the [S, 28] params of every cloud that has sweeps)."""
+    pts, lab, pseudo, lengths, owner, rows, params = walk = [], [], [], [], [], [], []
+    for b, c in enumerate(clouds):
+        for pos, p in enumerate(c["hist_points"]):
+            pts.append(p)
+            lengths.append(int(p.shape[0]))
+            owner.append(b)
+            rows.append(_nusc_row(pos, steps))
+        lab += list(c["hist_labels"])
+        pseudo += list(c["hist_pseudo"])
+        if len(c["hist_points"]):
+            params.append(c["params"])
+    return walk
+
+
+def _fuse_walk(walk, n_cls, in_feature_dim, device):
+    """The sweeps of _walk_sweeps in ONE ts_fuse_sweeps launch -> (fused rows cut to `in_feature_dim` columns (a view), labels
+    int64, pseudo labels int64, sweep index int32, no_ego bool, class-step table [S, C], owner of every sweep on the device - the
+    cached pair of stage._step_table, keyed by rows AND owners); without sweeps the row tensors are empty and the table is one
+    row of zeros"""
+    pts, lab, pseudo, lengths, owner, rows, params = walk
+    if not pts:
+        none = torch.empty(0, dtype=torch.int64, device=device)
+        return (torch.empty((0, in_feature_dim), dtype=torch.float32, device=device), none, none,
+                torch.empty(0, dtype=torch.int32, device=device), torch.empty(0, dtype=torch.bool, device=device),
+                torch.zeros((1, n_cls), dtype=torch.bool, device=device), torch.zeros(1, dtype=torch.int64, device=device))
+    stack = torch.cat(pts, 0).contiguous()
+    pseudo = torch.cat(pseudo, 0).long()
+    lab = torch.cat(lab, 0).long()
+    sweep32 = rows_index32(lengths, device)
+    table, owner_dev = _step_table("nusc-table", rows, owner, device)
+    fused, no_ego = B.fuse_sweeps(stack, sweep32, torch.cat(params, 0) if len(params) > 1 else params[0])
+    return fused[:, :in_feature_dim], lab, pseudo, sweep32, no_ego, table, owner_dev
+
+
 def _build_nuscenes_batch_mix(samples, partners, mix, voxel_size, steps, in_feature_dim, aug) -> Dict:
-    """build_nuscenes_batch with mix= (modelled on stage._build_multiscan_batch_mix): the sweeps of every sample and of every
-    partner that is used in ONE ts_fuse_sweeps launch; the ego box AND the class-step rule (_nusc_row by the sweep's position in
-    ITS cloud) as the keep byte of the fused mix - no compaction before it; ts_stage_mix on the single-frame pairs and on the fused
-    pairs, their row counts in one host read; the augmentation of both clouds through the mix's out_job; the minima of the mixed
-    single-frame clouds (ts_segment_min3); the clamp of EVERY fused row as one stable compaction (ts_stage_clamp_compact) with the
-    second host read, the survivors per sample; both voxelisations.  point_mask is what the reference's collate_batch makes it
-    (_prefix_mask).  The mix works on the first `in_feature_dim` columns of the 5-column rows: the sample's keyframe with column 4
-    set to 0, the partner's as the file holds it, the sweep rows of both with their time lag (see build_nuscenes_batch)."""
-    dev = samples[0]["points"].device
-    f, nb, n_cls = in_feature_dim, len(samples), len(steps)
+    """build_nuscenes_batch with mix=: the sweeps of every sample and of every partner that is used in ONE ts_fuse_sweeps launch
+    (_walk_sweeps, _fuse_walk); the ego box AND the class-step rule as the keep byte of the fused mix; then the tail both datasets
+    share, stage._mix_and_voxelize: two host reads before the voxelisation.  The mix works on the first `in_feature_dim` columns of
+    the 5-column rows: the sample's keyframe with column 4 set to 0, the partner's as the file holds it, the sweep rows of both
+    with their time lag (see build_nuscenes_batch)."""
+    dev, f = samples[0]["points"].device, in_feature_dim
     # the clouds that take part, in order: every sample's own, then its partner's where its mix moves rows of one
     used = [[s, partners[b] if mix[b].kind != M.NONE else None] for b, s in enumerate(samples)]
-    hp, hl, hs, lengths, rows, params = [], [], [], [], [], []
+    walk = _walk_sweeps([c for pair in used for c in pair if c is not None], steps)
+    fused, lab_h, pseudo, sweep32, no_ego, table, _ = _fuse_walk(walk, len(steps), f, dev)
+    hkeep = no_ego & _step_keep(table, sweep32, pseudo)
+    heads, first = [], 0
     for pair in used:
-        for c in pair:
-            if c is None:
-                continue
-            for pos, p in enumerate(c["hist_points"]):
-                hp.append(p)
-                lengths.append(int(p.shape[0]))
-                rows.append(_nusc_row(pos, steps))
-            hl += list(c["hist_labels"])
-            hs += list(c["hist_pseudo"])
-            if len(c["hist_points"]):
-                params.append(c["params"])
-    if hp:
-        stack = torch.cat(hp, 0).contiguous()
-        pseudo = torch.cat(hs, 0).long()
-        lab_h = torch.cat(hl, 0).long()
-        sweep32 = rows_index32(lengths, dev)
-        table, _ = _step_table("nusc-table", rows, [0] * len(rows), dev)
-        fused, no_ego = B.fuse_sweeps(stack, sweep32, torch.cat(params, 0) if len(params) > 1 else params[0])
-        fused = fused[:, :f]
-        hkeep = no_ego & table.view(-1)[sweep32.long() * n_cls + pseudo]
-    else:
-        fused = torch.empty((0, f), dtype=torch.float32, device=dev)
-        lab_h = torch.empty(0, dtype=torch.int64, device=dev)
-        hkeep = torch.empty(0, dtype=torch.bool, device=dev)
-    # job-major rows: [keyframe | partner's keyframe] for the single-frame mix, [keyframe | sweeps | partner's keyframe | partner's
-    # sweeps] for the fused one
-    s_pts, s_lab, s_n1, s_n2 = [], [], [], []
-    m_pts, m_lab, m_keep, m_n1, m_n2 = [], [], [], [], []
-    ones = torch.ones(max(int(c["points"].shape[0]) for pair in used for c in pair if c is not None), dtype=torch.bool, device=dev)
-    first = 0
-    for pair in used:
-        sizes = []
         for k, c in enumerate(pair):
             if c is None:
-                sizes.append((0, 0))
                 continue
             # column 4: 0 on the sample's keyframe (nuscenes_ms.py:109), the file's on the partner's (:136-141)
-            key = (_current_keyframe(c["points"], f) if k == 0 else c["points"][:, :f])
-            n, nh = int(key.shape[0]), sum(int(p.shape[0]) for p in c["hist_points"])
-            lab = c["labels"].reshape(-1).long()
-            s_pts.append(key)
-            s_lab.append(lab)
-            m_pts += [key, fused[first:first + nh]]
-            m_lab += [lab, lab_h[first:first + nh]]
-            m_keep += [ones[:n], hkeep[first:first + nh]]
+            key = _current_keyframe(c["points"], f) if k == 0 else c["points"][:, :f]
+            nh = sum(int(p.shape[0]) for p in c["hist_points"])
+            heads.append((key, c["labels"].reshape(-1).long(), first, nh))
             first += nh
-            sizes.append((n, nh))
-        s_n1.append(sizes[0][0])
-        s_n2.append(sizes[1][0])
-        m_n1.append(sizes[0][0] + sizes[0][1])
-        m_n2.append(sizes[1][0] + sizes[1][1])
-    totals = torch.empty((2, nb), dtype=torch.int64, device=dev)
-    cur, cur_lab, cur_b32, _ = B.stage_mix(torch.cat(s_pts, 0), torch.cat(s_lab, 0), mix, s_n1, s_n2, totals=totals[0])
-    ms, ms_lab, ms_b32, _ = B.stage_mix(torch.cat(m_pts, 0), torch.cat(m_lab, 0), mix, m_n1, m_n2, keep=torch.cat(m_keep, 0),
-                                        totals=totals[1])
-    n_cur, n_mixed = totals.tolist()                                    # host read 1 (rows of both mixes, all samples)
-    cur, cur_lab, cur_b32 = cur[:sum(n_cur)], cur_lab[:sum(n_cur)], cur_b32[:sum(n_cur)]
-    ms, ms_lab, ms_b32 = ms[:sum(n_mixed)], ms_lab[:sum(n_mixed)], ms_b32[:sum(n_mixed)]
-    if aug is not None:
-        rec_dev = torch.from_numpy(_aug_records(aug, nb)).to(dev, non_blocking=True)
-        augment_points(cur, rec_dev, cur_b32, out=cur)
-        augment_points(ms, rec_dev, ms_b32, out=ms)
-    cur_b = cur_b32.long()
-    lo = B.segment_min3(cur, cur_b, nb)
-    ms, ms_lab, ms_b, ms_b32, counts = B.stage_clamp_compact(ms, ms_lab, ms_b32, lo)
-    n_ms = counts.tolist()                                              # host read 2 (fused rows per sample)
-    kept = sum(n_ms)
-    ms, ms_lab, ms_b, ms_b32 = ms[:kept], ms_lab[:kept], ms_b[:kept], ms_b32[:kept]
-    return _voxelize_layout(cur, cur_lab, cur_b, n_cur, ms, ms_lab, ms_b, ms_b32, n_ms, _prefix_mask(n_cur, n_ms, dev), voxel_size,
-                            [s.get("name", "") for s in samples])
+    return _mix_and_voxelize(used, heads, fused, lab_h, hkeep, mix, aug, voxel_size)
 
 
 def build_nuscenes_batch(samples: List[Dict], voxel_size: float, steps: Sequence[int], in_feature_dim: int = 4, aug=None, mix=None,
@@ -284,9 +259,9 @@ def build_nuscenes_batch(samples: List[Dict], voxel_size: float, steps: Sequence
     """samples[b] = dict(points [n,5], labels [n], hist_points [..], hist_labels [..], hist_pseudo [..],
     params [S,28] float64 tensor, name).  Returns the collated batch_dict MinkUNetMs consumes
     (nuscenes_voxel_ms.py:77-212 == the SemanticKITTI stage on the first `in_feature_dim` columns).
-    The whole batch goes through ONE chain of launches: one ts_fuse_sweeps over every sweep point of every sample (ego box,
-    sensor -> keyframe -> current-frame transforms, time delta), the class-step rule (_nusc_row, stage._step_table) as one table
-    lookup, then stage.voxelize_batch_ms (one compaction, one batch-keyed voxelisation per cloud kind).
+    The whole batch goes through ONE chain of launches: one ts_fuse_sweeps over every sweep point of every sample of _walk_sweeps
+    (_fuse_walk: ego box, sensor -> keyframe -> current-frame transforms, time delta), the class-step rule (_nusc_row,
+    stage._step_table) as one table lookup, then stage.voxelize_batch_ms (one compaction, one batch-keyed voxelisation per cloud kind).
     aug: one AugParams per sample (data/augment.py) or None = the un-augmented path.  With it the current keyframes and all fused sweep
     rows are augmented in place (one ts_stage_augment launch each, the sweep rows through their sweep index) before the clamp.
     mix: one MixParams per sample (data/mix.py, `draw_mix_params(rng, omega, dataset="nuscenes", n_partners=len(reader))`) or None;
@@ -311,7 +286,6 @@ def build_nuscenes_batch(samples: List[Dict], voxel_size: float, steps: Sequence
         return _build_nuscenes_batch_mix(samples, partners, mix, voxel_size, steps, in_feature_dim, aug)
     dev = samples[0]["points"].device
     f = in_feature_dim
-    n_cls = len(steps)
     cur_f = _current_keyframe([s["points"] for s in samples], f)     # (one fresh tensor: the resident scans stay untouched)
     n_cur = [int(s["points"].shape[0]) for s in samples]
     rec = None if aug is None else _aug_records(aug, len(samples))
@@ -319,34 +293,11 @@ def build_nuscenes_batch(samples: List[Dict], voxel_size: float, steps: Sequence
         augment_points(cur_f, rec, rows_index32(n_cur, dev), out=cur_f)
     cur_list = list(torch.split(cur_f, n_cur))
     lab_list = [s["labels"].long() for s in samples]
-    hp, hl, hs, lengths, sample_of_sweep, rows, params = [], [], [], [], [], [], []
-    for b, s in enumerate(samples):
-        for pos, p in enumerate(s["hist_points"]):
-            hp.append(p)
-            lengths.append(int(p.shape[0]))
-            sample_of_sweep.append(b)
-            rows.append(_nusc_row(pos, steps))
-        hl += list(s["hist_labels"])
-        hs += list(s["hist_pseudo"])
-        if len(s["hist_points"]):
-            params.append(s["params"])
-    if hp:
-        stack = torch.cat(hp, 0).contiguous()
-        pseudo = torch.cat(hs, 0).long()
-        lab_h = torch.cat(hl, 0).long()
-        sweep32 = rows_index32(lengths, dev)
-        table, sample_of = _step_table("nusc-table", rows, sample_of_sweep, dev)
-        fused, no_ego = B.fuse_sweeps(stack, sweep32, torch.cat(params, 0) if len(params) > 1 else params[0])
-        hist_ms = fused[:, :f].contiguous()
-        if rec is not None:
-            augment_points(hist_ms, rec[np.asarray(sample_of_sweep, dtype=np.int64)], sweep32, out=hist_ms)
-    else:
-        hist_ms = torch.empty((0, f), dtype=cur_f.dtype, device=dev)
-        lab_h = pseudo = torch.empty(0, dtype=torch.int64, device=dev)
-        sweep32 = torch.empty(0, dtype=torch.int32, device=dev)
-        no_ego = None
-        table = torch.zeros((1, n_cls), dtype=torch.bool, device=dev)
-        sample_of = torch.zeros(1, dtype=torch.int64, device=dev)
+    walk = _walk_sweeps(samples, steps)
+    hist_ms, lab_h, pseudo, sweep32, no_ego, table, sample_of = _fuse_walk(walk, len(steps), f, dev)
+    hist_ms = hist_ms.contiguous()
+    if rec is not None and walk[0]:
+        augment_points(hist_ms, rec[np.asarray(walk[4], dtype=np.int64)], sweep32, out=hist_ms)
     return voxelize_batch_ms(cur_list, lab_list, cur_f, hist_ms, lab_h, sweep32, pseudo, table, sample_of, voxel_size,
                              [s.get("name", "") for s in samples], pre_keep=no_ego)
 

@@ -10,7 +10,10 @@ semantickitti_voxel_ms.py:77-212); here the same steps run on the GPU on residen
   moving objects       ts_stage_moving_*   (moving=) the SMSA recipe's static2moving / moving2static on the current scan and the
                                            un-filtered fused history (data/moving.py), before everything below
   scan mixing (mix=)   ts_stage_mix        PolarMix / LaserMix with a partner scan (data/mix.py), on the single-frame pair and on the
-                                           fused pair, before the augmentation (semantickitti_ms.py:151-237)
+                                           fused pair, before the augmentation (semantickitti_ms.py:151-237); _mix_and_voxelize, the
+                                           tail both datasets share
+  clamp after a mix    ts_stage_clamp_compact   every fused row against its sample's mixed single-frame minimum, one stable compaction
+                                           (without mix=: ts_stage_keep_flags, the history rows only; per sample: the ATen clamp)
   augmentation (aug=)  ts_stage_augment    rotate / scale / flip / translate of the current scan and every fused history row with the
                                            sample's AugParams (data/augment.py), before the clamp and both voxelisations
   voxel coordinates    ts_voxel_coords     int32(round_half_even(xyz / voxel)) - min
@@ -81,6 +84,22 @@ def _step_table(tag: str, rows, owner, device):
                    lambda: (torch.tensor(rows, dtype=torch.bool).to(device), torch.tensor(owner, dtype=torch.int64).to(device)))
 
 
+def _step_keep(table, scan_idx, cls, neg_last=False):
+    """bool [n]: table[scan_idx[i], cls[i]], the class-step decision of every history row.  table [S, C] bool (one _kitti_row or
+    _nusc_row per scan / sweep), scan_idx [n] int32 or int64, cls [n] int64.  neg_last: a negative class reads the table's last
+    column (_kitti_row's); without it every class is a column."""
+    n_cols = table.shape[1]
+    if neg_last:
+        cls = torch.where(cls < 0, torch.full_like(cls, n_cols - 1), cls)
+    return table.view(-1)[scan_idx.long() * n_cols + cls]
+
+
+def _deltas(s) -> List[int]:
+    """the frame offsets of a scan dict's history scans: its `deltas`, else -T .. -1"""
+    t = len(s["points"]) - 1
+    return s.get("deltas") or [i - t for i in range(t)]
+
+
 def _history_index(lengths: Sequence[int], deltas: Sequence[int], steps: Sequence[int], device):
     """Per-layout helpers of one sample, cached: scan index (int32) of every concatenated history point, and the [T, C + 1] table of
     _kitti_row per history scan."""
@@ -110,9 +129,7 @@ def _fuse_history(cur_pts, cur_lab, hist_pts, hist_lab, pose0, hist_poses, delta
     hp = torch.cat([p[:, :4] for p in hist_pts], 0).contiguous()
     hl = torch.cat(hist_lab, 0).long()
     fused = B.fuse_scans(hp, scan_idx, pose0, torch.stack(list(hist_poses), 0))
-    ps = hl if hist_pseudo is None else torch.cat(hist_pseudo, 0).long()
-    ps = torch.where(ps < 0, torch.full_like(ps, table.shape[1] - 1), ps)
-    keep = table.view(-1)[scan_idx.long() * table.shape[1] + ps]
+    keep = _step_keep(table, scan_idx, hl if hist_pseudo is None else torch.cat(hist_pseudo, 0).long(), neg_last=True)
     pts = torch.cat([cur_pts[:, :4], fused], 0)
     flag = torch.zeros((pts.shape[0], 1), dtype=pts.dtype, device=dev)
     flag[:n_cur] = 1                               # append_time_flag (semantickitti_ms.py:253-257)
@@ -270,8 +287,7 @@ def _fused_cloud(s, steps):
     sample and for its partner alike"""
     pts, lab, poses = s["points"], s["labels"], s["poses"]
     t = len(pts) - 1
-    deltas = s.get("deltas") or [i - t for i in range(t)]
-    raw_all, lab_all, keep = _fuse_history(pts[t], lab[t], pts[:t], lab[:t], poses[t], poses[:t], deltas, steps, s.get("pseudo"))
+    raw_all, lab_all, keep = _fuse_history(pts[t], lab[t], pts[:t], lab[:t], poses[t], poses[:t], _deltas(s), steps, s.get("pseudo"))
     return pts[t], lab[t].long(), raw_all, lab_all, keep
 
 
@@ -284,10 +300,7 @@ def _moving_rows(clouds: List[Dict]):
     dev = clouds[0]["points"][-1].device
     walk = _walk_scans(clouds, ())
     (hist_pts, _, _, lengths, owner, pose0s, poses, _), current = walk
-    deltas = []
-    for c in clouds:
-        t = len(c["points"]) - 1
-        deltas += list(c.get("deltas") or [i - t for i in range(t)])
+    deltas = [d for c in clouds for d in _deltas(c)]
     n_cur = [int(c[0].shape[0]) for c in current]
     n_hist = [c[3] for c in current]
     parts = [c[0][:, :4] for c in current]
@@ -394,15 +407,13 @@ def _fused_cloud_moved(s, steps, params):
     """_fused_cloud of one scan dict after its moving-object augmentation (steps: all 26 classes')"""
     cur, lab, fused, hl, ps, ((_, _, _, lengths, _, _, _, _), _) = _moved_clouds([s], [params])
     dev, n_cur = cur.device, cur.shape[0]
-    t = len(s["points"]) - 1
     flag = torch.zeros((n_cur + fused.shape[0], 1), dtype=cur.dtype, device=dev)
     flag[:n_cur] = 1
     raw_all = torch.cat([torch.cat([cur, fused], 0), flag], 1)
     keep = torch.ones(n_cur, dtype=torch.bool, device=dev)
-    if t:
-        scan_idx, table = _history_index(lengths, s.get("deltas") or [i - t for i in range(t)], steps, dev)
-        ps = torch.where(ps < 0, torch.full_like(ps, table.shape[1] - 1), ps)
-        keep = torch.cat([keep, table.view(-1)[scan_idx.long() * table.shape[1] + ps]])
+    if lengths:
+        scan_idx, table = _history_index(lengths, _deltas(s), steps, dev)
+        keep = torch.cat([keep, _step_keep(table, scan_idx, ps, neg_last=True)])
     return cur, lab, raw_all, torch.cat([lab, hl]), keep
 
 
@@ -517,7 +528,7 @@ def _walk_scans(clouds: List[Dict], steps: Sequence[int]):
         pts, ps = s["points"], s["poses"]
         lab = s["labels"] if s.get("labels") is not None else s["raw_labels"]      # (moving=: the classes come from raw_labels)
         t = len(pts) - 1
-        deltas = s.get("deltas") or [i - t for i in range(t)]
+        deltas = _deltas(s)
         pseudo = s.get("pseudo")
         first = n_hist
         for i in range(t):
@@ -534,78 +545,45 @@ def _walk_scans(clouds: List[Dict], steps: Sequence[int]):
     return hist, current
 
 
-def _build_multiscan_batch_mix(scans, partners, mix, voxel_size, steps, aug, moving=None, partner_moving=None) -> Dict:
-    """build_multiscan_batch with mix=: the samples' and the partners' history scans (_walk_scans) pose-fused in ONE launch, the class-step rule
-    as a keep byte per row (no compaction of its own), ts_stage_mix on the single-frame pairs and on the fused pairs of the whole
-    batch (three launches each, their row counts in one host read), the augmentation, the clamp of EVERY fused row against the
-    mixed single-frame cloud's minimum (after a mix the current scan is no prefix of the fused cloud any more;
-    semantickitti_voxel_ms.py:121-124), one compaction, both voxelisations.  point_mask stays what the reference's collate_batch
-    makes it (_prefix_mask).  moving= / partner_moving=: the samples' and the partners' moving-object augmentation first, one
-    ts_stage_moving_apply launch for all of them (_moved_clouds)."""
-    dev = scans[0]["points"][-1].device
-    nb, n_cls = len(scans), len(steps)
-    any_pseudo = any(c is not None and c.get("pseudo") is not None for c in list(scans) + list(partners))
-    # the clouds that take part, in order: every sample's own, then its partner's where its mix moves rows of one
-    used = [[s, partners[b] if mix[b].kind != M.NONE else None] for b, s in enumerate(scans)]
-    clouds = [c for pair in used for c in pair if c is not None]
-    (hist_pts, hist_lab, hist_ps, lengths, _, pose0s, poses, rows), current = _walk_scans(clouds, steps)
-    if moving is not None:
-        params = [q for b, pair in enumerate(used) for c, q in zip(pair, (moving[b], partner_moving[b])) if c is not None]
-        cur_all, cur_lab_all, fused, hl, hps, _ = _moved_clouds(clouds, params)
-        at = list(accumulate([int(c[0].shape[0]) for c in current], initial=0))
-        current = [(cur_all[a:b], cur_lab_all[a:b], c[2], c[3]) for a, b, c in zip(at[:-1], at[1:], current)]
-        if hist_pts:
-            scan32 = rows_index32(lengths, dev)
-            table = torch.tensor(rows, dtype=torch.bool).to(dev, non_blocking=True)
-            hps = torch.where(hps < 0, torch.full_like(hps, n_cls), hps)
-            hkeep = table.view(-1)[scan32.long() * (n_cls + 1) + hps]
-        else:
-            hkeep = torch.empty(0, dtype=torch.bool, device=dev)
-    elif hist_pts:
-        hp = torch.cat(hist_pts, 0).contiguous()
-        hl = torch.cat(hist_lab, 0).long()
-        hps = torch.cat(hist_ps, 0).long() if any_pseudo else hl
-        scan32 = rows_index32(lengths, dev)
-        table = torch.tensor(rows, dtype=torch.bool).to(dev, non_blocking=True)
-        fused = B.fuse_scans_batch(hp, scan32, torch.stack(pose0s, 0), torch.stack(poses, 0))
-        hps = torch.where(hps < 0, torch.full_like(hps, n_cls), hps)
-        hkeep = table.view(-1)[scan32.long() * (n_cls + 1) + hps]
-    else:
-        fused = torch.empty((0, 4), dtype=torch.float32, device=dev)
-        hl = torch.empty(0, dtype=torch.int64, device=dev)
-        hkeep = torch.empty(0, dtype=torch.bool, device=dev)
-    # job-major rows: [current | partner's current] for the single-frame mix, [current | history | partner's current | partner's
-    # history] for the fused one
-    s_pts, s_lab, s_n1, s_n2 = [], [], [], []
-    m_pts, m_lab, m_keep, m_len, m_n1, m_n2 = [], [], [], [], [], []
-    ones = torch.ones(max([c[0].shape[0] for c in current] + [1]), dtype=torch.bool, device=dev)
-    current = iter(current)
+def _mix_and_voxelize(used, heads, fused, fused_lab, fused_keep, mix, aug, voxel_size, time_flag=False) -> Dict:
+    """The tail of both datasets' mixed batch.  used[b] = [sample b, its partner or None]; heads: for every cloud of `used` that is
+    not None, in order, (head rows [n, F] - current scan or keyframe, cut to the mixed columns -, labels int64, first row and number
+    of rows of its history in `fused`); fused [Nh, F], fused_lab int64, fused_keep bool: the fused history rows of all those clouds,
+    un-filtered, with the class-step rule (and whatever else drops a row) as a keep byte - no compaction before the mix.
+    ts_stage_mix on the single-frame pairs and on the fused pairs of the whole batch (three launches each, their row counts in one
+    host read), the augmentation of both clouds through the mix's job column, the minima of the mixed single-frame clouds
+    (ts_segment_min3), the clamp of EVERY fused row against them as one stable compaction (ts_stage_clamp_compact: after a mix the
+    head is no prefix of the fused cloud any more; semantickitti_voxel_ms.py:121-124) with the second host read, the survivors per
+    sample, and both voxelisations.  point_mask stays what the reference's collate_batch makes it (_prefix_mask).
+    time_flag: append SemanticKITTI's flag column to the fused rows before their mix - 1 on a head, 0 on history."""
+    dev, nb = fused.device, len(used)
+    # job-major rows: [head | partner's head] for the single-frame mix, [head | history | partner's head | partner's history] for
+    # the fused one
+    s_pts, s_lab, s_n = [], [], ([], [])
+    m_pts, m_lab, m_keep, m_len, m_n = [], [], [], [], ([], [])
+    ones = torch.ones(max(int(h[0].shape[0]) for h in heads), dtype=torch.bool, device=dev)
+    heads = iter(heads)
     for pair in used:
-        sizes = []
-        for c in pair:
-            if c is None:
-                sizes.append((0, 0))
-                m_len += [0, 0]
-                continue
-            scan, lab, first, nh = next(current)
-            cur4 = scan[:, :4]
-            n = int(cur4.shape[0])
-            s_pts.append(cur4)
-            s_lab.append(lab)
-            m_pts += [cur4, fused[first:first + nh]]
-            m_lab += [lab, hl[first:first + nh]]
-            m_keep += [ones[:n], hkeep[first:first + nh]]
+        for k, c in enumerate(pair):
+            n = nh = 0
+            if c is not None:
+                head, lab, first, nh = next(heads)
+                n = int(head.shape[0])
+                s_pts.append(head)
+                s_lab.append(lab)
+                m_pts += [head, fused[first:first + nh]]
+                m_lab += [lab, fused_lab[first:first + nh]]
+                m_keep += [ones[:n], fused_keep[first:first + nh]]
             m_len += [n, nh]
-            sizes.append((n, nh))
-        s_n1.append(sizes[0][0])
-        s_n2.append(sizes[1][0])
-        m_n1.append(sizes[0][0] + sizes[0][1])
-        m_n2.append(sizes[1][0] + sizes[1][1])
+            s_n[k].append(n)
+            m_n[k].append(n + nh)
+    ms_in = torch.cat(m_pts, 0)
+    if time_flag:
+        flag = (rows_index(m_len, dev) % 2 == 0).to(torch.float32)      # append_time_flag (:253-257): the pieces alternate
+        ms_in = torch.cat([ms_in, flag.unsqueeze(1)], 1)
     totals = torch.empty((2, nb), dtype=torch.int64, device=dev)
-    cur, cur_lab, cur_b32, _ = B.stage_mix(torch.cat(s_pts, 0), torch.cat(s_lab, 0), mix, s_n1, s_n2, totals=totals[0])
-    flag = (rows_index(m_len, dev) % 2 == 0).to(torch.float32)          # append_time_flag (:253-257): the pieces alternate
-    ms_in = torch.cat([torch.cat(m_pts, 0), flag.unsqueeze(1)], 1)
-    ms, ms_lab, ms_b32, _ = B.stage_mix(ms_in, torch.cat(m_lab, 0), mix, m_n1, m_n2, keep=torch.cat(m_keep, 0), totals=totals[1])
+    cur, cur_lab, cur_b32, _ = B.stage_mix(torch.cat(s_pts, 0), torch.cat(s_lab, 0), mix, *s_n, totals=totals[0])
+    ms, ms_lab, ms_b32, _ = B.stage_mix(ms_in, torch.cat(m_lab, 0), mix, *m_n, keep=torch.cat(m_keep, 0), totals=totals[1])
     n_cur, n_mixed = totals.tolist()                                    # host read 1 (rows of both mixes, all samples)
     cur, cur_lab, cur_b32 = cur[:sum(n_cur)], cur_lab[:sum(n_cur)], cur_b32[:sum(n_cur)]
     ms, ms_lab, ms_b32 = ms[:sum(n_mixed)], ms_lab[:sum(n_mixed)], ms_b32[:sum(n_mixed)]
@@ -615,13 +593,44 @@ def _build_multiscan_batch_mix(scans, partners, mix, voxel_size, steps, aug, mov
         augment_points(ms, rec_dev, ms_b32, out=ms)
     cur_b = cur_b32.long()
     lo = B.segment_min3(cur, cur_b, nb)
-    ms_b = ms_b32.long()
-    idx = (ms[:, :3] >= lo[ms_b]).all(1).nonzero().squeeze(1)           # host read 2 (the compaction's size)
-    ms, ms_lab, ms_b, ms_b32 = ms[idx].contiguous(), ms_lab[idx], ms_b[idx], ms_b32[idx]
-    start = torch.searchsorted(ms_b, torch.arange(nb + 1, device=dev))
-    n_ms = (start[1:] - start[:-1]).tolist()                            # host read 3 (fused rows per sample)
+    ms, ms_lab, ms_b, ms_b32, counts = B.stage_clamp_compact(ms, ms_lab, ms_b32, lo)
+    n_ms = counts.tolist()                                              # host read 2 (fused rows per sample)
+    kept = sum(n_ms)
+    ms, ms_lab, ms_b, ms_b32 = ms[:kept], ms_lab[:kept], ms_b[:kept], ms_b32[:kept]
     return _voxelize_layout(cur, cur_lab, cur_b, n_cur, ms, ms_lab, ms_b, ms_b32, n_ms, _prefix_mask(n_cur, n_ms, dev), voxel_size,
-                            [s.get("name", "") for s in scans])
+                            [pair[0].get("name", "") for pair in used])
+
+
+def _build_multiscan_batch_mix(scans, partners, mix, voxel_size, steps, aug, moving=None, partner_moving=None) -> Dict:
+    """build_multiscan_batch with mix=: the samples' and the used partners' history scans (_walk_scans) pose-fused in ONE launch
+    (fuse_scans_batch), the class-step rule as a keep byte per row (_step_table, _step_keep), then _mix_and_voxelize with the time
+    flag: two host reads before the voxelisation.  moving= / partner_moving=: the samples' and the partners' moving-object
+    augmentation first, one ts_stage_moving_apply launch for all of them (_moved_clouds), which hands out the current rows, the
+    fused history and the pseudo classes of the raw classes as they were."""
+    dev = scans[0]["points"][-1].device
+    # the clouds that take part, in order: every sample's own, then its partner's where its mix moves rows of one
+    used = [[s, partners[b] if mix[b].kind != M.NONE else None] for b, s in enumerate(scans)]
+    clouds = [c for pair in used for c in pair if c is not None]
+    (hist_pts, hist_lab, hist_ps, lengths, owner, pose0s, poses, rows), current = _walk_scans(clouds, steps)
+    if moving is not None:
+        params = [q for b, pair in enumerate(used) for c, q in zip(pair, (moving[b], partner_moving[b])) if c is not None]
+        cur_all, cur_lab_all, fused, hl, hps, _ = _moved_clouds(clouds, params)
+        n_cur = [int(c[0].shape[0]) for c in current]
+        current = [(p, l, c[2], c[3]) for p, l, c in zip(torch.split(cur_all, n_cur), torch.split(cur_lab_all, n_cur), current)]
+    elif hist_pts:
+        hl = torch.cat(hist_lab, 0).long()
+        hps = hl if all(c.get("pseudo") is None for c in clouds) else torch.cat(hist_ps, 0).long()
+        fused = B.fuse_scans_batch(torch.cat(hist_pts, 0).contiguous(), rows_index32(lengths, dev), torch.stack(pose0s, 0),
+                                   torch.stack(poses, 0))
+    else:
+        fused = torch.empty((0, 4), dtype=torch.float32, device=dev)
+        hl = torch.empty(0, dtype=torch.int64, device=dev)
+    if hist_pts:
+        hkeep = _step_keep(_step_table("kitti-table", rows, owner, dev)[0], rows_index32(lengths, dev), hps, neg_last=True)
+    else:
+        hkeep = torch.empty(0, dtype=torch.bool, device=dev)
+    heads = [(scan[:, :4], lab, first, nh) for scan, lab, first, nh in current]
+    return _mix_and_voxelize(used, heads, fused, hl, hkeep, mix, aug, voxel_size, time_flag=True)
 
 
 def build_multiscan_batch(scans: List[Dict], voxel_size: float, steps: Sequence[int], aug=None, mix=None, partners=None,
@@ -636,8 +645,9 @@ def build_multiscan_batch(scans: List[Dict], voxel_size: float, steps: Sequence[
     before the clamp minima are taken - two launches and one small host-to-device copy more than aug=None, the un-augmented path.
     mix: one MixParams per sample (data/mix.py) or None; partners[b]: the scan dict of sample b's partner (None where its mix needs
     none).  With it every sample is mixed with its partner - PolarMix / LaserMix on the single-frame pair and on the fused pair,
-    semantickitti_ms.py:151-237 - before the augmentation (_build_multiscan_batch_mix); mix=None is the path without it, launch
-    for launch.
+    semantickitti_ms.py:151-237 - before the augmentation, and every fused row is clamped by ts_stage_clamp_compact
+    (_build_multiscan_batch_mix, _mix_and_voxelize: two host reads before the voxelisation); mix=None is the path without it,
+    launch for launch.
     moving: one MovingParams per sample (data/moving.py; None in the list: nothing moves) or None; partner_moving[b]: the
     MovingParams of sample b's partner.  The SMSA recipe (semantickitti_ms_ms.py): scan dicts then carry `raw_labels` - one tensor
     of FULL uint32 labels (any integer dtype wide enough) per scan, parallel to `points` - and `labels` is not read: the classes are

@@ -321,3 +321,71 @@ def test_stage_paths_agree_and_mix_none_is_the_old_path(g_multiscan):
         S.build_multiscan_batch(scans, 0.05, steps, mix=mix[:2], partners=partners)
     with pytest.raises(ValueError):
         S.build_multiscan_batch(scans, 0.05, steps, mix=mix, partners=[None, None, None])
+
+
+# ------------------------------------------------------------------------------------------------ 4. the shared tail at its edges
+EDGE_STEPS = [0, 1, 2, 1, 1, 1, 1, 1, 1, 1, 3, 1]     # classes 1 .. 8: PolarMix's instances; 9 and 11: background from every scan
+NAN_MARK, ZMIN_MARK, Z_MIN = 2.0, 3.0, -7.0           # intensities no cloud() row has (theirs are below 1); cloud() has z >= -6
+
+
+def edge_scans():
+    """Three scan dicts whose fused rows have 5 columns: current scans of 300, 257 and 130 points, history of 251 + 249, 40 and no
+    points, identity-plus-small-translation poses (none along z: a fused row keeps its z bits).  The sample boundaries fall inside
+    a 64-lane wave and inside a 256-row block.  In sample 0 the current row 0 lies below everything else, outside the PolarMix
+    sector; one history row has z on that minimum exactly (ZMIN_MARK in column 3), another a NaN x (NAN_MARK); both of a class
+    that every scan contributes and that is no instance class."""
+    rng = np.random.RandomState(5)
+    scans = []
+    for b, sizes in enumerate(([251, 249, 300], [40, 257], [130])):
+        clouds = [cloud(rng, n, 4, classes=len(EDGE_STEPS)) for n in sizes]
+        poses = [np.eye(4, dtype=np.float32) for _ in sizes]
+        for t, pose in enumerate(poses):
+            pose[:2, 3] = 0.05 * (t + 1), -0.03 * (t + b)
+        scans.append({"points": [c[0] for c in clouds], "labels": [c[1] for c in clouds], "poses": poses, "name": f"edge{b}"})
+    pts, lab = scans[0]["points"], scans[0]["labels"]
+    pts[2][0], lab[2][0] = (-4.16, -9.09, Z_MIN, 0.5), 9          # yaw +2.0: outside (ALPHA, ALPHA + pi)
+    pts[0][5], lab[0][5] = (-5.0, -9.0, Z_MIN, ZMIN_MARK), 9
+    pts[1][7], lab[1][7] = (np.nan, 3.0, -1.0, NAN_MARK), 11
+    return [{k: [T(a) for a in v] if k != "name" else v for k, v in s.items()} for s in scans]
+
+
+@pytest.mark.parametrize("with_aug", [False, True])
+def test_shared_tail_at_its_edges(with_aug):
+    scans = edge_scans()
+    mix = [polar(), laser(1), M.MixParams()]
+    partners = [scans[1], scans[2], None]            # a partner with history, one without; sample 0's marked rows are in job 0 only
+    aug = [A.draw_train_params(np.random.RandomState(17 + b)) for b in range(3)] if with_aug else None
+    calls = []
+    real = B.stage_clamp_compact
+
+    def record(*a):
+        calls.append((a, real(*a)))
+        return calls[-1][1]
+    B.stage_clamp_compact = record
+    try:
+        batched = S.build_multiscan_batch(scans, 0.05, EDGE_STEPS, aug=aug, mix=mix, partners=partners)
+        assert len(calls) == 1                                       # the kernel, once per batched call
+        again = S.build_multiscan_batch(scans, 0.05, EDGE_STEPS, aug=aug, mix=mix, partners=partners)
+        assert len(calls) == 2
+        per_sample = S.build_multiscan_batch_per_sample(scans, 0.05, EDGE_STEPS, aug=aug, mix=mix, partners=partners)
+        assert len(calls) == 2                                       # the per-sample path keeps its own clamp
+    finally:
+        B.stage_clamp_compact = real
+    same_batches(batched, per_sample)
+    same_batches(batched, again)
+    n_ms = batched["num_points_ms"].view(-1)
+    assert int(n_ms.sum()) == batched["point_mask"].numel() == batched["targets_mapped_ms"].F.shape[0]
+    assert int(batched["num_points"][2]) == 130 and int(n_ms[2]) == 130          # un-mixed, no history: its own scan
+    # what the clamp was given and what it let through
+    (rows, _, sample32, lo), (out, _, _, _, counts) = calls[0]
+    assert rows.ndim == 2 and rows.shape[1] == 5 and rows.shape[0] > int(n_ms.sum()) and lo.shape == (3, 3)
+    assert torch.equal(counts.cpu(), n_ms) and bool((sample32[1:] >= sample32[:-1]).all())
+    out = out[:int(counts.sum())]
+    nan_in, nan_out = torch.isnan(rows).any(1), torch.isnan(out).any(1)
+    assert int(nan_in.sum()) == 1 and float(rows[nan_in][0, 3]) == NAN_MARK and int(sample32[nan_in]) == 0
+    assert not bool(nan_out.any()) and not bool((out[:, 3] == NAN_MARK).any())   # the NaN row fell to the clamp
+    assert not bool(torch.isnan(batched["lidar_ms"].F).any())
+    edge = rows[:, 3] == ZMIN_MARK
+    assert int(edge.sum()) == 1 and int(sample32[edge]) == 0
+    assert torch.equal(rows[edge][0, 2].view(torch.int32), lo[0, 2].view(torch.int32))      # z exactly on the minimum ...
+    assert int((out[:, 3] == ZMIN_MARK).sum()) == 1                                         # ... survives

@@ -13,6 +13,7 @@ from conftest import GOLDEN
 
 pytestmark = pytest.mark.gpu
 
+from taseg_amd import backend as B  # noqa: E402
 from taseg_amd.data import augment as A  # noqa: E402
 from taseg_amd.data import mix as M  # noqa: E402
 from taseg_amd.data import nuscenes as N  # noqa: E402
@@ -133,10 +134,24 @@ def test_paths_agree_on_mixed_kinds_and_missing_history(g_multiscan_nus):
     mix = [polar(), M.MixParams(kind=M.LASER, strategy=1, degrees=True, dataset="nuscenes"), M.MixParams()]
     partners = [samples[1], samples[0], None]
     aug = [A.draw_train_params(rng) for _ in three]
-    for au in (aug, None):
-        a = N.build_nuscenes_batch(three, VOXEL, steps, aug=au, mix=mix, partners=partners)
-        same_batches(a, N.build_nuscenes_batch_per_sample(three, VOXEL, steps, aug=au, mix=mix, partners=partners))
-        same_batches(a, N.build_nuscenes_batch(three, VOXEL, steps, aug=au, mix=mix, partners=partners))
+    calls = []
+    real = B.stage_clamp_compact
+
+    def record(*a):
+        calls.append(a[0].shape)
+        return real(*a)
+    B.stage_clamp_compact = record
+    try:
+        for au in (aug, None):
+            a = N.build_nuscenes_batch(three, VOXEL, steps, aug=au, mix=mix, partners=partners)
+            n_calls = len(calls)
+            same_batches(a, N.build_nuscenes_batch_per_sample(three, VOXEL, steps, aug=au, mix=mix, partners=partners))
+            assert len(calls) == n_calls                             # the per-sample path keeps its own clamp
+            same_batches(a, N.build_nuscenes_batch(three, VOXEL, steps, aug=au, mix=mix, partners=partners))
+    finally:
+        B.stage_clamp_compact = real
+    # ts_stage_clamp_compact ran once per batched call, on rows of in_feature_dim columns
+    assert len(calls) == 4 and all(len(shape) == 2 and shape[1] == 4 for shape in calls)
     n = a["num_points"].view(-1).tolist()
     assert n[2] == samples[1]["points"].shape[0] and n[0] != samples[0]["points"].shape[0]
     # a history-less partner, a self-partner (the same dict), a history-less sample that is mixed

@@ -1,5 +1,5 @@
-"""The data stage's shared host helpers on CPU tensors: the walk over scan dicts, both class-step rules, the bounded layout cache
-and the prefix mask (taseg_amd/data/stage.py, nuscenes.py)."""
+"""The data stage's shared host helpers on CPU tensors: the walks over scan dicts and sample dicts, both class-step rules and their
+lookup, the default frame offsets, the bounded layout cache and the prefix mask (taseg_amd/data/stage.py, nuscenes.py)."""
 import torch
 
 from taseg_amd.data import nuscenes as N
@@ -39,6 +39,56 @@ def test_walk_scans_lists_every_history_scan_once():
                     [False, True, False, False, False],      # delta -3
                     [False, True, True, False, False],       # delta -2
                     [False, True, False, False, False]]      # delta -1
+
+
+def _sample_dict(n_key, sweeps, seed):
+    """a nuScenes sample dict with len(sweeps) selected sweeps; every tensor is distinct"""
+    g = torch.Generator().manual_seed(seed)
+    return dict(points=torch.randn(n_key, 5, generator=g), labels=torch.randint(0, len(STEPS), (n_key,), generator=g),
+                hist_points=[torch.randn(n, 5, generator=g) for n in sweeps],
+                hist_labels=[torch.randint(0, len(STEPS), (n,), generator=g) for n in sweeps],
+                hist_pseudo=[torch.randint(0, len(STEPS), (n,), generator=g) for n in sweeps],
+                params=torch.randn(len(sweeps), 28, generator=g, dtype=torch.float64))
+
+
+def test_walk_sweeps_lists_every_sweep_once():
+    clouds = [_sample_dict(4, [], 0),                                            # the first keyframe of its scene: no sweeps
+              _sample_dict(3, [2, 5, 1], 1),
+              _sample_dict(2, [3, 2], 2)]                                        # a partner: walked like a sample
+    pts, lab, pseudo, lengths, owner, rows, params = N._walk_sweeps(clouds, STEPS)
+    assert lengths == [2, 5, 1, 3, 2] and owner == [1, 1, 1, 2, 2]
+    for got, key in ((pts, "hist_points"), (lab, "hist_labels"), (pseudo, "hist_pseudo")):
+        want = clouds[1][key] + clouds[2][key]
+        assert len(got) == len(want) and all(a is b for a, b in zip(got, want))
+    # one row per sweep, by its position in ITS cloud: the partner's sweeps start at 0 again
+    assert rows == [N._nusc_row(pos, STEPS) for pos in (0, 1, 2, 0, 1)]
+    assert len(params) == 2 and params[0] is clouds[1]["params"] and params[1] is clouds[2]["params"]
+    assert N._walk_sweeps(clouds[:1], STEPS) == ([],) * 7
+
+
+def test_step_keep_against_a_loop():
+    g = torch.Generator().manual_seed(3)
+    for neg_last in (True, False):
+        table = torch.rand(5, len(STEPS) + neg_last, generator=g) < 0.5
+        assert table.any() and not table.all()
+        scan = torch.randint(0, 5, (200,), generator=g, dtype=torch.int32)
+        cls = torch.randint(-1 if neg_last else 0, len(STEPS), (200,), generator=g)
+        assert not neg_last or (cls == -1).sum() > 10
+        got = S._step_keep(table, scan, cls, neg_last=neg_last)
+        want = [bool(table[int(s_), int(c) if c >= 0 else table.shape[1] - 1]) for s_, c in zip(scan, cls)]
+        assert got.dtype == torch.bool and got.tolist() == want
+        assert S._step_keep(table, scan.long(), cls, neg_last=neg_last).tolist() == want
+        none = S._step_keep(table, scan[:0], cls[:0], neg_last=neg_last)
+        assert none.dtype == torch.bool and none.shape == (0,)
+    # the SemanticKITTI rows: class -1 is never kept, whatever the scan
+    table = torch.tensor([S._kitti_row(d, STEPS) for d in (-5, -2)])
+    assert S._step_keep(table, torch.tensor([0, 1, 0, 1]), torch.tensor([-1, -1, 3, 3]), neg_last=True).tolist() == [False, False, True, False]
+
+
+def test_deltas_default_and_given():
+    assert S._deltas(_scan_dict([2, 1, 3, 2], 0)) == [-3, -2, -1]
+    assert S._deltas(_scan_dict([3, 2, 5], 1, deltas=[-5, -2])) == [-5, -2]
+    assert S._deltas(_scan_dict([4], 2)) == [] and S._deltas(_scan_dict([4], 2, deltas=None)) == []
 
 
 def test_nuscenes_rows_by_sweep_position():
