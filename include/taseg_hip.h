@@ -959,6 +959,37 @@ size_t ts_stage_clamp_compact_workspace_bytes(int64_t n, int32_t n_samples);
 int ts_stage_clamp_compact(const float *points, int64_t n, int32_t point_stride, const int64_t *labels, const int32_t *sample,
                            const float *lo, int32_t n_samples, float *out, int64_t *out_labels, int64_t *out_sample,
                            int32_t *out_sample32, int64_t *counts, void *ws, size_t ws_bytes, ts_stream_t stream);
+/* Both fused clouds of the mask-distillation recipe's batch from ONE pass over the pose-fused, un-filtered history
+ * (csrc/kd_stage.hip; taseg_amd/data/kd.py): semantickitti_ms_kd.py:141-147 - the student's cloud `raw_data_ms` (history filtered
+ * by the pseudo labels under FLEXIBLE_STEPS) and the teacher's `raw_data_ms_gt` (the same history filtered by the annotations under
+ * FLEXIBLE_STEPS_GT), the masks of :332-344, `append_time_flag` :280-284 - and semantickitti_voxel_ms_kd.py:125-132, both clouds
+ * clamped to the current scan's minimum.  It replaces ts_stage_keep_flags -> nonzero -> searchsorted -> ts_stage_layout, run once
+ * per cloud.  cur [n_cur, cur_stride >= 4] float32 the current scans of all samples one after the other (columns 0 .. 3 are
+ * read), cur_labels [n_cur] int64, cur_start [n_samples + 1] int64 their cumulative row counts; hist [n_hist, 4] float32 the
+ * history rows, their samples ASCENDING, hist_labels [n_hist] int64, scan_idx [n_hist] int32; cls_a / cls_b [n_hist] int64 the
+ * class column of either rule (negative: column neg_col); table_a / table_b [n_scans, table_cols] bytes; sample_of_scan [n_scans]
+ * int64; lo [n_samples, 3] float32 (ts_segment_min3 of the current scans), 1 <= n_samples <= TS_STAGE_PAIR_MAX_SAMPLES.
+ * History row i belongs to cloud A iff table_a[scan_idx[i]][cls_a[i]] != 0 and x >= lo[s][0] && y >= lo[s][1] && z >= lo[s][2]
+ * with s = sample_of_scan[scan_idx[i]] - a NaN on either side fails, as numpy's `>=`; a row whose sample is outside [0,
+ * n_samples) belongs to neither - and to cloud B iff the same holds with table_b / cls_b.
+ * out_a / out_b [capacity, 5] float32: the clouds sample-major, each sample's current scan first, its kept history behind it in
+ * input order; column 4 is 1 on a current row and 0 on a history row.  Cloud A carries labels and the is-current byte
+ * (`point_mask`), both carry the sample index as int64 and int32.  counts [n_samples, 3] int64: kept history rows of A, of B, and
+ * the history rows that pass B's step rule BEFORE the clamp (the reference's `num_points_ms_gt` is never updated after it,
+ * semantickitti_voxel_ms_kd.py:88, :132) - the caller reads them once per batch; cloud A holds n_cur + sum(counts[:, 0]) rows,
+ * cloud B n_cur + sum(counts[:, 1]), the rows behind them are not written.  capacity >= n_cur + n_hist bounds every store.  Three
+ * launches (counts per block of 256 rows from wave ballots; one block per cloud scanning the block counts beside a few summing
+ * the per-sample counts; the scatter by rank of history and current rows);
+ * no atomics: the same bits every run. */
+#define TS_STAGE_PAIR_MAX_SAMPLES 64
+size_t ts_stage_layout_pair_workspace_bytes(int64_t n_hist, int32_t n_samples);
+int ts_stage_layout_pair(const float *cur, int64_t n_cur, int32_t cur_stride, const int64_t *cur_labels, const int64_t *cur_start,
+                         const float *hist, int64_t n_hist, const int64_t *hist_labels, const int32_t *scan_idx,
+                         const int64_t *cls_a, const int64_t *cls_b, const uint8_t *table_a, const uint8_t *table_b,
+                         int32_t n_scans, int32_t table_cols, int32_t neg_col, const int64_t *sample_of_scan, const float *lo,
+                         int32_t n_samples, float *out_a, int64_t *out_labels_a, int64_t *out_sample_a, int32_t *out_sample32_a,
+                         uint8_t *out_is_cur_a, float *out_b, int64_t *out_sample_b, int32_t *out_sample32_b, int64_t capacity,
+                         int64_t *counts, void *ws, size_t ws_bytes, ts_stream_t stream);
 /* Moving-object augmentation of the SMSA recipe (csrc/moving.hip; taseg_amd/data/moving.py draws the parameters):
  * semantickitti_ms_ms.py:305-351 `static2moving` and :353-384 `moving2static`, called at :152-163 for the sample and at :198-207 /
  * :248-257 for its mix partner, on the current scan and the pose-fused UN-FILTERED history rows, before the class-step mask

@@ -188,6 +188,9 @@ SIGNATURES = {
     "ts_stage_mix": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _sz, _vp]),
     "ts_stage_clamp_compact_workspace_bytes": (_sz, [_i64, _i32]),
     "ts_stage_clamp_compact": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "ts_stage_layout_pair_workspace_bytes": (_sz, [_i64, _i32]),
+    "ts_stage_layout_pair": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp,
+                                    _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _sz, _vp]),
     "ts_stage_moving_workspace_bytes": (_sz, [_i64, _i32, _i64]),
     "ts_stage_moving_stats": (_i32, [_vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ts_stage_moving_apply": (_i32, [_vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp]),

@@ -1420,6 +1420,56 @@ def stage_layout(cur, cur_lab, cur_b, hist, hist_lab, hist_b, idx, cur_start, ke
     return pts, lab, sample, sample32, is_cur
 
 
+def stage_layout_pair(cur, cur_lab, cur_start, hist, hist_lab, scan_idx, cls_a, cls_b, table_a, table_b, sample_of_scan, lo,
+                      neg_col=-1):
+    """csrc/kd_stage.hip: both fused clouds of a mask-distillation batch from one pass over the history, in three launches.  cur
+    [Nc, F >= 4] float32 the current scans one after the other, cur_lab [Nc] int64, cur_start [B + 1] int64 their cumulative row
+    counts; hist [Nh, 4] float32 the pose-fused un-filtered history rows, samples ascending, hist_lab [Nh] int64, scan_idx [Nh]
+    int32; cls_a / cls_b [Nh] int64 and table_a / table_b [S, C] bool: the class column and the class-step table of either cloud
+    (a negative class reads column neg_col); sample_of_scan [S] int64; lo [B <= 64, 3] float32 (segment_min3 of the current scans).
+    Returns ((pts_a [Nc + Nh, 5], labels int64, sample int64, sample int32, is_current bool), (pts_b [Nc + Nh, 5], sample int64,
+    sample int32), counts [B, 3] int64): kept history rows of A, of B, and the rows passing B's step rule before the clamp, per
+    sample.  Cloud A holds Nc + counts[:, 0].sum() rows, cloud B Nc + counts[:, 1].sum() - the caller reads counts.  No host read
+    here."""
+    L.require_device(cur, cur_lab, cur_start, hist, hist_lab, scan_idx, cls_a, cls_b, table_a, table_b, sample_of_scan, lo)
+    cur, hist, lo, scan_idx = _f32(cur, "cur"), _f32(hist, "hist"), _f32(lo, "lo"), _i32(scan_idx, "scan_idx")
+    if cur.ndim != 2 or cur.shape[1] < 4 or hist.ndim != 2 or hist.shape[1] != 4:
+        raise TypeError("cur must be float32 [n, F >= 4], hist float32 [n, 4]")
+    if lo.ndim != 2 or lo.shape[1] != 3 or not 1 <= lo.shape[0] <= 64:
+        raise ValueError("stage_layout_pair: lo must be [1 .. 64, 3]")
+    n_cur, n_hist, nb = cur.shape[0], hist.shape[0], lo.shape[0]
+    for t, name in ((cur_lab, "cur_lab"), (cur_start, "cur_start"), (hist_lab, "hist_lab"), (cls_a, "cls_a"), (cls_b, "cls_b"),
+                    (sample_of_scan, "sample_of_scan")):
+        if t.dtype != torch.int64:
+            raise TypeError(name + " must be int64")
+    cur_lab, cur_start, hist_lab = cur_lab.contiguous(), cur_start.contiguous(), hist_lab.contiguous()
+    cls_a, cls_b, sample_of_scan = cls_a.contiguous(), cls_b.contiguous(), sample_of_scan.contiguous()
+    table_a, table_b = table_a.contiguous(), table_b.contiguous()
+    if table_a.dtype not in (torch.bool, torch.uint8) or table_a.ndim != 2 or table_b.dtype != table_a.dtype or \
+            table_b.shape != table_a.shape or sample_of_scan.shape != (table_a.shape[0],):
+        raise TypeError("table_a / table_b must be bool / uint8 matrices of one shape, one row per entry of sample_of_scan")
+    if cur_lab.shape != (n_cur,) or cur_start.shape != (nb + 1,) or hist_lab.shape != (n_hist,) or scan_idx.shape != (n_hist,) or \
+            cls_a.shape != (n_hist,) or cls_b.shape != (n_hist,):
+        raise ValueError("stage_layout_pair: one label per current row, B + 1 starts, one label, scan and class per history row")
+    dev, cap = cur.device, n_cur + n_hist
+    pts_a = torch.empty((cap, 5), dtype=torch.float32, device=dev)
+    pts_b = torch.empty((cap, 5), dtype=torch.float32, device=dev)
+    lab_a = torch.empty(cap, dtype=torch.int64, device=dev)
+    b_a, b_b = torch.empty(cap, dtype=torch.int64, device=dev), torch.empty(cap, dtype=torch.int64, device=dev)
+    b32_a, b32_b = torch.empty(cap, dtype=torch.int32, device=dev), torch.empty(cap, dtype=torch.int32, device=dev)
+    is_cur = torch.empty(cap, dtype=torch.bool, device=dev)
+    counts = torch.empty((nb, 3), dtype=torch.int64, device=dev)
+    lib = L.load()
+    ws_bytes = lib.ts_stage_layout_pair_workspace_bytes(n_hist, nb)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    L.check(lib.ts_stage_layout_pair(L.ptr(cur), n_cur, cur.shape[1], L.ptr(cur_lab), L.ptr(cur_start), L.ptr(hist), n_hist,
+                                     L.ptr(hist_lab), L.ptr(scan_idx), L.ptr(cls_a), L.ptr(cls_b), L.ptr(table_a), L.ptr(table_b),
+                                     table_a.shape[0], table_a.shape[1], int(neg_col), L.ptr(sample_of_scan), L.ptr(lo), nb,
+                                     L.ptr(pts_a), L.ptr(lab_a), L.ptr(b_a), L.ptr(b32_a), L.ptr(is_cur), L.ptr(pts_b), L.ptr(b_b),
+                                     L.ptr(b32_b), cap, L.ptr(counts), L.ptr(ws), ws_bytes, L.stream()), "ts_stage_layout_pair")
+    return (pts_a, lab_a, b_a, b32_a, is_cur), (pts_b, b_b, b32_b), counts
+
+
 def stage_split_voxels(coords4, index, inverse, row_sample, n_samples):
     """csrc/stage.hip: after sparse_quantize on a whole batch -> (vox [m, 4] int32 = coords4[index], offset [B] int32 cumulative
     voxel counts, inverse_local [n] int64 = voxel index inside the point's own sample)."""

@@ -14,8 +14,9 @@ Split between host and device the way the work splits:
   device  the per-point arithmetic (ts_stage_augment, csrc/stage.hip): float64 in the reference's order, one rounding to float32,
           switched-off steps skipped (`augment_points`; the stage functions of data/stage.py and data/nuscenes.py take `aug=`).
 
-LaserMix / PolarMix, which the recipe applies before this augmentation, are in data/mix.py.  The image-side jitter and the TIAF /
-KD variants (`aug_points_rgb_ms`, `aug_points_ms_gt`) are not here.
+LaserMix / PolarMix, which the recipe applies before this augmentation, are in data/mix.py.  The KD variant `aug_points_ms_gt`
+(seg_utils.py:168-239: the same draws and arithmetic on three clouds) is this kernel with the sample's record on the teacher's
+rows too (data/kd.py).  The image-side jitter and the TIAF variant (`aug_points_rgb_ms`) are not here.
 """
 from dataclasses import dataclass
 from typing import List, Optional, Sequence, Tuple, Union

@@ -17,6 +17,8 @@ The rotate / scale / flip / translate augmentation of the training recipe and th
 LaserMix / PolarMix (:151-237) go in the same way: `mix=[draw_mix_params(rng, omega) ...]` and `partners=` (taseg_amd/data/mix.py).
 The SMSA recipe (semantickitti_ms_ms.py: 26 classes, the moving-object augmentation) reads the full labels:
 `multiscan_sample(..., full_labels=True)` adds `raw_labels`, which `moving_tables` and `moving=` take (taseg_amd/data/moving.py).
+The mask-distillation recipe (semantickitti_ms_kd.py: a third cloud filtered by the annotations) reads `multiscan_sample(...,
+canon=True)`, whose `canon` column `build_kd_batch` takes (taseg_amd/data/kd.py).
 """
 import os
 from typing import Dict, List, Optional, Sequence
@@ -106,18 +108,20 @@ class KittiSequence:
 
 
 def multiscan_sample(seq: KittiSequence, frame: int, multiscan: int, steps: Sequence[int], device="cuda",
-                     pseudo_subdir: Optional[str] = None, full_labels: bool = False) -> Dict:
+                     pseudo_subdir: Optional[str] = None, full_labels: bool = False, canon: bool = False) -> Dict:
     """Frame `frame` and its up-to-`multiscan` history frames (ONLY_HISTORY, oldest first; frames before the start of
     the sequence are skipped like the reference's try/except, :285-291) as resident tensors for build_multiscan_batch.
     Pseudo labels: the annotations themselves (PSEUDO_MASK 'gt') or the .label files under `pseudo_subdir`.
     full_labels=True adds `raw_labels`: the full uint32 label words of every scan (int64), for the SMSA recipe's stage (`moving=`);
-    with `pseudo_subdir` the pseudo classes are then those of the 26-class map."""
+    with `pseudo_subdir` the pseudo classes are then those of the 26-class map.
+    canon=True adds `canon`: per history scan the class whose canonical raw id the ANNOTATION is, or -1 - what the teacher's mask
+    of the mask-distillation recipe compares (semantickitti_ms_kd.py:339-344), for `build_kd_batch` (taseg_amd/data/kd.py)."""
     dev = torch.device(device)
     frames = [frame + d for d in range(-multiscan, 0) if frame + d >= 0] + [frame]
-    pts, labs, poses, pseudo, full = [], [], [], [], []
-    canon = _CANON
+    pts, labs, poses, pseudo, full, canon_gt = [], [], [], [], [], []
+    table = _CANON
     if full_labels:
-        from .moving import CANONICAL_CLASS as canon
+        from .moving import CANONICAL_CLASS as table
     for f in frames:
         raw = seq.raw_labels(f) if seq.has_labels else np.zeros(len(seq.points(f)), dtype=np.int64)
         if full_labels:
@@ -127,7 +131,11 @@ def multiscan_sample(seq: KittiSequence, frame: int, multiscan: int, steps: Sequ
         poses.append(torch.from_numpy(seq.poses[f]).to(dev))
         if f != frame:
             praw = raw if pseudo_subdir is None else seq.raw_labels(f, pseudo_subdir)
-            pseudo.append(torch.from_numpy(canon[praw]).to(dev))
+            pseudo.append(torch.from_numpy(table[praw]).to(dev))
+            if canon:
+                canon_gt.append(torch.from_numpy(table[raw]).to(dev))
     extra = {"raw_labels": full} if full_labels else {}
+    if canon:
+        extra["canon"] = canon_gt
     return {"points": pts, "labels": labs, "poses": poses, "pseudo": pseudo, "deltas": [f - frame for f in frames[:-1]],
             "name": seq.scan_path(frame), **extra}

@@ -16,6 +16,8 @@ semantickitti_voxel_ms.py:77-212); here the same steps run on the GPU on residen
                                            (without mix=: ts_stage_keep_flags, the history rows only; per sample: the ATen clamp)
   augmentation (aug=)  ts_stage_augment    rotate / scale / flip / translate of the current scan and every fused history row with the
                                            sample's AugParams (data/augment.py), before the clamp and both voxelisations
+  three clouds         ts_stage_layout_pair   the mask-distillation recipe's student and teacher clouds from one pass over the
+                                           history, voxelised with one shift (data/kd.py build_kd_batch)
   voxel coordinates    ts_voxel_coords     int32(round_half_even(xyz / voxel)) - min
   voxel grouping       ts_sparse_quantize  radix sort + first-occurrence representative + inverse map
 
@@ -494,9 +496,12 @@ def voxelize_batch_ms(cur_list: List[torch.Tensor], lab_list: List[torch.Tensor]
     return _voxelize_layout(cur, cur_lab, cur_b, n_cur, ms_pts, ms_lab, ms_b, ms_b32, n_ms, point_mask, voxel_size, names)
 
 
-def _voxelize_layout(cur, cur_lab, cur_b, n_cur, ms_pts, ms_lab, ms_b, ms_b32, n_ms, point_mask, voxel_size, names) -> Dict:
+def _voxelize_layout(cur, cur_lab, cur_b, n_cur, ms_pts, ms_lab, ms_b, ms_b32, n_ms, point_mask, voxel_size, names,
+                     return_shift=False) -> Dict:
     """the two voxelisations and the batch_dict of voxelize_batch_ms, from the clouds laid out sample-major: cur [sum n_cur, F] with
-    labels and sample index (int64), the fused clouds ms_pts [sum n_ms, Fm] with labels and sample index (int64 and int32)"""
+    labels and sample index (int64), the fused clouds ms_pts [sum n_ms, Fm] with labels and sample index (int64 and int32).
+    return_shift: returns (batch_dict, the fused clouds' minima [B, 3] int32) - further clouds of the samples share that shift
+    (data/kd.py)."""
     dev, nb = cur.device, len(n_cur)
     coords_ms, mins = B.voxel_coords(ms_pts, voxel_size, batch_idx=ms_b32, n_batch=nb)
     index_ms, inverse_ms = B.sparse_quantize(coords_ms)                 # host read 3 (voxels of the fused clouds)
@@ -505,7 +510,7 @@ def _voxelize_layout(cur, cur_lab, cur_b, n_cur, ms_pts, ms_lab, ms_b, ms_b32, n
     vox_ms, offset_ms, inv_ms = B.stage_split_voxels(coords_ms, index_ms, inverse_ms, ms_b, nb)
     vox_c, offset_c, inv_c = B.stage_split_voxels(coords_c, index_c, inverse_c, cur_b, nb)
     index_ms, index_c = index_ms.long(), index_c.long()
-    return {
+    batch = {
         "name": list(names),
         "lidar": SparseTensor(cur[index_c], vox_c), "targets": SparseTensor(cur_lab[index_c], vox_c),
         "targets_mapped": SparseTensor(cur_lab, coords_c), "inverse_map": SparseTensor(inv_c, coords_c),
@@ -515,6 +520,7 @@ def _voxelize_layout(cur, cur_lab, cur_b, n_cur, ms_pts, ms_lab, ms_b, ms_b32, n
         "num_points_ms": torch.tensor(n_ms).view(-1, 1),
         "offset": offset_c, "offset_ms": offset_ms, "point_mask": point_mask,
     }
+    return (batch, mins) if return_shift else batch
 
 
 def _walk_scans(clouds: List[Dict], steps: Sequence[int]):
