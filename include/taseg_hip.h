@@ -1088,6 +1088,68 @@ int ts_project_fov(const float *points, int64_t n, const double *proj, int32_t i
 int ts_project_cam(const float *points, int64_t n, const double *cam, int32_t img_w, int32_t img_h, int32_t crop_top,
                    float row_offset, float *pix, uint8_t *keep, ts_stream_t stream);
 
+/* The camera side of the TIAF stage for a whole batch (csrc/tiaf_stage.hip; taseg_amd/data/tiaf.py).
+ *
+ * ts_tiaf_image_stack: the camera frames of one call straight into the planes the model reads
+ * (semantickitti_ms_mm.py:428-452 `get_fov_points`, the image part - `image[..., [2,1,0]] / 255.`, IMAGE_FLIP :436-440 `np.fliplr` of
+ * image and semantic map, the top-left crop with zero padding :443-452 - and semantickitti_voxel_ms_mm.py:245-248, the NCHW
+ * permutation of collate_batch).  images / semantic / img_h / img_w / flips are HOST arrays of n_frames <= TS_TIAF_IMAGE_FRAMES
+ * entries: device pointers to uint8 [h, w, 3] RGB images and (semantic may be NULL, so may an entry) float32 [h, w, 1] maps, their
+ * sizes, a flip byte each (flips NULL: none); they reach the kernel BY VALUE in its argument block - nothing is uploaded.  table
+ * [256] float32 on the device: i / 255 as the HOST rounds it (the device's division need not round as numpy's).  For frame t,
+ * r < crop_h, q < crop_w, c < 3:
+ *   out_image   [first + t][c][r][q] = r < min(crop_h, h) && q < min(crop_w, w) ? table[img[r][flip ? w - 1 - q : q][2 - c]] : 0
+ *   out_semantic[first + t][0][r][q] = the semantic map at the same source pixel, or 0
+ * so the flip acts on the full-width image BEFORE the crop: with w > crop_w a flipped frame shows the image's right part.
+ * out_image [n_total, 3, crop_h, crop_w], out_semantic [n_total, 1, crop_h, crop_w] (or NULL) float32, first + n_frames <= n_total.
+ * One launch; every output element of the frames is written exactly once (no fill pass); 16-byte stores and dword loads of the
+ * image when crop_w % 4 == 0 and the outputs are 16-byte aligned; any h, w, crop_h, crop_w, any image alignment otherwise.
+ *
+ * ts_tiaf_fov_cloud: the FOV cloud of a whole batch as one stable compaction.  points [n_points, 4] float32: the rows of every
+ * camera frame of every sample, sample-major, inside a sample NEWEST frame first (`raw_data_fov_ms.insert(0, ...)`, :369).  The
+ * call works on n_rows VIRTUAL rows: frame [n_rows] int32 ASCENDING names the record of every virtual row, and virtual row i of
+ * frame f reads point row records[f].src + (i - records[f].first) - frames of several samples (the votes of a TTA batch) may
+ * read the same point rows.  records [n_frames <= TS_TIAF_MAX_FRAMES] TsTiafFrame on the device (their samples ascending), aug
+ * [n_samples, TS_AUG_RECORD] doubles or NULL, lo [n_samples, 3] float32 - the minimum of the sample's AUGMENTED single-frame
+ * cloud - or NULL, 1 <= n_samples <= TS_TIAF_MAX_SAMPLES.  Per virtual row, in this order:
+ *   1  the projection and frustum test of ts_project_fov with the record's proj, img_w, img_h            (:416-426)
+ *   2  col = flip ? img_w - 1 - col : col                                                                (:441)
+ *   3  row < crop_h && col < crop_w, on the flipped column                                                (:454)
+ *   4  fov_dist > 0: sqrt(x * x + y * y) <= fov_dist on the un-fused point, float32 multiply, add, sqrt   (:365-367)
+ *   5  TS_TIAF_FUSE: the pose fuse of ts_fuse_scan with the record's pose0, pose                          (:368)
+ *   6  aug: the arithmetic of ts_stage_augment on xyz with the sample's record    (semantickitti_voxel_ms_mm.py:92-124)
+ *   7  lo: x >= lo[s][0] && y >= lo[s][1] && z >= lo[s][2], NaN on either side fails                      (... :132-133)
+ * A row whose sample or point row is out of range does not survive.  out [capacity, 6] float32 = (x, y, z, intensity, row +
+ * row_offset, col) of the survivors in input order, out_sample int64 / out_sample32 int32 their samples (the rows behind the
+ * survivors are not written); counts [n_samples] int64 the survivors of every sample - the caller's one host read.  capacity >=
+ * n_rows bounds every store.  Three launches (counts per block of 256 rows from wave ballots, a one-block scan, the scatter by
+ * rank - pass 3 recomputes the decision of pass 1 on the same bits); no atomics: the same bits every run. */
+#define TS_TIAF_IMAGE_FRAMES 16
+#define TS_TIAF_MAX_SAMPLES 64
+#define TS_TIAF_MAX_FRAMES 1024
+#define TS_TIAF_FLIP 1
+#define TS_TIAF_FUSE 2
+typedef struct TsTiafFrame {
+  double proj[12];         /* P2 . Tr of the frame's sequence, 3 x 4 row-major */
+  float pose0[16];         /* the pose of the sample's current frame, 4 x 4 row-major */
+  float pose[16];          /* the frame's own pose */
+  float row_offset;        /* crop_h * position of the frame in its sample's image stack */
+  float fov_dist;          /* <= 0: off */
+  int32_t sample;
+  int32_t img_w, img_h;
+  int32_t flags;           /* TS_TIAF_FLIP | TS_TIAF_FUSE */
+  int32_t first;           /* the frame's first virtual row */
+  int32_t src;             /* the point row it reads */
+} TsTiafFrame;
+int ts_tiaf_image_stack(const uint8_t *const *images, const float *const *semantic, const int32_t *img_h, const int32_t *img_w,
+                        const uint8_t *flips, int32_t n_frames, const float *table, int32_t crop_h, int32_t crop_w, int64_t first,
+                        int64_t n_total, float *out_image, float *out_semantic, ts_stream_t stream);
+size_t ts_tiaf_fov_cloud_workspace_bytes(int64_t n_rows, int32_t n_samples);
+int ts_tiaf_fov_cloud(const float *points, int64_t n_points, const int32_t *frame, int64_t n_rows, const TsTiafFrame *records,
+                      int32_t n_frames, const double *aug, const float *lo, int32_t n_samples, int32_t crop_h, int32_t crop_w,
+                      float *out, int64_t *out_sample, int32_t *out_sample32, int64_t capacity, int64_t *counts, void *ws,
+                      size_t ws_bytes, ts_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -181,6 +181,9 @@ SIGNATURES = {
     "ts_fuse_sweeps": (_i32, [_vp, _vp, _i64, _vp, _i32, _vp, _vp, _vp]),
     "ts_project_fov": (_i32, [_vp, _i64, _vp, _i32, _i32, _i32, _i32, _c.c_float, _vp, _vp, _vp]),
     "ts_project_cam": (_i32, [_vp, _i64, _vp, _i32, _i32, _i32, _c.c_float, _vp, _vp, _vp]),
+    "ts_tiaf_image_stack": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _i32, _i64, _i64, _vp, _vp, _vp]),
+    "ts_tiaf_fov_cloud_workspace_bytes": (_sz, [_i64, _i32]),
+    "ts_tiaf_fov_cloud": (_i32, [_vp, _i64, _vp, _i64, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _sz, _vp]),
     "ts_segment_min3": (_i32, [_vp, _i64, _i32, _vp, _i32, _vp, _vp]),
     "ts_stage_keep_flags": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp]),
     "ts_stage_augment": (_i32, [_vp, _i64, _i32, _vp, _vp, _i32, _vp, _vp]),

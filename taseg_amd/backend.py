@@ -1470,6 +1470,94 @@ def stage_layout_pair(cur, cur_lab, cur_start, hist, hist_lab, scan_idx, cls_a, 
     return (pts_a, lab_a, b_a, b32_a, is_cur), (pts_b, b_b, b32_b), counts
 
 
+TIAF_IMAGE_FRAMES, TIAF_MAX_SAMPLES, TIAF_MAX_FRAMES, TIAF_FRAME_BYTES = 16, 64, 1024, 256      # include/taseg_hip.h
+
+
+def tiaf_image_stack(images, semantic, flips, table, crop):
+    """csrc/tiaf_stage.hip: camera frames straight into the planes the model reads.  images: uint8 [h, w, 3] RGB device tensors;
+    semantic: as many float32 [h, w, 1] (or [h, w]) maps, or None; flips: a bool per frame or None; table: float32 [256] on the
+    device (i / 255 as the host rounds it); crop = (HEIGHT, WIDTH).  Returns (image [N, 3, H, W], semantic [N, 1, H, W] or None)
+    float32: BGR / 255, the flip before the top-left crop, zero padded - every element written once, one launch per 16 frames."""
+    import ctypes
+    n = len(images)
+    if n == 0:
+        raise ValueError("tiaf_image_stack: no frames")
+    if semantic is not None and len(semantic) != n or flips is not None and len(flips) != n:
+        raise ValueError("tiaf_image_stack: one semantic map and one flip per frame")
+    L.require_device(table, *images, *(semantic or ()))
+    table = _f32(table, "table")
+    if table.shape != (256,):
+        raise TypeError("table must be float32 [256]")
+    H, W = int(crop[0]), int(crop[1])
+    keep = []                                          # contiguous copies stay alive until the launches are issued
+    for im in images:
+        if im.dtype != torch.uint8 or im.ndim != 3 or im.shape[2] != 3:
+            raise TypeError("camera images must be uint8 [h, w, 3]")
+        keep.append(im.contiguous())
+    sems = None
+    if semantic is not None:
+        sems = []
+        for im, sm in zip(keep, semantic):
+            if sm.dtype != torch.float32 or sm.numel() != im.shape[0] * im.shape[1] or tuple(sm.shape[:2]) != tuple(im.shape[:2]):
+                raise TypeError("semantic maps must be float32 [h, w, 1] of their image's size")
+            sems.append(sm.contiguous())
+    dev = keep[0].device
+    out = torch.empty((n, 3, H, W), dtype=torch.float32, device=dev)
+    out_sem = None if sems is None else torch.empty((n, 1, H, W), dtype=torch.float32, device=dev)
+    lib, stream = L.load(), L.stream()
+    for at in range(0, n, TIAF_IMAGE_FRAMES):
+        k = min(TIAF_IMAGE_FRAMES, n - at)
+        ptrs = (ctypes.c_void_p * k)(*[t.data_ptr() for t in keep[at:at + k]])
+        sptr = None if sems is None else (ctypes.c_void_p * k)(*[t.data_ptr() for t in sems[at:at + k]])
+        hs = (ctypes.c_int32 * k)(*[t.shape[0] for t in keep[at:at + k]])
+        ws = (ctypes.c_int32 * k)(*[t.shape[1] for t in keep[at:at + k]])
+        fl = None if flips is None else (ctypes.c_uint8 * k)(*[1 if f else 0 for f in flips[at:at + k]])
+        L.check(lib.ts_tiaf_image_stack(ptrs, sptr, hs, ws, fl, k, L.ptr(table), H, W, at, n, L.ptr(out), L.ptr(out_sem), stream),
+                "ts_tiaf_image_stack")
+    return out, out_sem
+
+
+def tiaf_fov_cloud(points, frame, records, n_samples, crop, aug=None, lo=None):
+    """csrc/tiaf_stage.hip: the FOV cloud of a batch as one stable compaction in three launches.  points [n, 4] float32: the rows of
+    every camera frame of every sample, sample-major, newest frame first; frame [m] int32 ascending: the record of every VIRTUAL
+    row (m = n unless records share point rows); records: uint8 [F, 256] on the device, the TsTiafFrame table
+    (taseg_amd.data.tiaf.FRAME_DTYPE); aug: float64 [B, 8] on the device or None; lo: float32 [B, 3] or None; crop = (HEIGHT, WIDTH).
+    Returns (out [m, 6], out_sample [m] int64, out_sample32 [m] int32, counts [B] int64): the survivors in input order in the first
+    sum(counts) rows - the caller reads counts.  No host read here."""
+    L.require_device(points, frame, records, aug, lo)
+    points, frame = _f32(points, "points"), _i32(frame, "frame")
+    if points.ndim != 2 or points.shape[1] != 4:
+        raise TypeError("points must be a float32 [n, 4] tensor")
+    if records.dtype != torch.uint8 or records.ndim != 2 or records.shape[1] != TIAF_FRAME_BYTES:
+        raise TypeError("records must be the uint8 [F, 256] frame table")
+    records = records.contiguous()
+    nb, nf = int(n_samples), records.shape[0]
+    if not 1 <= nb <= TIAF_MAX_SAMPLES or not 1 <= nf <= TIAF_MAX_FRAMES:
+        raise ValueError("tiaf_fov_cloud: at most %d samples and %d frame records per call" % (TIAF_MAX_SAMPLES, TIAF_MAX_FRAMES))
+    if frame.ndim != 1:
+        raise ValueError("tiaf_fov_cloud: frame must be [m]")
+    if aug is not None:
+        if aug.dtype != torch.float64 or tuple(aug.shape) != (nb, 8):
+            raise TypeError("aug must be float64 [B, 8]")
+        aug = aug.contiguous()
+    if lo is not None:
+        lo = _f32(lo, "lo")
+        if tuple(lo.shape) != (nb, 3):
+            raise ValueError("tiaf_fov_cloud: lo must be [B, 3]")
+    dev, n, m = points.device, points.shape[0], frame.shape[0]
+    out = torch.empty((m, 6), dtype=torch.float32, device=dev)
+    out_sample = torch.empty(m, dtype=torch.int64, device=dev)
+    out_sample32 = torch.empty(m, dtype=torch.int32, device=dev)
+    counts = torch.empty(nb, dtype=torch.int64, device=dev)
+    lib = L.load()
+    ws_bytes = lib.ts_tiaf_fov_cloud_workspace_bytes(m, nb)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    L.check(lib.ts_tiaf_fov_cloud(L.ptr(points), n, L.ptr(frame), m, L.ptr(records), nf, L.ptr(aug), L.ptr(lo), nb, int(crop[0]),
+                                  int(crop[1]), L.ptr(out), L.ptr(out_sample), L.ptr(out_sample32), m, L.ptr(counts), L.ptr(ws),
+                                  ws_bytes, L.stream()), "ts_tiaf_fov_cloud")
+    return out, out_sample, out_sample32, counts
+
+
 def stage_split_voxels(coords4, index, inverse, row_sample, n_samples):
     """csrc/stage.hip: after sparse_quantize on a whole batch -> (vox [m, 4] int32 = coords4[index], offset [B] int32 cumulative
     voxel counts, inverse_local [n] int64 = voxel index inside the point's own sample)."""

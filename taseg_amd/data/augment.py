@@ -16,7 +16,8 @@ Split between host and device the way the work splits:
 
 LaserMix / PolarMix, which the recipe applies before this augmentation, are in data/mix.py.  The KD variant `aug_points_ms_gt`
 (seg_utils.py:168-239: the same draws and arithmetic on three clouds) is this kernel with the sample's record on the teacher's
-rows too (data/kd.py).  The image-side jitter and the TIAF variant (`aug_points_rgb_ms`) are not here.
+rows too (data/kd.py).  The TIAF variant `aug_points_rgb_ms` (seg_utils.py:241-313: the same draws and arithmetic on the current
+scan, the fused cloud and the FOV cloud) and the image flip are in data/tiaf.py; the image-side colour jitter is not built.
 """
 from dataclasses import dataclass
 from typing import List, Optional, Sequence, Tuple, Union
