@@ -953,7 +953,7 @@ int ts_stage_mix(const float *points, int64_t n_rows, int32_t point_stride, cons
  * sample is outside [0, n_samples) does not survive.  out [n, point_stride], out_labels [n], out_sample [n] int64, out_sample32
  * [n] int32: the surviving rows in input order (the rows behind them are not written); counts [n_samples] int64 the survivors of
  * every sample - the caller reads them once per batch, the output holds sum(counts) rows.  Three launches (counts per block of 256
- * rows from wave ballots, a one-block scan, the scatter by rank); no atomics: the same bits every run. */
+ * rows from wave ballots, the shared scan, the scatter by rank); no atomics: the same bits every run. */
 #define TS_CLAMP_MAX_SAMPLES 64
 size_t ts_stage_clamp_compact_workspace_bytes(int64_t n, int32_t n_samples);
 int ts_stage_clamp_compact(const float *points, int64_t n, int32_t point_stride, const int64_t *labels, const int32_t *sample,
@@ -1122,7 +1122,7 @@ int ts_project_cam(const float *points, int64_t n, const double *cam, int32_t im
  * A row whose sample or point row is out of range does not survive.  out [capacity, 6] float32 = (x, y, z, intensity, row +
  * row_offset, col) of the survivors in input order, out_sample int64 / out_sample32 int32 their samples (the rows behind the
  * survivors are not written); counts [n_samples] int64 the survivors of every sample - the caller's one host read.  capacity >=
- * n_rows bounds every store.  Three launches (counts per block of 256 rows from wave ballots, a one-block scan, the scatter by
+ * n_rows bounds every store.  Three launches (counts per block of 256 rows from wave ballots, the shared scan, the scatter by
  * rank - pass 3 recomputes the decision of pass 1 on the same bits); no atomics: the same bits every run. */
 #define TS_TIAF_IMAGE_FRAMES 16
 #define TS_TIAF_MAX_SAMPLES 64

@@ -34,7 +34,8 @@ def _newer(src, dst):
 
 
 def _deps():
-    return [os.path.join(HERE, "common.h"), os.path.join(ROOT, "include", "taseg_hip.h"), os.path.abspath(__file__)]
+    return [os.path.join(HERE, "common.h"), os.path.join(HERE, "compact.h"), os.path.join(HERE, "stage_rules.h"),
+            os.path.join(ROOT, "include", "taseg_hip.h"), os.path.abspath(__file__)]
 
 
 def build(force=False, verbose=True):

@@ -1,102 +1,91 @@
-// The clamp of the fused clouds as one stable compaction for a whole batch (taseg_amd/data/nuscenes.py, the mix path).
+// The clamp of the fused clouds as one stable compaction for a whole batch (taseg_amd/data/nuscenes.py, the mix path), and the
+// scan pass that every compaction of csrc/compact.h shares.
 // Reference (numpy, one sample at a time): R/pcseg/data/dataset/nuscenes/nuscenes_voxel_ms.py:122-125 and
 // semantickitti/semantickitti_voxel_ms.py:121-124 - `point_ms[(point_ms[:, :3] >= point[:, :3].min(0)).all(1)]`.
 //
-// After a mix the current scan is no prefix of the fused cloud, so EVERY fused row is compared with its sample's minimum.  Rows
-// are handled in blocks of 256, in the idiom of csrc/mix.hip:
-//   1  cc_count_kernel    one lane per row: the survivors per block (wave ballots) and per (block, sample)
-//   2  cc_scan_kernel     one block: the survivors of every sample, exclusive scan of the block counts
-//   3  cc_scatter_kernel  rank inside the block from wave ballots, destination = block offset + rank
-// Order is decided by counts and ranks alone - no atomics - so the rows keep their input order and the bits are the same every run.
-#include "common.h"
-
-#define CC_ROWS 256
-#define CC_WAVES (CC_ROWS / TS_WAVE)
+// After a mix the current scan is no prefix of the fused cloud, so EVERY fused row is compared with its sample's minimum: the
+// three passes of csrc/compact.h with the clamp of csrc/stage_rules.h as the row rule, one tally per sample.
+#include "compact.h"
+#include "stage_rules.h"
 
 namespace {
 
-// numpy's `>=` on float32: false for NaN on either side
 __device__ __forceinline__ bool cc_keeps(float x, float y, float z, const float *__restrict__ lo, int s, int n_samples) {
-  if (s < 0 || s >= n_samples) return false;
-  const float *q = lo + 3 * s;
-  return x >= q[0] && y >= q[1] && z >= q[2];
+  return s >= 0 && s < n_samples && sr_clamp_keeps(x, y, z, lo, s);
 }
 
-__global__ __launch_bounds__(CC_ROWS) void cc_count_kernel(const float *__restrict__ pts, int64_t n, int f,
+__global__ __launch_bounds__(CP_ROWS) void cc_count_kernel(const float *__restrict__ pts, int64_t n, int f,
                                                            const int *__restrict__ sample, const float *__restrict__ lo,
                                                            int n_samples, int *__restrict__ blk_cnt,
-                                                           int *__restrict__ blk_sample) {
-  __shared__ int wcnt[CC_WAVES];
-  __shared__ int scnt[CC_WAVES][TS_CLAMP_MAX_SAMPLES];
-  const int64_t i = (int64_t)blockIdx.x * CC_ROWS + threadIdx.x;
-  const int lane = threadIdx.x & (TS_WAVE - 1), w = threadIdx.x / TS_WAVE;
-  scnt[w][lane] = 0;                    // (TS_CLAMP_MAX_SAMPLES == TS_WAVE: every wave clears its own row)
+                                                           int *__restrict__ blk_tally) {
+  __shared__ int wcnt[CP_WAVES];
+  __shared__ int scnt[CP_WAVES][TS_WAVE];
+  const int64_t i = (int64_t)blockIdx.x * CP_ROWS + threadIdx.x;
+  cp_tally_clear<1>(scnt);
   __syncthreads();
   int s = -1;
-  bool keep = false;
+  bool keep[1] = {false};
   if (i < n) {
     const float *p = pts + i * f;
     s = sample[i];
-    keep = cc_keeps(p[0], p[1], p[2], lo, s, n_samples);
+    keep[0] = cc_keeps(p[0], p[1], p[2], lo, s, n_samples);
   }
-  unsigned long long rem = __ballot(keep);
-  if (lane == 0) wcnt[w] = __popcll(rem);
-  // `sample` ascends: a wave holds one sample, or a few at a boundary - one round per distinct sample (rem is wave-uniform)
-  while (rem) {
-    const int s0 = __shfl(s, __ffsll((long long)rem) - 1);
-    const unsigned long long m = __ballot(keep && s == s0);
-    if (lane == 0) scnt[w][s0] += __popcll(m);
-    rem &= ~m;
-  }
+  cp_ballot(keep[0], wcnt);
+  cp_tally_wave<1>(s, keep, scnt);
   __syncthreads();
-  if (threadIdx.x == 0) {
-    int c = 0;
-    for (int v = 0; v < CC_WAVES; ++v) c += wcnt[v];
-    blk_cnt[blockIdx.x] = c;
-  }
-  if (threadIdx.x < n_samples) {
-    int c = 0;
-    for (int v = 0; v < CC_WAVES; ++v) c += scnt[v][threadIdx.x];
-    blk_sample[(int64_t)blockIdx.x * n_samples + threadIdx.x] = c;
-  }
+  if (threadIdx.x == 0) blk_cnt[blockIdx.x] = cp_block_sum(wcnt);
+  cp_tally_store<1>(scnt, n_samples, blk_tally);
 }
 
-__global__ __launch_bounds__(256) void cc_scan_kernel(int n_blocks, int n_samples, const int *__restrict__ blk_cnt,
-                                                      const int *__restrict__ blk_sample, int *__restrict__ offs,
+// blocks 0 .. n_clouds - 1: offs [n_clouds][n_blocks] = exclusive scans of blk_cnt, one block per cloud - every thread sums a
+// contiguous chunk, the 256 chunk sums are scanned in LDS, every thread writes its chunk's running sums (a single wave walking
+// 40 000 block counts 64 at a time waits for one load after the other);  block n_clouds + g: wave w sums row j = 4 g + w of
+// blk_tally [n_tallies][n_blocks] into counts[j], the blocks lane-strided
+__global__ __launch_bounds__(256) void cp_scan_kernel(int n_blocks, int n_clouds, int n_tallies, const int *__restrict__ blk_cnt,
+                                                      const int *__restrict__ blk_tally, int *__restrict__ offs,
                                                       int64_t *__restrict__ counts) {
+  __shared__ int part[256];
   const int lane = threadIdx.x & (TS_WAVE - 1), w = threadIdx.x / TS_WAVE;
-  // the survivors of every sample: one wave per sample, the blocks lane-strided (integer sums: any order gives the same value)
-  for (int s = w; s < n_samples; s += 256 / TS_WAVE) {
-    int c = 0;                           // (n < 2^30 rows in all)
-    for (int b = lane; b < n_blocks; b += TS_WAVE) c += blk_sample[(int64_t)b * n_samples + s];
+  if ((int)blockIdx.x >= n_clouds) {
+    const int j = ((int)blockIdx.x - n_clouds) * (256 / TS_WAVE) + w;
+    if (j >= n_tallies) return;
+    const int *row = blk_tally + (int64_t)j * n_blocks;
+    int c = 0;                           // (n < 2^30 rows in all; integer sums: any order gives the same value)
+    for (int b = lane; b < n_blocks; b += TS_WAVE) c += row[b];
     for (int d = TS_WAVE / 2; d > 0; d >>= 1) c += __shfl_xor(c, d);
-    if (lane == 0) counts[s] = (int64_t)c;
+    if (lane == 0) counts[j] = (int64_t)c;
+    return;
   }
-  if (w != 0) return;
-  int running = 0;
-  for (int c = 0; c < n_blocks; c += TS_WAVE) {
-    const int i = c + lane;
-    const int v = i < n_blocks ? blk_cnt[i] : 0;
-    int incl = v;
-    for (int d = 1; d < TS_WAVE; d <<= 1) {
-      const int t = __shfl_up(incl, d);
-      if (lane >= d) incl += t;
-    }
-    if (i < n_blocks) offs[i] = running + incl - v;
-    running += __shfl(incl, TS_WAVE - 1);
+  const int *cnt = blk_cnt + (int64_t)blockIdx.x * n_blocks;
+  int *out = offs + (int64_t)blockIdx.x * n_blocks;
+  const int chunk = (n_blocks + 255) / 256;
+  const int first = min((int)threadIdx.x * chunk, n_blocks), last = min(first + chunk, n_blocks);
+  int sum = 0;
+  for (int i = first; i < last; ++i) sum += cnt[i];
+  part[threadIdx.x] = sum;
+  __syncthreads();
+  for (int d = 1; d < 256; d <<= 1) {
+    const int t = (int)threadIdx.x >= d ? part[threadIdx.x - d] : 0;
+    __syncthreads();
+    part[threadIdx.x] += t;
+    __syncthreads();
+  }
+  int running = part[threadIdx.x] - sum;      // the block counts before this thread's chunk
+  for (int i = first; i < last; ++i) {
+    out[i] = running;
+    running += cnt[i];
   }
 }
 
 template <bool VEC4>
-__global__ __launch_bounds__(CC_ROWS) void cc_scatter_kernel(const float *__restrict__ pts, int64_t n, int f,
+__global__ __launch_bounds__(CP_ROWS) void cc_scatter_kernel(const float *__restrict__ pts, int64_t n, int f,
                                                              const int64_t *__restrict__ lab, const int *__restrict__ sample,
                                                              const float *__restrict__ lo, int n_samples,
                                                              const int *__restrict__ offs, float *__restrict__ out,
                                                              int64_t *__restrict__ out_lab, int64_t *__restrict__ out_sample,
                                                              int *__restrict__ out_sample32) {
-  __shared__ int wcnt[CC_WAVES];
-  const int64_t i = (int64_t)blockIdx.x * CC_ROWS + threadIdx.x;
-  const int lane = threadIdx.x & (TS_WAVE - 1), w = threadIdx.x / TS_WAVE;
+  __shared__ int wcnt[CP_WAVES];
+  const int64_t i = (int64_t)blockIdx.x * CP_ROWS + threadIdx.x;
   int s = -1;
   bool keep = false;
   float4 p = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -110,12 +99,10 @@ __global__ __launch_bounds__(CC_ROWS) void cc_scatter_kernel(const float *__rest
     }
     keep = cc_keeps(p.x, p.y, p.z, lo, s, n_samples);       // the comparison of pass 1 on the same bits
   }
-  const unsigned long long m = __ballot(keep);
-  if (lane == 0) wcnt[w] = __popcll(m);
+  const CpBallot b = cp_ballot(keep, wcnt);
   __syncthreads();
   if (!keep) return;
-  int64_t dst = (int64_t)offs[blockIdx.x] + __popcll(m & ((1ull << lane) - 1ull));
-  for (int v = 0; v < w; ++v) dst += wcnt[v];
+  const int64_t dst = offs[blockIdx.x] + cp_rank(b, wcnt);
   if (dst >= n) return;                                     // (cannot happen: survivors <= rows; bounds every store)
   if (VEC4) {
     reinterpret_cast<float4 *>(out)[dst] = p;
@@ -132,57 +119,43 @@ __global__ __launch_bounds__(CC_ROWS) void cc_scatter_kernel(const float *__rest
   out_sample32[dst] = s;
 }
 
-struct CcWorkspace {
-  int *blk_cnt, *offs, *blk_sample;
-  size_t bytes;
-};
-
-CcWorkspace cc_carve(void *ws, int64_t n_blocks, int64_t n_samples) {
-  CcWorkspace c;
-  size_t at = 0;
-  char *base = (char *)ws;
-  c.blk_cnt = (int *)(base + at);
-  at += ts_align_up((size_t)n_blocks * sizeof(int), 256);
-  c.offs = (int *)(base + at);
-  at += ts_align_up((size_t)n_blocks * sizeof(int), 256);
-  c.blk_sample = (int *)(base + at);
-  at += ts_align_up((size_t)n_blocks * n_samples * sizeof(int), 256);
-  c.bytes = std::max<size_t>(at, 256);
-  return c;
-}
-
 }  // namespace
 
+void ts_compact_scan(const CpWorkspace &c, int n_blocks, int n_clouds, int n_tallies, int64_t *counts, hipStream_t stream) {
+  cp_scan_kernel<<<n_clouds + (int)ts_cdiv(n_tallies, 256 / TS_WAVE), 256, 0, stream>>>(n_blocks, n_clouds, n_tallies, c.blk_cnt,
+                                                                                        c.blk_tally, c.offs, counts);
+}
+
 extern "C" size_t ts_stage_clamp_compact_workspace_bytes(int64_t n, int32_t n_samples) {
-  return cc_carve(nullptr, ts_cdiv(std::max<int64_t>(n, 0), CC_ROWS), std::max(n_samples, 0)).bytes;
+  return cp_carve(nullptr, ts_cdiv(std::max<int64_t>(n, 0), CP_ROWS), 1, std::max(n_samples, 0)).bytes;
 }
 
 extern "C" int ts_stage_clamp_compact(const float *points, int64_t n, int32_t point_stride, const int64_t *labels,
                                       const int32_t *sample, const float *lo, int32_t n_samples, float *out, int64_t *out_labels,
                                       int64_t *out_sample, int32_t *out_sample32, int64_t *counts, void *ws, size_t ws_bytes,
                                       ts_stream_t stream) {
-  static_assert(TS_CLAMP_MAX_SAMPLES == TS_WAVE, "cc_count_kernel clears one LDS row per wave");
+  static_assert(TS_CLAMP_MAX_SAMPLES == TS_WAVE, "cc_count_kernel keeps one LDS counter per (wave, sample)");
   TS_REQUIRE(n >= 0 && n < (int64_t)1 << 30 && point_stride >= 3 && n_samples >= 1 && n_samples <= TS_CLAMP_MAX_SAMPLES,
              TS_ERR_INVALID_ARGUMENT, "ts_stage_clamp_compact: bad sizes");
   TS_REQUIRE(lo && counts && ws && ((uintptr_t)ws & 3) == 0, TS_ERR_INVALID_ARGUMENT, "ts_stage_clamp_compact: null pointer");
   TS_REQUIRE(n == 0 || (points && labels && sample && out && out_labels && out_sample && out_sample32), TS_ERR_INVALID_ARGUMENT,
              "ts_stage_clamp_compact: null pointer");
-  const int64_t n_blocks = ts_cdiv(n, CC_ROWS);
-  const CcWorkspace c = cc_carve(ws, n_blocks, n_samples);
+  const int64_t n_blocks = ts_cdiv(n, CP_ROWS);
+  const CpWorkspace c = cp_carve(ws, n_blocks, 1, n_samples);
   TS_REQUIRE(ws_bytes >= c.bytes, TS_ERR_INVALID_ARGUMENT, "ts_stage_clamp_compact: workspace too small");
   hipStream_t st = (hipStream_t)stream;
   if (n_blocks > 0) {
-    cc_count_kernel<<<(int)n_blocks, CC_ROWS, 0, st>>>(points, n, point_stride, sample, lo, n_samples, c.blk_cnt, c.blk_sample);
+    cc_count_kernel<<<(int)n_blocks, CP_ROWS, 0, st>>>(points, n, point_stride, sample, lo, n_samples, c.blk_cnt, c.blk_tally);
     TS_CHECK_LAUNCH("ts_stage_clamp_compact (count)");
   }
-  cc_scan_kernel<<<1, 256, 0, st>>>((int)n_blocks, n_samples, c.blk_cnt, c.blk_sample, c.offs, counts);
+  ts_compact_scan(c, (int)n_blocks, 1, n_samples, counts, st);
   TS_CHECK_LAUNCH("ts_stage_clamp_compact (scan)");
   if (n_blocks > 0) {
     if (point_stride == 4 && ((((uintptr_t)points) | ((uintptr_t)out)) & 15) == 0) {
-      cc_scatter_kernel<true><<<(int)n_blocks, CC_ROWS, 0, st>>>(points, n, point_stride, labels, sample, lo, n_samples, c.offs, out,
+      cc_scatter_kernel<true><<<(int)n_blocks, CP_ROWS, 0, st>>>(points, n, point_stride, labels, sample, lo, n_samples, c.offs, out,
                                                                  out_labels, out_sample, out_sample32);
     } else {
-      cc_scatter_kernel<false><<<(int)n_blocks, CC_ROWS, 0, st>>>(points, n, point_stride, labels, sample, lo, n_samples, c.offs,
+      cc_scatter_kernel<false><<<(int)n_blocks, CP_ROWS, 0, st>>>(points, n, point_stride, labels, sample, lo, n_samples, c.offs,
                                                                   out, out_labels, out_sample, out_sample32);
     }
     TS_CHECK_LAUNCH("ts_stage_clamp_compact (scatter)");

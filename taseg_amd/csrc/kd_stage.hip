@@ -5,21 +5,15 @@
 // semantickitti_voxel_ms_kd.py:125-132 (both clouds clamped to the current scan's minimum; :88 `num_points_ms_gt` is taken BEFORE
 // the clamp and never updated).
 //
-// Every history row is read once and written to up to two destinations.  Rows are handled in blocks of 256, in the idiom of
-// csrc/compact.hip:
-//   1  lp_count_kernel    one lane per history row: rows kept for A and for B per block (wave ballots), and per (block, sample)
-//                         kept A / kept B / B's step rule before the clamp
-//   2  lp_scan_kernel     blocks 0 and 1: exclusive scan of the block counts of A / of B;  the blocks behind them: one wave per (sample,
-//                         count), the three counts of every sample summed over the blocks (stored count-major: the lanes of a
-//                         wave read neighbouring ints)
-//   3  lp_scatter_kernel  history blocks: rank inside the block from wave ballots, destination = current rows of the samples up to
-//                         the row's own + block offset + rank;  current blocks: destination = index + kept history of the samples
-//                         before the row's own (a running sum of the <= 64 sample counts, in LDS), in both clouds
-// Order is decided by counts and ranks alone - no atomics - so the rows keep their input order and the bits are the same every run.
-#include "common.h"
+// Every history row is read once and written to up to two destinations: the three passes of csrc/compact.h over TWO clouds, with
+// three tallies per sample (kept A / kept B / B's step rule before the clamp).  Its own:
+//   lp_flags           the row rule: both class-step lookups and the clamp (csrc/stage_rules.h)
+//   lp_scatter_kernel  history blocks: destination = current rows of the samples up to the row's own + block offset + rank;  current
+//                      blocks: destination = index + kept history of the samples before the row's own (a running sum of the <= 64
+//                      sample counts, in LDS), in both clouds
+#include "compact.h"
+#include "stage_rules.h"
 
-#define LP_ROWS 256
-#define LP_WAVES (LP_ROWS / TS_WAVE)
 #define LP_F 5                           // x, y, z, intensity, time flag
 
 namespace {
@@ -32,12 +26,6 @@ struct LpRule {
   int n_scans, cols, neg_col, n_samples;
 };
 
-// table[scan][class], the class-step rule of stage_keep_kernel: a negative class reads column neg_col
-__device__ __forceinline__ bool lp_step(const unsigned char *__restrict__ table, int s, int64_t c, int cols, int neg_col) {
-  if (c < 0) c = neg_col;
-  return c >= 0 && c < cols && table[(int64_t)s * cols + c] != 0;
-}
-
 // bit 0: kept for A, bit 1: kept for B, bit 2: B's step rule alone (before the clamp); *sample = the row's sample or -1
 __device__ __forceinline__ int lp_flags(const LpRule &r, int64_t i, float x, float y, float z, int *sample) {
   const int s = min(max(r.scan[i], 0), r.n_scans - 1);
@@ -45,97 +33,31 @@ __device__ __forceinline__ int lp_flags(const LpRule &r, int64_t i, float x, flo
   *sample = -1;
   if (b < 0 || b >= r.n_samples) return 0;
   *sample = (int)b;
-  const bool sa = lp_step(r.table_a, s, r.cls_a[i], r.cols, r.neg_col);
-  const bool sb = lp_step(r.table_b, s, r.cls_b[i], r.cols, r.neg_col);
-  const float *q = r.lo + 3 * b;
-  const bool in = x >= q[0] && y >= q[1] && z >= q[2];        // numpy's `>=` on float32: false for NaN on either side
+  const bool sa = sr_class_step(r.table_a, s, r.cls_a[i], r.cols, r.neg_col);
+  const bool sb = sr_class_step(r.table_b, s, r.cls_b[i], r.cols, r.neg_col);
+  const bool in = sr_clamp_keeps(x, y, z, r.lo, b);
   return (sa && in ? 1 : 0) | (sb && in ? 2 : 0) | (sb ? 4 : 0);
 }
 
-__global__ __launch_bounds__(LP_ROWS) void lp_count_kernel(const float *__restrict__ hist, int64_t n_hist, LpRule r,
-                                                           int *__restrict__ blk_cnt, int *__restrict__ blk_sample) {
-  __shared__ int wcnt[LP_WAVES][2];
-  __shared__ int scnt[LP_WAVES][TS_STAGE_PAIR_MAX_SAMPLES][3];
-  const int64_t i = (int64_t)blockIdx.x * LP_ROWS + threadIdx.x;
-  const int lane = threadIdx.x & (TS_WAVE - 1), w = threadIdx.x / TS_WAVE;
-  for (int k = 0; k < 3; ++k) scnt[w][lane][k] = 0;  // (TS_STAGE_PAIR_MAX_SAMPLES == TS_WAVE: every wave clears its own rows)
+__global__ __launch_bounds__(CP_ROWS) void lp_count_kernel(const float *__restrict__ hist, int64_t n_hist, LpRule r,
+                                                           int *__restrict__ blk_cnt, int *__restrict__ blk_tally) {
+  __shared__ int wcnt[2][CP_WAVES];
+  __shared__ int scnt[CP_WAVES][3 * TS_WAVE];
+  const int64_t i = (int64_t)blockIdx.x * CP_ROWS + threadIdx.x;
+  cp_tally_clear<3>(scnt);
   __syncthreads();
   int s = -1, fl = 0;
   if (i < n_hist) {
     const float *p = hist + i * 4;
     fl = lp_flags(r, i, p[0], p[1], p[2], &s);
   }
-  const unsigned long long ma = __ballot(fl & 1), mb = __ballot(fl & 2);
-  if (lane == 0) {
-    wcnt[w][0] = __popcll(ma);
-    wcnt[w][1] = __popcll(mb);
-  }
-  // the samples ascend: a wave holds one sample, or a few at a boundary - one round per distinct sample (rem is wave-uniform)
-  unsigned long long rem = __ballot(fl != 0);
-  while (rem) {
-    const int s0 = __shfl(s, __ffsll((long long)rem) - 1);
-    const bool mine = fl != 0 && s == s0;
-    const unsigned long long m = __ballot(mine);
-    const unsigned long long a = __ballot(mine && (fl & 1)), b = __ballot(mine && (fl & 2)), c = __ballot(mine && (fl & 4));
-    if (lane == 0) {
-      scnt[w][s0][0] += __popcll(a);
-      scnt[w][s0][1] += __popcll(b);
-      scnt[w][s0][2] += __popcll(c);
-    }
-    rem &= ~m;
-  }
+  const bool hit[3] = {(fl & 1) != 0, (fl & 2) != 0, (fl & 4) != 0};
+  cp_ballot(hit[0], wcnt[0]);
+  cp_ballot(hit[1], wcnt[1]);
+  cp_tally_wave<3>(s, hit, scnt);
   __syncthreads();
-  if (threadIdx.x < 2) {
-    int c = 0;
-    for (int v = 0; v < LP_WAVES; ++v) c += wcnt[v][threadIdx.x];
-    blk_cnt[(int64_t)threadIdx.x * gridDim.x + blockIdx.x] = c;
-  }
-  if (threadIdx.x < 3 * r.n_samples) {
-    const int sm = threadIdx.x / 3, k = threadIdx.x % 3;
-    int c = 0;
-    for (int v = 0; v < LP_WAVES; ++v) c += scnt[v][sm][k];
-    blk_sample[(int64_t)threadIdx.x * gridDim.x + blockIdx.x] = c;          // [3 * n_samples][n_blocks]: lp_scan_kernel reads along a row
-  }
-}
-
-// blocks 0 and 1: offs [2][n_blocks] = exclusive scans of blk_cnt, block 0 cloud A's and block 1 cloud B's - every thread sums a
-// contiguous chunk, the 256 chunk sums are scanned in LDS, every thread writes its chunk's running sums (a single wave walking
-// 40 000 block counts 64 at a time waits for one load after the other);  block 2 + g: wave w sums row j = 4 g + w of blk_sample
-// [3 * n_samples][n_blocks] into counts[j] (j = 3 * sample + count), the blocks lane-strided
-__global__ __launch_bounds__(256) void lp_scan_kernel(int n_blocks, int n_samples, const int *__restrict__ blk_cnt,
-                                                      const int *__restrict__ blk_sample, int *__restrict__ offs,
-                                                      int64_t *__restrict__ counts) {
-  __shared__ int part[256];
-  const int lane = threadIdx.x & (TS_WAVE - 1), w = threadIdx.x / TS_WAVE;
-  if (blockIdx.x >= 2) {
-    const int j = ((int)blockIdx.x - 2) * (256 / TS_WAVE) + w;
-    if (j >= 3 * n_samples) return;
-    const int *row = blk_sample + (int64_t)j * n_blocks;
-    int c = 0;                           // (n < 2^30 rows in all; integer sums: any order gives the same value)
-    for (int b = lane; b < n_blocks; b += TS_WAVE) c += row[b];
-    for (int d = TS_WAVE / 2; d > 0; d >>= 1) c += __shfl_xor(c, d);
-    if (lane == 0) counts[j] = (int64_t)c;
-    return;
-  }
-  const int *cnt = blk_cnt + (int64_t)blockIdx.x * n_blocks;
-  int *out = offs + (int64_t)blockIdx.x * n_blocks;
-  const int chunk = (n_blocks + 255) / 256;
-  const int first = min((int)threadIdx.x * chunk, n_blocks), last = min(first + chunk, n_blocks);
-  int sum = 0;
-  for (int i = first; i < last; ++i) sum += cnt[i];
-  part[threadIdx.x] = sum;
-  __syncthreads();
-  for (int d = 1; d < 256; d <<= 1) {
-    const int t = (int)threadIdx.x >= d ? part[threadIdx.x - d] : 0;
-    __syncthreads();
-    part[threadIdx.x] += t;
-    __syncthreads();
-  }
-  int running = part[threadIdx.x] - sum;      // the block counts before this thread's chunk
-  for (int i = first; i < last; ++i) {
-    out[i] = running;
-    running += cnt[i];
-  }
+  if (threadIdx.x < 2) blk_cnt[(int64_t)threadIdx.x * gridDim.x + blockIdx.x] = cp_block_sum(wcnt[threadIdx.x]);
+  cp_tally_store<3>(scnt, 3 * r.n_samples, blk_tally);
 }
 
 struct LpOut {
@@ -156,20 +78,19 @@ __device__ __forceinline__ void lp_store_row(float *__restrict__ pts, int64_t ds
 }
 
 template <bool VEC4>
-__global__ __launch_bounds__(LP_ROWS) void lp_scatter_kernel(const float *__restrict__ cur, int64_t n_cur, int cur_stride,
+__global__ __launch_bounds__(CP_ROWS) void lp_scatter_kernel(const float *__restrict__ cur, int64_t n_cur, int cur_stride,
                                                              const int64_t *__restrict__ cur_lab,
                                                              const int64_t *__restrict__ cur_start,
                                                              const float *__restrict__ hist, int64_t n_hist,
                                                              const int64_t *__restrict__ hist_lab, LpRule r, int n_hist_blocks,
                                                              const int *__restrict__ offs, const int64_t *__restrict__ counts,
                                                              LpOut o) {
-  __shared__ int wcnt[LP_WAVES][2];
+  __shared__ int wcnt[2][CP_WAVES];
   __shared__ int64_t cs[TS_STAGE_PAIR_MAX_SAMPLES + 1];
   __shared__ int64_t kstart[2][TS_STAGE_PAIR_MAX_SAMPLES];   // kept history rows of the samples before s, cloud A and cloud B
-  const int lane = threadIdx.x & (TS_WAVE - 1), w = threadIdx.x / TS_WAVE;
   if (threadIdx.x <= r.n_samples) cs[threadIdx.x] = cur_start[threadIdx.x];
   if ((int)blockIdx.x < n_hist_blocks) {
-    const int64_t i = (int64_t)blockIdx.x * LP_ROWS + threadIdx.x;
+    const int64_t i = (int64_t)blockIdx.x * CP_ROWS + threadIdx.x;
     int s = -1, fl = 0;
     float4 p = make_float4(0.f, 0.f, 0.f, 0.f);
     if (i < n_hist) {
@@ -181,18 +102,12 @@ __global__ __launch_bounds__(LP_ROWS) void lp_scatter_kernel(const float *__rest
       }
       fl = lp_flags(r, i, p.x, p.y, p.z, &s);               // the decisions of pass 1 on the same bits
     }
-    const unsigned long long ma = __ballot(fl & 1), mb = __ballot(fl & 2);
-    if (lane == 0) {
-      wcnt[w][0] = __popcll(ma);
-      wcnt[w][1] = __popcll(mb);
-    }
+    const CpBallot ba = cp_ballot(fl & 1, wcnt[0]), bb = cp_ballot(fl & 2, wcnt[1]);
     __syncthreads();
     if (!(fl & 3)) return;
-    const unsigned long long below = (1ull << lane) - 1ull;
     const int64_t head = cs[s + 1];                         // the current rows of the samples up to the row's own
     if (fl & 1) {
-      int64_t dst = head + offs[blockIdx.x] + __popcll(ma & below);
-      for (int v = 0; v < w; ++v) dst += wcnt[v][0];
+      const int64_t dst = head + offs[blockIdx.x] + cp_rank(ba, wcnt[0]);
       if (dst >= 0 && dst < o.capacity) {                   // (cannot fail: kept rows <= rows; bounds every store)
         lp_store_row(o.pts_a, dst, p, 0.f);
         o.lab_a[dst] = hist_lab[i];
@@ -202,8 +117,7 @@ __global__ __launch_bounds__(LP_ROWS) void lp_scatter_kernel(const float *__rest
       }
     }
     if (fl & 2) {
-      int64_t dst = head + offs[(int64_t)n_hist_blocks + blockIdx.x] + __popcll(mb & below);
-      for (int v = 0; v < w; ++v) dst += wcnt[v][1];
+      const int64_t dst = head + offs[(int64_t)n_hist_blocks + blockIdx.x] + cp_rank(bb, wcnt[1]);
       if (dst >= 0 && dst < o.capacity) {
         lp_store_row(o.pts_b, dst, p, 0.f);
         o.sample_b[dst] = s;
@@ -220,7 +134,7 @@ __global__ __launch_bounds__(LP_ROWS) void lp_scatter_kernel(const float *__rest
     }
   }
   __syncthreads();
-  const int64_t i = (int64_t)(blockIdx.x - n_hist_blocks) * LP_ROWS + threadIdx.x;
+  const int64_t i = (int64_t)(blockIdx.x - n_hist_blocks) * CP_ROWS + threadIdx.x;
   if (i >= n_cur) return;
   // the row's sample: the last s with cur_start[s] <= i (an empty sample shares its start with the next one)
   int lo = 0, hi = r.n_samples;
@@ -246,29 +160,10 @@ __global__ __launch_bounds__(LP_ROWS) void lp_scatter_kernel(const float *__rest
   }
 }
 
-struct LpWorkspace {
-  int *blk_cnt, *offs, *blk_sample;
-  size_t bytes;
-};
-
-LpWorkspace lp_carve(void *ws, int64_t n_blocks, int64_t n_samples) {
-  LpWorkspace c;
-  size_t at = 0;
-  char *base = (char *)ws;
-  c.blk_cnt = (int *)(base + at);
-  at += ts_align_up((size_t)2 * n_blocks * sizeof(int), 256);
-  c.offs = (int *)(base + at);
-  at += ts_align_up((size_t)2 * n_blocks * sizeof(int), 256);
-  c.blk_sample = (int *)(base + at);
-  at += ts_align_up((size_t)n_blocks * 3 * n_samples * sizeof(int), 256);
-  c.bytes = std::max<size_t>(at, 256);
-  return c;
-}
-
 }  // namespace
 
 extern "C" size_t ts_stage_layout_pair_workspace_bytes(int64_t n_hist, int32_t n_samples) {
-  return lp_carve(nullptr, ts_cdiv(std::max<int64_t>(n_hist, 0), LP_ROWS), std::max(n_samples, 0)).bytes;
+  return cp_carve(nullptr, ts_cdiv(std::max<int64_t>(n_hist, 0), CP_ROWS), 2, 3 * (int64_t)std::max(n_samples, 0)).bytes;
 }
 
 extern "C" int ts_stage_layout_pair(const float *cur, int64_t n_cur, int32_t cur_stride, const int64_t *cur_labels,
@@ -279,8 +174,8 @@ extern "C" int ts_stage_layout_pair(const float *cur, int64_t n_cur, int32_t cur
                                     int64_t *out_labels_a, int64_t *out_sample_a, int32_t *out_sample32_a, uint8_t *out_is_cur_a,
                                     float *out_b, int64_t *out_sample_b, int32_t *out_sample32_b, int64_t capacity,
                                     int64_t *counts, void *ws, size_t ws_bytes, ts_stream_t stream) {
-  static_assert(TS_STAGE_PAIR_MAX_SAMPLES == TS_WAVE, "lp_count_kernel clears one LDS row per lane");
-  static_assert(3 * TS_STAGE_PAIR_MAX_SAMPLES <= LP_ROWS, "lp_count_kernel writes one (sample, column) per lane");
+  static_assert(TS_STAGE_PAIR_MAX_SAMPLES == TS_WAVE, "lp_count_kernel keeps three LDS counters per (wave, sample)");
+  static_assert(3 * TS_STAGE_PAIR_MAX_SAMPLES <= CP_ROWS, "lp_count_kernel writes one tally per lane");
   TS_REQUIRE(n_cur >= 0 && n_hist >= 0 && n_cur + n_hist < (int64_t)1 << 30 && cur_stride >= 4 && n_scans >= 1 &&
                  table_cols >= 1 && n_samples >= 1 && n_samples <= TS_STAGE_PAIR_MAX_SAMPLES && capacity >= n_cur + n_hist,
              TS_ERR_INVALID_ARGUMENT, "ts_stage_layout_pair: bad sizes");
@@ -292,26 +187,25 @@ extern "C" int ts_stage_layout_pair(const float *cur, int64_t n_cur, int32_t cur
   TS_REQUIRE(n_cur == 0 || (cur && cur_labels), TS_ERR_INVALID_ARGUMENT, "ts_stage_layout_pair: null pointer");
   TS_REQUIRE(n_hist == 0 || (hist && hist_labels && scan_idx && cls_a && cls_b && table_a && table_b && sample_of_scan),
              TS_ERR_INVALID_ARGUMENT, "ts_stage_layout_pair: null pointer");
-  const int64_t n_blocks = ts_cdiv(n_hist, LP_ROWS), n_cur_blocks = ts_cdiv(n_cur, LP_ROWS);
-  const LpWorkspace c = lp_carve(ws, n_blocks, n_samples);
+  const int64_t n_blocks = ts_cdiv(n_hist, CP_ROWS), n_cur_blocks = ts_cdiv(n_cur, CP_ROWS);
+  const CpWorkspace c = cp_carve(ws, n_blocks, 2, 3 * n_samples);
   TS_REQUIRE(ws_bytes >= c.bytes, TS_ERR_INVALID_ARGUMENT, "ts_stage_layout_pair: workspace too small");
   hipStream_t st = (hipStream_t)stream;
   const LpRule r = {table_a, table_b, cls_a, cls_b, sample_of_scan, scan_idx, lo, n_scans, table_cols, neg_col, n_samples};
   if (n_blocks > 0) {
-    lp_count_kernel<<<(int)n_blocks, LP_ROWS, 0, st>>>(hist, n_hist, r, c.blk_cnt, c.blk_sample);
+    lp_count_kernel<<<(int)n_blocks, CP_ROWS, 0, st>>>(hist, n_hist, r, c.blk_cnt, c.blk_tally);
     TS_CHECK_LAUNCH("ts_stage_layout_pair (count)");
   }
-  lp_scan_kernel<<<2 + (int)ts_cdiv(3 * n_samples, 256 / TS_WAVE), 256, 0, st>>>((int)n_blocks, n_samples, c.blk_cnt, c.blk_sample,
-                                                                                 c.offs, counts);
+  ts_compact_scan(c, (int)n_blocks, 2, 3 * n_samples, counts, st);
   TS_CHECK_LAUNCH("ts_stage_layout_pair (scan)");
   if (n_blocks + n_cur_blocks > 0) {
     const LpOut o = {out_a, out_b, out_labels_a, out_sample_a, out_sample_b, out_sample32_a, out_sample32_b, out_is_cur_a, capacity};
     const int grid = (int)(n_blocks + n_cur_blocks);
     if ((((uintptr_t)hist) & 15) == 0) {
-      lp_scatter_kernel<true><<<grid, LP_ROWS, 0, st>>>(cur, n_cur, cur_stride, cur_labels, cur_start, hist, n_hist, hist_labels, r,
+      lp_scatter_kernel<true><<<grid, CP_ROWS, 0, st>>>(cur, n_cur, cur_stride, cur_labels, cur_start, hist, n_hist, hist_labels, r,
                                                         (int)n_blocks, c.offs, counts, o);
     } else {
-      lp_scatter_kernel<false><<<grid, LP_ROWS, 0, st>>>(cur, n_cur, cur_stride, cur_labels, cur_start, hist, n_hist, hist_labels,
+      lp_scatter_kernel<false><<<grid, CP_ROWS, 0, st>>>(cur, n_cur, cur_stride, cur_labels, cur_start, hist, n_hist, hist_labels,
                                                          r, (int)n_blocks, c.offs, counts, o);
     }
     TS_CHECK_LAUNCH("ts_stage_layout_pair (scatter)");

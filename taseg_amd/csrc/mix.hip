@@ -5,18 +5,20 @@
 // PolarMix_nuscenes.py / LaserMix_nuscenes.py.
 //
 // A mix is a stable multi-segment partition of the rows of two clouds plus two rotated copies of one block of segments.  JOBS (one
-// per sample, any number per call) are concatenated job-major, cloud 1 before cloud 2; every job owns whole 256-row blocks:
+// per sample, any number per call) are concatenated job-major, cloud 1 before cloud 2; every job owns whole 256-row blocks.
+// The three passes of csrc/compact.h, counted and ranked per SEGMENT (its ballot, rank and scan-step helpers; the scan kernel is
+// this file's own: per job, over 18 segments):
 //   1  mix_key_kernel      one lane per row: segment ids (A, B) of the row (B: the instance class of a cloud-2 row, which may ALSO
 //                          be a sector row), and the rows per (block, segment)
 //   2  mix_scan_kernel     one block per job: exclusive scan of those counts over the job's blocks, segment bases, the job's rows
-//   3  mix_scatter_kernel  rank inside the block from wave ballots, destination = job base + segment base + block offset + rank
-// Order is decided by counts and ranks alone - no atomics - so the result is the reference's order and the same bits every run.
-#include "common.h"
+//   3  mix_scatter_kernel  destination = job base + segment base + block offset + rank inside the block
+// No atomics: the result is the reference's order and the same bits every run.
+#include "compact.h"
+#include "stage_rules.h"
 
 #define MIX_NSEG (2 + TS_MIX_MAX_CLASSES)   // POLAR: 0 cloud 1 kept, 1 cloud 2's sector, 2 + k instance class k ; LASER: band j
 #define MIX_DROP 0xFF
 #define MIX_META (MIX_NSEG + 1)             // per job: segment bases, instance rows
-#define MIX_ROWS 256
 
 namespace {
 
@@ -30,18 +32,18 @@ __device__ __forceinline__ int mix_job_of_block(const double *__restrict__ rec, 
   return j;
 }
 
-__global__ __launch_bounds__(MIX_ROWS) void mix_key_kernel(const float *__restrict__ pts, int64_t n_rows, int f,
+__global__ __launch_bounds__(CP_ROWS) void mix_key_kernel(const float *__restrict__ pts, int64_t n_rows, int f,
                                                            const int64_t *__restrict__ lab,
                                                            const unsigned char *__restrict__ keep,
                                                            const double *__restrict__ rec, const int *__restrict__ classes,
                                                            int n_jobs, uchar2 *__restrict__ keys, int *__restrict__ counts) {
 #pragma clang fp contract(off)
-  __shared__ int wcnt[MIX_ROWS / TS_WAVE][MIX_NSEG];
+  __shared__ int wcnt[MIX_NSEG][CP_WAVES];
   const int b = blockIdx.x, j = mix_job_of_block(rec, n_jobs, b);
   const double *q = rec + (int64_t)j * TS_MIX_RECORD;
   const int kind = (int)q[0];
   const int64_t n1 = (int64_t)q[17], n2 = (int64_t)q[18], row0 = (int64_t)q[19];
-  const int64_t r = (int64_t)(b - (int)q[21]) * MIX_ROWS + threadIdx.x;
+  const int64_t r = (int64_t)(b - (int)q[21]) * CP_ROWS + threadIdx.x;
   const int64_t row = row0 + r;
   unsigned char A = MIX_DROP, B = MIX_DROP;
   if (r < n1 + n2 && row < n_rows) {
@@ -81,17 +83,9 @@ __global__ __launch_bounds__(MIX_ROWS) void mix_key_kernel(const float *__restri
     if (keep && keep[row] == 0) A = B = MIX_DROP;
     keys[row] = make_uchar2(A, B);
   }
-  const int lane = threadIdx.x & (TS_WAVE - 1), w = threadIdx.x / TS_WAVE;
-  for (int s = 0; s < MIX_NSEG; ++s) {
-    const unsigned long long m = __ballot(A == s || B == s);
-    if (lane == 0) wcnt[w][s] = __popcll(m);
-  }
+  for (int s = 0; s < MIX_NSEG; ++s) cp_ballot(A == s || B == s, wcnt[s]);
   __syncthreads();
-  if (threadIdx.x < MIX_NSEG) {
-    int c = 0;
-    for (int v = 0; v < MIX_ROWS / TS_WAVE; ++v) c += wcnt[v][threadIdx.x];
-    counts[(int64_t)b * MIX_NSEG + threadIdx.x] = c;
-  }
+  if (threadIdx.x < MIX_NSEG) counts[(int64_t)b * MIX_NSEG + threadIdx.x] = cp_block_sum(wcnt[threadIdx.x]);
 }
 
 __global__ __launch_bounds__(256) void mix_scan_kernel(const double *__restrict__ rec, int n_blocks,
@@ -108,11 +102,7 @@ __global__ __launch_bounds__(256) void mix_scan_kernel(const double *__restrict_
     for (int c = 0; c < nb; c += TS_WAVE) {
       const int i = c + lane;
       const int v = i < nb ? counts[(int64_t)(first + i) * MIX_NSEG + s] : 0;
-      int incl = v;
-      for (int d = 1; d < TS_WAVE; d <<= 1) {
-        const int t = __shfl_up(incl, d);
-        if (lane >= d) incl += t;
-      }
+      const int incl = cp_wave_inclusive(v, lane);
       if (i < nb) offs[(int64_t)(first + i) * MIX_NSEG + s] = running + incl - v;
       running += __shfl(incl, TS_WAVE - 1);
     }
@@ -132,15 +122,11 @@ __global__ __launch_bounds__(256) void mix_scan_kernel(const double *__restrict_
   }
 }
 
-// np.dot(xyz_f32, [[c, s, 0], [-s, c, 0], [0, 0, 1]]) stored into a float32 array (PolarMix_semantickitti.py:48-53): the ROTATE
-// step of stage_augment_kernel (csrc/stage.hip), dgemm's fused-multiply-add chain in k order, one rounding to float32
+// np.dot(xyz_f32, [[c, s, 0], [-s, c, 0], [0, 0, 1]]) stored into a float32 array (PolarMix_semantickitti.py:48-53): the rotation
+// of csrc/stage_rules.h, one rounding to float32
 __device__ __forceinline__ float4 mix_rotate(float4 p, double c, double s) {
-#pragma clang fp contract(off)
-  const double X = p.x, Y = p.y, Z = p.z;
-  const double rx = fma(Z, 0.0, fma(Y, -s, X * c));
-  const double ry = fma(Z, 0.0, fma(Y, c, X * s));
-  const double rz = fma(Z, 1.0, fma(Y, 0.0, X * 0.0));
-  return make_float4((float)rx, (float)ry, (float)rz, p.w);
+  const double3 r = sr_rotate_z(p.x, p.y, p.z, c, s);
+  return make_float4((float)r.x, (float)r.y, (float)r.z, p.w);
 }
 
 // one output row: xyz (and column 3 under VEC4) from `head`, the other columns from the source row - all of them (tail_all) or
@@ -164,20 +150,20 @@ __device__ __forceinline__ void mix_store(float *__restrict__ out, int64_t *__re
 }
 
 template <bool VEC4>
-__global__ __launch_bounds__(MIX_ROWS) void mix_scatter_kernel(const float *__restrict__ pts, int64_t n_rows, int f,
+__global__ __launch_bounds__(CP_ROWS) void mix_scatter_kernel(const float *__restrict__ pts, int64_t n_rows, int f,
                                                                const int64_t *__restrict__ lab, const uchar2 *__restrict__ keys,
                                                                const double *__restrict__ rec, int n_jobs,
                                                                const int *__restrict__ offs, const int64_t *__restrict__ meta,
                                                                const int64_t *__restrict__ totals, float *__restrict__ out,
                                                                int64_t *__restrict__ out_lab, int *__restrict__ out_job,
                                                                int64_t cap) {
-  __shared__ int wcnt[MIX_ROWS / TS_WAVE][MIX_NSEG];
+  __shared__ int wcnt[MIX_NSEG][CP_WAVES];
   __shared__ int64_t sbase[MIX_NSEG];
   __shared__ int64_t job_base;
   const int b = blockIdx.x, j = mix_job_of_block(rec, n_jobs, b);
   const double *q = rec + (int64_t)j * TS_MIX_RECORD;
   const int64_t n1 = (int64_t)q[17], n2 = (int64_t)q[18], row0 = (int64_t)q[19];
-  const int64_t r = (int64_t)(b - (int)q[21]) * MIX_ROWS + threadIdx.x;
+  const int64_t r = (int64_t)(b - (int)q[21]) * CP_ROWS + threadIdx.x;
   const int64_t row = row0 + r;
   const bool valid = r < n1 + n2 && row < n_rows;
   if (threadIdx.x < MIX_NSEG) sbase[threadIdx.x] = meta[(int64_t)j * MIX_META + threadIdx.x] + offs[(int64_t)b * MIX_NSEG + threadIdx.x];
@@ -192,14 +178,11 @@ __global__ __launch_bounds__(MIX_ROWS) void mix_scatter_kernel(const float *__re
     A = k.x;
     B = k.y;
   }
-  const int lane = threadIdx.x & (TS_WAVE - 1), w = threadIdx.x / TS_WAVE;
-  int rank_a = 0, rank_b = 0;
+  CpBallot ba = {}, bb = {};
   for (int s = 0; s < MIX_NSEG; ++s) {
-    const unsigned long long m = __ballot(A == s || B == s);
-    const int below = __popcll(m & ((1ull << lane) - 1ull));
-    if (A == s) rank_a = below;
-    if (B == s) rank_b = below;
-    if (lane == 0) wcnt[w][s] = __popcll(m);
+    const CpBallot m = cp_ballot(A == s || B == s, wcnt[s]);
+    if (A == s) ba = m;
+    if (B == s) bb = m;
   }
   __syncthreads();
   if (!valid || (A == MIX_DROP && B == MIX_DROP)) return;
@@ -212,13 +195,11 @@ __global__ __launch_bounds__(MIX_ROWS) void mix_scatter_kernel(const float *__re
   }
   const int64_t l = lab[row];
   if (A < MIX_NSEG) {
-    int64_t dst = job_base + sbase[A] + rank_a;
-    for (int v = 0; v < w; ++v) dst += wcnt[v][A];
+    const int64_t dst = job_base + sbase[A] + cp_rank(ba, wcnt[A]);
     mix_store<VEC4>(out, out_lab, out_job, dst, cap, f, p, src, true, l, j);
   }
   if (B < MIX_NSEG) {
-    int64_t dst = job_base + sbase[B] + rank_b;
-    for (int v = 0; v < w; ++v) dst += wcnt[v][B];
+    const int64_t dst = job_base + sbase[B] + cp_rank(bb, wcnt[B]);
     const int64_t inst = meta[(int64_t)j * MIX_META + MIX_NSEG];
     const bool tail_all = q[9] != 0.0;
     mix_store<VEC4>(out, out_lab, out_job, dst, cap, f, p, src, true, l, j);
@@ -261,7 +242,7 @@ extern "C" int ts_stage_mix(const float *points, int64_t n_rows, int32_t point_s
                             int64_t *out_labels, int32_t *out_job, int64_t capacity, int64_t *totals, void *ws, size_t ws_bytes,
                             ts_stream_t stream) {
   TS_REQUIRE(n_rows >= 0 && n_rows < (int64_t)1 << 30 && point_stride >= 3 && n_jobs > 0 && n_jobs <= 1024 && n_blocks >= 0 &&
-                 n_blocks <= n_rows / MIX_ROWS + n_jobs && capacity >= 0,
+                 n_blocks <= n_rows / CP_ROWS + n_jobs && capacity >= 0,
              TS_ERR_INVALID_ARGUMENT, "ts_stage_mix: bad sizes");
   TS_REQUIRE(records && classes && totals && ws && ((uintptr_t)ws & 7) == 0, TS_ERR_INVALID_ARGUMENT, "ts_stage_mix: null pointer");
   TS_REQUIRE(n_rows == 0 || (points && labels), TS_ERR_INVALID_ARGUMENT, "ts_stage_mix: null pointer");
@@ -270,7 +251,7 @@ extern "C" int ts_stage_mix(const float *points, int64_t n_rows, int32_t point_s
   TS_REQUIRE(ws_bytes >= m.bytes, TS_ERR_INVALID_ARGUMENT, "ts_stage_mix: workspace too small");
   hipStream_t st = (hipStream_t)stream;
   if (n_blocks > 0) {
-    mix_key_kernel<<<(int)n_blocks, MIX_ROWS, 0, st>>>(points, n_rows, point_stride, labels, keep, records, classes, n_jobs, m.keys,
+    mix_key_kernel<<<(int)n_blocks, CP_ROWS, 0, st>>>(points, n_rows, point_stride, labels, keep, records, classes, n_jobs, m.keys,
                                                        m.counts);
     TS_CHECK_LAUNCH("ts_stage_mix (keys)");
   }
@@ -278,10 +259,10 @@ extern "C" int ts_stage_mix(const float *points, int64_t n_rows, int32_t point_s
   TS_CHECK_LAUNCH("ts_stage_mix (scan)");
   if (n_blocks > 0) {
     if (point_stride == 4 && ((((uintptr_t)points) | ((uintptr_t)out)) & 15) == 0) {
-      mix_scatter_kernel<true><<<(int)n_blocks, MIX_ROWS, 0, st>>>(points, n_rows, point_stride, labels, m.keys, records, n_jobs,
+      mix_scatter_kernel<true><<<(int)n_blocks, CP_ROWS, 0, st>>>(points, n_rows, point_stride, labels, m.keys, records, n_jobs,
                                                                    m.offs, m.meta, totals, out, out_labels, out_job, capacity);
     } else {
-      mix_scatter_kernel<false><<<(int)n_blocks, MIX_ROWS, 0, st>>>(points, n_rows, point_stride, labels, m.keys, records, n_jobs,
+      mix_scatter_kernel<false><<<(int)n_blocks, CP_ROWS, 0, st>>>(points, n_rows, point_stride, labels, m.keys, records, n_jobs,
                                                                     m.offs, m.meta, totals, out, out_labels, out_job, capacity);
     }
     TS_CHECK_LAUNCH("ts_stage_mix (scatter)");

@@ -11,9 +11,9 @@
 //     1  mov_init_kernel     counters and min / max cells of every candidate
 //     2  mov_probe_kernel    one lane per row: the row's candidate (binary search in its cloud's table; a row of another raw
 //                            class costs no probe), counts and float32 min / max with INTEGER atomics (exact, order-free), the
-//                            matching rows per 256-row block
-//     3  mov_scan_kernel     exclusive scan of those block counts
-//     4  mov_compact_kernel  the matching rows (candidate, x, y, kind) in ROW ORDER: rank inside the block from wave ballots
+//                            matching rows per 256-row block (pass 1 of csrc/compact.h)
+//     3  mov_scan_kernel     its own one-wave exclusive scan of those block counts: int64 offsets and the total, `matched`
+//     4  mov_compact_kernel  the matching rows (candidate, x, y, kind) in ROW ORDER (pass 3 of csrc/compact.h)
 //     5  mov_gather_kernel   one wave per candidate: its rows out of that list, in order: current x / y, history y, x / y at
 //                            frame offset -1
 //     6  mov_mean_kernel     one wave per (candidate, column): numpy's float32 mean - chunks of 8192, numpy's pairwise rule
@@ -21,9 +21,8 @@
 //   ts_stage_moving_apply    one lane per row: the row's record (binary search in the cloud's uploaded record table), centre
 //                            shift, per-offset shift, raw-class rewrite, the mapped label through the 260-entry table
 // No float atomics, order decided by counts and ranks alone: the same bits every run.
-#include "common.h"
+#include "compact.h"
 
-#define MOV_ROWS 256
 #define MOV_NONE 0xFFFF
 #define MOV_CHUNK 8192          // numpy's reduction buffer: a strided float32 column is summed in pieces of 8192
 #define MOV_LEAF 128            // PW_BLOCKSIZE of numpy's pairwise sum
@@ -62,14 +61,14 @@ __global__ __launch_bounds__(256) void mov_init_kernel(int cap, int *__restrict_
   mm[4 * k + 1] = mm[4 * k + 3] = 0u;        // maxima
 }
 
-__global__ __launch_bounds__(MOV_ROWS) void mov_probe_kernel(const float *__restrict__ pts, int64_t n_rows, int64_t n_cur, int f,
+__global__ __launch_bounds__(CP_ROWS) void mov_probe_kernel(const float *__restrict__ pts, int64_t n_rows, int64_t n_cur, int f,
                                                              const int64_t *__restrict__ lab, const int *__restrict__ cloud,
                                                              const int *__restrict__ delta, const int64_t *__restrict__ cand,
                                                              const int *__restrict__ cand_start, int n_clouds, int cap,
                                                              unsigned short *__restrict__ slot, int *__restrict__ counts,
                                                              unsigned *__restrict__ mm, int *__restrict__ blk_cnt) {
-  __shared__ int wcnt[MOV_ROWS / TS_WAVE];
-  const int64_t r = (int64_t)blockIdx.x * MOV_ROWS + threadIdx.x;
+  __shared__ int wcnt[CP_WAVES];
+  const int64_t r = (int64_t)blockIdx.x * CP_ROWS + threadIdx.x;
   int s = -1;
   if (r < n_rows) {
     const int64_t l = lab[r];
@@ -92,15 +91,9 @@ __global__ __launch_bounds__(MOV_ROWS) void mov_probe_kernel(const float *__rest
       }
     }
   }
-  const int lane = threadIdx.x & (TS_WAVE - 1), w = threadIdx.x / TS_WAVE;
-  const unsigned long long m = __ballot(s >= 0);
-  if (lane == 0) wcnt[w] = __popcll(m);
+  cp_ballot(s >= 0, wcnt);
   __syncthreads();
-  if (threadIdx.x == 0) {
-    int c = 0;
-    for (int v = 0; v < MOV_ROWS / TS_WAVE; ++v) c += wcnt[v];
-    blk_cnt[blockIdx.x] = c;
-  }
+  if (threadIdx.x == 0) blk_cnt[blockIdx.x] = cp_block_sum(wcnt);
 }
 
 // one wave: exclusive scan of blk_cnt into blk_off, the total into matched[0]
@@ -111,35 +104,28 @@ __global__ __launch_bounds__(TS_WAVE) void mov_scan_kernel(int64_t n_blocks, con
   for (int64_t c = 0; c < n_blocks; c += TS_WAVE) {
     const int64_t i = c + lane;
     const int v = i < n_blocks ? blk_cnt[i] : 0;
-    int incl = v;
-    for (int d = 1; d < TS_WAVE; d <<= 1) {
-      const int t = __shfl_up(incl, d);
-      if (lane >= d) incl += t;
-    }
+    const int incl = cp_wave_inclusive(v, lane);
     if (i < n_blocks) blk_off[i] = running + incl - v;
     running += __shfl(incl, TS_WAVE - 1);
   }
   if (lane == 0) matched[0] = running;
 }
 
-__global__ __launch_bounds__(MOV_ROWS) void mov_compact_kernel(const float *__restrict__ pts, int64_t n_rows, int64_t n_cur, int f,
+__global__ __launch_bounds__(CP_ROWS) void mov_compact_kernel(const float *__restrict__ pts, int64_t n_rows, int64_t n_cur, int f,
                                                                const int *__restrict__ delta,
                                                                const unsigned short *__restrict__ slot,
                                                                const int64_t *__restrict__ blk_off, int64_t cap_rows,
                                                                unsigned short *__restrict__ l_slot,
                                                                unsigned char *__restrict__ l_kind, float *__restrict__ l_x,
                                                                float *__restrict__ l_y) {
-  __shared__ int wcnt[MOV_ROWS / TS_WAVE];
-  const int64_t r = (int64_t)blockIdx.x * MOV_ROWS + threadIdx.x;
+  __shared__ int wcnt[CP_WAVES];
+  const int64_t r = (int64_t)blockIdx.x * CP_ROWS + threadIdx.x;
   const unsigned short s = r < n_rows ? slot[r] : (unsigned short)MOV_NONE;
   const bool hit = s != MOV_NONE;
-  const int lane = threadIdx.x & (TS_WAVE - 1), w = threadIdx.x / TS_WAVE;
-  const unsigned long long m = __ballot(hit);
-  if (lane == 0) wcnt[w] = __popcll(m);
+  const CpBallot b = cp_ballot(hit, wcnt);
   __syncthreads();
   if (!hit) return;
-  int64_t dst = blk_off[blockIdx.x] + __popcll(m & ((1ull << lane) - 1ull));
-  for (int v = 0; v < w; ++v) dst += wcnt[v];
+  const int64_t dst = blk_off[blockIdx.x] + cp_rank(b, wcnt);
   if (dst >= cap_rows) return;          // (the caller sees matched > cap_rows)
   l_slot[dst] = s;
   l_kind[dst] = r < n_cur ? 0 : (delta[r] == -1 ? 2 : 1);      // current | history | history at frame offset -1
@@ -289,14 +275,14 @@ __global__ __launch_bounds__(TS_WAVE) void mov_mean_kernel(const int *__restrict
   if (lane == 0) out[4 + col] = mean;
 }
 
-__global__ __launch_bounds__(MOV_ROWS) void mov_apply_kernel(float *__restrict__ pts, int64_t n_rows, int64_t n_cur, int f,
+__global__ __launch_bounds__(256) void mov_apply_kernel(float *__restrict__ pts, int64_t n_rows, int64_t n_cur, int f,
                                                              const int64_t *__restrict__ lab, const int *__restrict__ cloud,
                                                              const int *__restrict__ delta, const int64_t *__restrict__ rec_lab,
                                                              const int *__restrict__ rec_start, int n_clouds,
                                                              const double *__restrict__ rec, const int64_t *__restrict__ lut,
                                                              int64_t *__restrict__ out_lab) {
 #pragma clang fp contract(off)
-  const int64_t r = (int64_t)blockIdx.x * MOV_ROWS + threadIdx.x;
+  const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (r >= n_rows) return;
   const int64_t l = lab[r];
   int raw = (int)(l & 0xFFFF);
@@ -341,7 +327,7 @@ MovWorkspace mov_carve(void *ws, int64_t n_rows, int64_t cap, int64_t cap_rows) 
   MovWorkspace m;
   size_t at = 0;
   char *base = (char *)ws;
-  const int64_t n_blocks = ts_cdiv(n_rows, MOV_ROWS);
+  const int64_t n_blocks = ts_cdiv(n_rows, CP_ROWS);
   auto take = [&](size_t bytes) {
     char *p = base + at;
     at += ts_align_up(bytes, 256);
@@ -379,18 +365,18 @@ extern "C" int ts_stage_moving_stats(const float *points, int64_t n_rows, int64_
   const MovWorkspace m = mov_carve(ws, n_rows, cap, cap_rows);
   TS_REQUIRE(ws_bytes >= m.bytes, TS_ERR_INVALID_ARGUMENT, "ts_stage_moving_stats: workspace too small");
   hipStream_t st = (hipStream_t)stream;
-  const int64_t n_blocks = ts_cdiv(n_rows, MOV_ROWS);
+  const int64_t n_blocks = ts_cdiv(n_rows, CP_ROWS);
   mov_init_kernel<<<(int)ts_cdiv(cap, 256), 256, 0, st>>>(cap, counts, m.mm);
   TS_CHECK_LAUNCH("ts_stage_moving_stats (init)");
   if (n_blocks > 0) {
-    mov_probe_kernel<<<(int)n_blocks, MOV_ROWS, 0, st>>>(points, n_rows, n_cur, point_stride, labels, cloud, delta, cand, cand_start,
+    mov_probe_kernel<<<(int)n_blocks, CP_ROWS, 0, st>>>(points, n_rows, n_cur, point_stride, labels, cloud, delta, cand, cand_start,
                                                          n_clouds, cap, m.slot, counts, m.mm, m.blk_cnt);
     TS_CHECK_LAUNCH("ts_stage_moving_stats (probe)");
   }
   mov_scan_kernel<<<1, TS_WAVE, 0, st>>>(n_blocks, m.blk_cnt, m.blk_off, matched);
   TS_CHECK_LAUNCH("ts_stage_moving_stats (scan)");
   if (n_blocks > 0) {
-    mov_compact_kernel<<<(int)n_blocks, MOV_ROWS, 0, st>>>(points, n_rows, n_cur, point_stride, delta, m.slot, m.blk_off, cap_rows,
+    mov_compact_kernel<<<(int)n_blocks, CP_ROWS, 0, st>>>(points, n_rows, n_cur, point_stride, delta, m.slot, m.blk_off, cap_rows,
                                                            m.l_slot, m.l_kind, m.l_x, m.l_y);
     TS_CHECK_LAUNCH("ts_stage_moving_stats (compact)");
   }
@@ -413,7 +399,7 @@ extern "C" int ts_stage_moving_apply(float *points, int64_t n_rows, int64_t n_cu
   TS_REQUIRE(rec_start && lut, TS_ERR_INVALID_ARGUMENT, "ts_stage_moving_apply: null pointer");
   if (n_rows == 0) return TS_OK;
   TS_REQUIRE(points && labels && cloud && delta && out_labels, TS_ERR_INVALID_ARGUMENT, "ts_stage_moving_apply: null pointer");
-  mov_apply_kernel<<<(int)ts_cdiv(n_rows, MOV_ROWS), MOV_ROWS, 0, (hipStream_t)stream>>>(
+  mov_apply_kernel<<<(int)ts_cdiv(n_rows, 256), 256, 0, (hipStream_t)stream>>>(
       points, n_rows, n_cur, point_stride, labels, cloud, delta, rec_labels, rec_start, n_clouds, records, lut, out_labels);
   TS_CHECK_LAUNCH("ts_stage_moving_apply");
   return TS_OK;

@@ -5,6 +5,7 @@
 // chains these kernels with ts_fuse_scans_batch / ts_fuse_sweeps, ts_segment_min3, ts_voxel_coords and ts_sparse_quantize; every
 // tensor of the resulting batch_dict equals the per-sample form bit for bit (tests/test_gpu_ops.py).
 #include "common.h"
+#include "stage_rules.h"
 
 // keep[i] = pre[i] (optional) AND table[scan[i]][class(i)] AND (x, y, z)(i) >= lo[sample(i)]  ;  sample[i] = sample_of_scan[scan[i]]
 //   class(i) = cls[i], or the column neg_col where cls[i] < 0 (KITTI: a pseudo label that is no class's canonical raw id: never kept)
@@ -19,15 +20,12 @@ __global__ __launch_bounds__(256) void stage_keep_kernel(const float *__restrict
   const int64_t step = (int64_t)gridDim.x * blockDim.x;
   for (; i < n; i += step) {
     const int s = min(max(scan[i], 0), n_scans - 1);
-    int64_t c = cls[i];
-    if (c < 0) c = neg_col;
     const int64_t b = sample_of_scan[s];
-    bool k = c >= 0 && c < cols && table[(int64_t)s * cols + c] != 0;
+    bool k = sr_class_step(table, s, cls[i], cols, neg_col);
     if (pre) k = k && pre[i] != 0;
     if (k && b >= 0 && b < n_samples) {
       const float *p = pts + i * pstride;
-      const float *l = lo + 3 * b;
-      k = p[0] >= l[0] && p[1] >= l[1] && p[2] >= l[2];
+      k = sr_clamp_keeps(p[0], p[1], p[2], lo, b);
     } else {
       k = false;
     }
@@ -52,26 +50,17 @@ extern "C" int ts_stage_keep_flags(const float *points, int64_t n, int32_t point
   return TS_OK;
 }
 
-// Point augmentation (R/tools/utils/common/seg_utils.py:102-166 aug_points_ms, :43-100 aug_points): rotation about z, scale, x/y
-// flip, translation on the xyz columns, one parameter record of TS_AUG_RECORD doubles per sample:
-//   { c, s, scale, tx, ty, tz, bits, flip }   bits: 1 rotate, 2 scale, 4 flip, 8 translate, 16 scale in float32 ; flip: 0 .. 3
-// The reference multiplies the float32 cloud with a float64 matrix (np.dot), so everything after the rotation is float64 and the
-// store into its float32 array (semantickitti_voxel_ms.py:90) is the ONE rounding; a step that is switched off is skipped, not run
-// with identity values (-0.0 + 0.0 = +0.0), so a record without bits returns the input's bits.  Bit 16: without the rotation the
-// cloud is still float32 when it is scaled and numpy multiplies a float32 array by a Python float IN float32 - host-side choice
-// (taseg_amd/data/augment.py), the kernel only honours it.
+// Point augmentation: sr_augment (csrc/stage_rules.h) on the xyz columns, one parameter record of TS_AUG_RECORD doubles per sample.
 // One lane per point; VEC4: rows of 4 floats, 16-byte aligned -> one 16-byte load and one 16-byte store per lane.
 template <bool VEC4>
 __global__ __launch_bounds__(256) void stage_augment_kernel(const float *pts, int64_t n, int pstride,
                                                             const int *__restrict__ sample, const double *__restrict__ params,
                                                             int n_samples, float *out) {   // out may BE pts (in place)
-#pragma clang fp contract(off)
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t step = (int64_t)gridDim.x * blockDim.x;
   for (; i < n; i += step) {
     const int b = sample ? min(max(sample[i], 0), n_samples - 1) : 0;
     const double *q = params + (int64_t)TS_AUG_RECORD * b;
-    const int bits = (int)q[6];
     float4 p;
     if (VEC4) {
       p = reinterpret_cast<const float4 *>(pts)[i];
@@ -79,46 +68,7 @@ __global__ __launch_bounds__(256) void stage_augment_kernel(const float *pts, in
       const float *r = pts + i * pstride;
       p = make_float4(r[0], r[1], r[2], 0.f);
     }
-    if (bits & 15) {
-      double X = p.x, Y = p.y, Z = p.z;
-      if (bits & 1) {
-        // np.dot(xyz, [[c, s, 0], [-s, c, 0], [0, 0, 1]]): dgemm's fused-multiply-add chain in k order, as in ts_fuse_sweeps.  The
-        // order matters where x*c and y*s cancel (a point at 45 degrees of azimuth under the TTA rotation pi/4): what is left is
-        // the rounding error of the first product, and it decides the float32 result.
-        const double c = q[0], s = q[1];
-        const double rx = fma(Z, 0.0, fma(Y, -s, X * c));
-        const double ry = fma(Z, 0.0, fma(Y, c, X * s));
-        const double rz = fma(Z, 1.0, fma(Y, 0.0, X * 0.0));
-        X = rx;
-        Y = ry;
-        Z = rz;
-      }
-      if (bits & 2) {
-        if (bits & 16) {
-          const float sc = (float)q[2];
-          X = (double)__fmul_rn((float)X, sc);
-          Y = (double)__fmul_rn((float)Y, sc);
-          Z = (double)__fmul_rn((float)Z, sc);
-        } else {
-          X *= q[2];
-          Y *= q[2];
-          Z *= q[2];
-        }
-      }
-      if (bits & 4) {
-        const int flip = (int)q[7];
-        if (flip & 1) X = -X;
-        if (flip & 2) Y = -Y;
-      }
-      if (bits & 8) {
-        X += q[3];
-        Y += q[4];
-        Z += q[5];
-      }
-      p.x = (float)X;
-      p.y = (float)Y;
-      p.z = (float)Z;
-    }
+    sr_augment(q, p.x, p.y, p.z);
     if (VEC4) {
       reinterpret_cast<float4 *>(out)[i] = p;
     } else {

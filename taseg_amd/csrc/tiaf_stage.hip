@@ -7,16 +7,10 @@
 //                         255 through the host's table, the flip, the top-left crop and the zero padding in the one store that
 //                         writes every output element.  Frame pointers, sizes and flip bytes travel in the kernel arguments.
 //   ts_tiaf_fov_cloud     projection -> flip -> crop test -> FOV_DIST -> pose fuse -> augmentation -> clamp per row, the survivors
-//                         as one stable compaction, in the three-launch idiom of csrc/compact.hip:
-//                           1  tf_count_kernel    one lane per row: survivors per block of 256 rows (wave ballots), per (block, sample)
-//                           2  tf_scan_kernel     one block: the survivors of every sample, exclusive scan of the block counts
-//                           3  tf_scatter_kernel  the decision of pass 1 recomputed on the same bits, rank inside the block from wave
-//                                                 ballots, destination = block offset + rank
-//                         No atomics: the rows keep their input order and the bits are the same every run.
-#include "common.h"
-
-#define TF_ROWS 256
-#define TF_WAVES (TF_ROWS / TS_WAVE)
+//                         as one stable compaction: the three passes of csrc/compact.h with tf_row as the row rule, one tally per
+//                         sample; the augmentation and the clamp inside tf_row are those of csrc/stage_rules.h.
+#include "compact.h"
+#include "stage_rules.h"
 
 namespace {
 
@@ -119,8 +113,8 @@ struct TfRule {
 };
 
 // Does virtual row i survive, and as which output row?  o = (x, y, z, intensity, row + row_offset, col); *sample its sample.
-// The arithmetic restates project_fov_kernel / fuse_scan_kernel (csrc/pointops.hip) and stage_augment_kernel (csrc/stage.hip)
-// with the same explicit intrinsics; both passes call it, so pass 3 decides on the bits pass 1 counted.
+// Steps 1 - 5 restate project_fov_kernel / fuse_scan_kernel (csrc/pointops.hip) with the same explicit intrinsics; both passes
+// call it, so pass 3 decides on the bits pass 1 counted.
 __device__ __forceinline__ bool tf_row(const TfRule &r, int64_t i, float (&o)[6], int *sample) {
 #pragma clang fp contract(off)  // only the explicit fma() below fuse (__fmul_rn / __fadd_rn are inline functions of the HIP headers:
                                 // they keep their roundings because build.py compiles this file with -ffp-contract=off, as pointops.hip)
@@ -172,53 +166,9 @@ __device__ __forceinline__ bool tf_row(const TfRule &r, int64_t i, float (&o)[6]
       q[j] = s;
     }
   }
-  // 6  ts_stage_augment: float64 in the reference's order, ONE rounding to float32, a step that is off skipped
-  if (r.aug) {
-    const double *a = r.aug + (int64_t)TS_AUG_RECORD * b;
-    const int bits = (int)a[6];
-    if (bits & 15) {
-      double X = q[0], Y = q[1], Z = q[2];
-      if (bits & 1) {
-        const double c = a[0], s = a[1];
-        const double rx = fma(Z, 0.0, fma(Y, -s, X * c));
-        const double ry = fma(Z, 0.0, fma(Y, c, X * s));
-        const double rz = fma(Z, 1.0, fma(Y, 0.0, X * 0.0));
-        X = rx;
-        Y = ry;
-        Z = rz;
-      }
-      if (bits & 2) {
-        if (bits & 16) {
-          const float sc = (float)a[2];
-          X = (double)__fmul_rn((float)X, sc);
-          Y = (double)__fmul_rn((float)Y, sc);
-          Z = (double)__fmul_rn((float)Z, sc);
-        } else {
-          X *= a[2];
-          Y *= a[2];
-          Z *= a[2];
-        }
-      }
-      if (bits & 4) {
-        const int flip = (int)a[7];
-        if (flip & 1) X = -X;
-        if (flip & 2) Y = -Y;
-      }
-      if (bits & 8) {
-        X += a[3];
-        Y += a[4];
-        Z += a[5];
-      }
-      q[0] = (float)X;
-      q[1] = (float)Y;
-      q[2] = (float)Z;
-    }
-  }
-  // 7  the clamp of ts_stage_clamp_compact: numpy's `>=` on float32, false for NaN on either side
-  if (r.lo) {
-    const float *m = r.lo + 3 * b;
-    if (!(q[0] >= m[0] && q[1] >= m[1] && q[2] >= m[2])) return false;
-  }
+  // 6  ts_stage_augment, 7  the clamp of ts_stage_clamp_compact
+  if (r.aug) sr_augment(r.aug + (int64_t)TS_AUG_RECORD * b, q[0], q[1], q[2]);
+  if (r.lo && !sr_clamp_keeps(q[0], q[1], q[2], r.lo, b)) return false;
   o[0] = q[0];
   o[1] = q[1];
   o[2] = q[2];
@@ -228,83 +178,38 @@ __device__ __forceinline__ bool tf_row(const TfRule &r, int64_t i, float (&o)[6]
   return true;
 }
 
-__global__ __launch_bounds__(TF_ROWS) void tf_count_kernel(TfRule r, int *__restrict__ blk_cnt, int *__restrict__ blk_sample) {
-  __shared__ int wcnt[TF_WAVES];
-  __shared__ int scnt[TF_WAVES][TS_TIAF_MAX_SAMPLES];
-  const int64_t i = (int64_t)blockIdx.x * TF_ROWS + threadIdx.x;
-  const int lane = threadIdx.x & (TS_WAVE - 1), w = threadIdx.x / TS_WAVE;
-  scnt[w][lane] = 0;                    // (TS_TIAF_MAX_SAMPLES == TS_WAVE: every wave clears its own row)
+__global__ __launch_bounds__(CP_ROWS) void tf_count_kernel(TfRule r, int *__restrict__ blk_cnt, int *__restrict__ blk_tally) {
+  __shared__ int wcnt[CP_WAVES];
+  __shared__ int scnt[CP_WAVES][TS_WAVE];
+  const int64_t i = (int64_t)blockIdx.x * CP_ROWS + threadIdx.x;
+  cp_tally_clear<1>(scnt);
   __syncthreads();
   int s = -1;
-  bool keep = false;
+  bool keep[1] = {false};
   if (i < r.n_rows) {
     float o[6];
-    keep = tf_row(r, i, o, &s);
+    keep[0] = tf_row(r, i, o, &s);
   }
-  unsigned long long rem = __ballot(keep);
-  if (lane == 0) wcnt[w] = __popcll(rem);
-  // the samples ascend: a wave holds one sample, or a few at a boundary - one round per distinct sample (rem is wave-uniform)
-  while (rem) {
-    const int s0 = __shfl(s, __ffsll((long long)rem) - 1);
-    const unsigned long long m = __ballot(keep && s == s0);
-    if (lane == 0) scnt[w][s0] += __popcll(m);
-    rem &= ~m;
-  }
+  cp_ballot(keep[0], wcnt);
+  cp_tally_wave<1>(s, keep, scnt);
   __syncthreads();
-  if (threadIdx.x == 0) {
-    int c = 0;
-    for (int v = 0; v < TF_WAVES; ++v) c += wcnt[v];
-    blk_cnt[blockIdx.x] = c;
-  }
-  if (threadIdx.x < r.n_samples) {
-    int c = 0;
-    for (int v = 0; v < TF_WAVES; ++v) c += scnt[v][threadIdx.x];
-    blk_sample[(int64_t)blockIdx.x * r.n_samples + threadIdx.x] = c;
-  }
+  if (threadIdx.x == 0) blk_cnt[blockIdx.x] = cp_block_sum(wcnt);
+  cp_tally_store<1>(scnt, r.n_samples, blk_tally);
 }
 
-__global__ __launch_bounds__(256) void tf_scan_kernel(int n_blocks, int n_samples, const int *__restrict__ blk_cnt,
-                                                      const int *__restrict__ blk_sample, int *__restrict__ offs,
-                                                      int64_t *__restrict__ counts) {
-  const int lane = threadIdx.x & (TS_WAVE - 1), w = threadIdx.x / TS_WAVE;
-  // the survivors of every sample: one wave per sample, the blocks lane-strided (integer sums: any order gives the same value)
-  for (int s = w; s < n_samples; s += 256 / TS_WAVE) {
-    int c = 0;                           // (n < 2^30 rows in all)
-    for (int b = lane; b < n_blocks; b += TS_WAVE) c += blk_sample[(int64_t)b * n_samples + s];
-    for (int d = TS_WAVE / 2; d > 0; d >>= 1) c += __shfl_xor(c, d);
-    if (lane == 0) counts[s] = (int64_t)c;
-  }
-  if (w != 0) return;
-  int running = 0;
-  for (int c = 0; c < n_blocks; c += TS_WAVE) {
-    const int i = c + lane;
-    const int v = i < n_blocks ? blk_cnt[i] : 0;
-    int incl = v;
-    for (int d = 1; d < TS_WAVE; d <<= 1) {
-      const int t = __shfl_up(incl, d);
-      if (lane >= d) incl += t;
-    }
-    if (i < n_blocks) offs[i] = running + incl - v;
-    running += __shfl(incl, TS_WAVE - 1);
-  }
-}
-
-__global__ __launch_bounds__(TF_ROWS) void tf_scatter_kernel(TfRule r, const int *__restrict__ offs, float *__restrict__ out,
+__global__ __launch_bounds__(CP_ROWS) void tf_scatter_kernel(TfRule r, const int *__restrict__ offs, float *__restrict__ out,
                                                              int64_t *__restrict__ out_sample, int *__restrict__ out_sample32,
                                                              int64_t capacity) {
-  __shared__ int wcnt[TF_WAVES];
-  const int64_t i = (int64_t)blockIdx.x * TF_ROWS + threadIdx.x;
-  const int lane = threadIdx.x & (TS_WAVE - 1), w = threadIdx.x / TS_WAVE;
+  __shared__ int wcnt[CP_WAVES];
+  const int64_t i = (int64_t)blockIdx.x * CP_ROWS + threadIdx.x;
   int s = -1;
   bool keep = false;
   float o[6];
   if (i < r.n_rows) keep = tf_row(r, i, o, &s);             // the decision of pass 1 on the same bits
-  const unsigned long long m = __ballot(keep);
-  if (lane == 0) wcnt[w] = __popcll(m);
+  const CpBallot b = cp_ballot(keep, wcnt);
   __syncthreads();
   if (!keep) return;
-  int64_t dst = (int64_t)offs[blockIdx.x] + __popcll(m & ((1ull << lane) - 1ull));
-  for (int v = 0; v < w; ++v) dst += wcnt[v];
+  const int64_t dst = offs[blockIdx.x] + cp_rank(b, wcnt);
   if (dst < 0 || dst >= capacity) return;                   // (cannot happen: survivors <= rows <= capacity; bounds every store)
   float2 *d = reinterpret_cast<float2 *>(out + dst * 6);    // rows of 24 bytes: 8-byte aligned
   d[0] = make_float2(o[0], o[1]);
@@ -312,25 +217,6 @@ __global__ __launch_bounds__(TF_ROWS) void tf_scatter_kernel(TfRule r, const int
   d[2] = make_float2(o[4], o[5]);
   out_sample[dst] = s;
   out_sample32[dst] = s;
-}
-
-struct TfWorkspace {
-  int *blk_cnt, *offs, *blk_sample;
-  size_t bytes;
-};
-
-TfWorkspace tf_carve(void *ws, int64_t n_blocks, int64_t n_samples) {
-  TfWorkspace c;
-  size_t at = 0;
-  char *base = (char *)ws;
-  c.blk_cnt = (int *)(base + at);
-  at += ts_align_up((size_t)n_blocks * sizeof(int), 256);
-  c.offs = (int *)(base + at);
-  at += ts_align_up((size_t)n_blocks * sizeof(int), 256);
-  c.blk_sample = (int *)(base + at);
-  at += ts_align_up((size_t)n_blocks * n_samples * sizeof(int), 256);
-  c.bytes = std::max<size_t>(at, 256);
-  return c;
 }
 
 }  // namespace
@@ -374,14 +260,14 @@ extern "C" int ts_tiaf_image_stack(const uint8_t *const *images, const float *co
 }
 
 extern "C" size_t ts_tiaf_fov_cloud_workspace_bytes(int64_t n_rows, int32_t n_samples) {
-  return tf_carve(nullptr, ts_cdiv(std::max<int64_t>(n_rows, 0), TF_ROWS), std::max(n_samples, 0)).bytes;
+  return cp_carve(nullptr, ts_cdiv(std::max<int64_t>(n_rows, 0), CP_ROWS), 1, std::max(n_samples, 0)).bytes;
 }
 
 extern "C" int ts_tiaf_fov_cloud(const float *points, int64_t n_points, const int32_t *frame, int64_t n_rows,
                                  const TsTiafFrame *records, int32_t n_frames, const double *aug, const float *lo, int32_t n_samples,
                                  int32_t crop_h, int32_t crop_w, float *out, int64_t *out_sample, int32_t *out_sample32,
                                  int64_t capacity, int64_t *counts, void *ws, size_t ws_bytes, ts_stream_t stream) {
-  static_assert(TS_TIAF_MAX_SAMPLES == TS_WAVE, "tf_count_kernel clears one LDS row per wave");
+  static_assert(TS_TIAF_MAX_SAMPLES == TS_WAVE, "tf_count_kernel keeps one LDS counter per (wave, sample)");
   static_assert(sizeof(TsTiafFrame) == 256, "the frame record is 256 bytes (taseg_amd/data/tiaf.py FRAME_DTYPE)");
   TS_REQUIRE(n_points >= 0 && n_rows >= 0 && n_rows < (int64_t)1 << 30 && n_points < (int64_t)1 << 30 && n_frames >= 1 &&
                  n_frames <= TS_TIAF_MAX_FRAMES && n_samples >= 1 && n_samples <= TS_TIAF_MAX_SAMPLES && crop_h > 0 && crop_w > 0 &&
@@ -393,19 +279,19 @@ extern "C" int ts_tiaf_fov_cloud(const float *points, int64_t n_points, const in
              "ts_tiaf_fov_cloud: null pointer");
   TS_REQUIRE((((uintptr_t)points) & 15) == 0 && (((uintptr_t)out) & 7) == 0, TS_ERR_INVALID_ARGUMENT,
              "ts_tiaf_fov_cloud: points must be 16-byte, out 8-byte aligned");
-  const int64_t n_blocks = ts_cdiv(n_rows, TF_ROWS);
-  const TfWorkspace c = tf_carve(ws, n_blocks, n_samples);
+  const int64_t n_blocks = ts_cdiv(n_rows, CP_ROWS);
+  const CpWorkspace c = cp_carve(ws, n_blocks, 1, n_samples);
   TS_REQUIRE(ws_bytes >= c.bytes, TS_ERR_INVALID_ARGUMENT, "ts_tiaf_fov_cloud: workspace too small");
   hipStream_t st = (hipStream_t)stream;
   const TfRule r = {(const float4 *)points, frame, records, aug, lo, n_rows, n_points, n_frames, n_samples, crop_h, crop_w};
   if (n_blocks > 0) {
-    tf_count_kernel<<<(int)n_blocks, TF_ROWS, 0, st>>>(r, c.blk_cnt, c.blk_sample);
+    tf_count_kernel<<<(int)n_blocks, CP_ROWS, 0, st>>>(r, c.blk_cnt, c.blk_tally);
     TS_CHECK_LAUNCH("ts_tiaf_fov_cloud (count)");
   }
-  tf_scan_kernel<<<1, 256, 0, st>>>((int)n_blocks, n_samples, c.blk_cnt, c.blk_sample, c.offs, counts);
+  ts_compact_scan(c, (int)n_blocks, 1, n_samples, counts, st);
   TS_CHECK_LAUNCH("ts_tiaf_fov_cloud (scan)");
   if (n_blocks > 0) {
-    tf_scatter_kernel<<<(int)n_blocks, TF_ROWS, 0, st>>>(r, c.offs, out, out_sample, out_sample32, capacity);
+    tf_scatter_kernel<<<(int)n_blocks, CP_ROWS, 0, st>>>(r, c.offs, out, out_sample, out_sample32, capacity);
     TS_CHECK_LAUNCH("ts_tiaf_fov_cloud (scatter)");
   }
   return TS_OK;

@@ -135,6 +135,26 @@ def test_many_blocks_twice_the_same_bits():
     assert got[4].tolist() == want[3].tolist() and np.array_equal(bits(got[0][:m].cpu().numpy()), bits(want[0]))
 
 
+@pytest.mark.parametrize("n_blocks", [255, 256, 257, 513, 1000])
+def test_block_counts_around_the_scan_chunk(n_blocks):
+    """the scan's 256 threads own one block count each up to 256 blocks and several behind it (chunks of 2, 3 and 4 here; the last
+    chunks partial or empty); the last block of rows is partial"""
+    rng = np.random.RandomState(n_blocks)
+    n = 256 * n_blocks - 5
+    first = n // 5
+    run(*batch(rng, [first, 0, n - first], 4))
+
+
+def test_64_samples_over_257_blocks():
+    """every wave of the scan's tally blocks sums a row"""
+    rng = np.random.RandomState(64)
+    n = 256 * 257 - 5
+    sizes = [int(v) for v in rng.randint(500, 1500, 63)]
+    sizes[11] = 0
+    assert sum(sizes) < n
+    run(*batch(rng, sizes + [n - sum(sizes)], 4))
+
+
 def test_arguments_are_checked():
     pts, lab, s, lo = (T(np.zeros((4, 4), np.float32)), T(np.zeros(4, np.int64)), T(np.zeros(4, np.int32)), T(np.zeros((1, 3), np.float32)))
     with pytest.raises(RuntimeError, match="no CPU fallback"):

@@ -151,10 +151,11 @@ def test_layout_pair_one_sample_matches_the_rule(n_hist):
         assert any(bits_equal(r[:3], d["lo"][0]) for r in s[0][301:]), "the row equal to the minimum is kept"
 
 
-@pytest.mark.parametrize("n_hist", [0, 1, 255, 256, 257, 513])
+@pytest.mark.parametrize("n_hist", [0, 1, 255, 256, 257, 513, 256 * 257 + 1])
 def test_layout_pair_three_samples_the_middle_one_without_history(n_hist):
     # sample 0: half of the rows in two scans; sample 1: none; sample 2: the rest in two scans - more than one block of current
-    # rows too, and an odd number of them
+    # rows too, and an odd number of them.  256 * 257 + 1 rows are 258 blocks: every thread of both clouds' scans owns two block
+    # counts, the last chunks partial or empty
     d = make_inputs(200 + n_hist, [257, 130, 401], [split(n_hist // 2, 2), [], split(n_hist - n_hist // 2, 2)])
     counts = check_against_rule(d, n_hist)
     assert not counts[1].any()

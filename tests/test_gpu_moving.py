@@ -207,8 +207,9 @@ def test_means_follow_numpy_at_every_size_of_the_rule():
     same_table(S.moving_tables([s])[0][0], got, "second run")
 
 
-@pytest.mark.parametrize("total", [255, 256, 257, 513])
+@pytest.mark.parametrize("total", [255, 256, 257, 513, 64 * 256 + 3])
 def test_rows_straddling_the_block_size(total):
+    # (64 * 256 + 3 rows: 65 blocks, the last instance row's block offset is the carry of the scan's first wave-wide step)
     rng = np.random.RandomState(total)
     s, cur, full_c, hp, hl, hd = synthetic_cloud(rng, [25, 15], 20, deltas=(-1,), hist_share=1.0)
     # (40 + 20 current rows, 40 + 20 history rows; pad the history up to `total` rows in all, the last row an instance row)

@@ -323,6 +323,29 @@ def test_fov_cloud_without_records_of_augmentation_and_clamp_and_shared_rows(g):
     assert s64[:2 * k].tolist() == [0] * k + [1] * k
 
 
+def test_fov_cloud_more_than_256_blocks_of_shared_rows(g):
+    """220 records over three samples read the same 300 point rows: 66 000 virtual rows, 258 blocks, so every thread of the scan
+    owns two block counts and the last chunks are partial or empty; the rows of ts_project_fov's mask once per record"""
+    from taseg_amd import backend as B
+    from taseg_amd.data import tiaf as TF
+    from taseg_amd.data.stage import rows_index32
+    c = fov_case(g, -1.0)
+    proj, p = T(g["proj"]), T(c["pts"][0])
+    pix, ok = B.project_fov(p, proj, c["img"], c["crop"], 0.0)
+    want = torch.cat([p[ok], pix[ok]], 1)
+    n, k, n_rec = len(c["pts"][0]), int(ok.sum()), 220
+    assert n * n_rec > 256 * 257 and 0 < k < n
+    sample = [0] * 100 + [1] * 7 + [2] * 113
+    pose0, pose = T(c["pose0"][0]), T(c["pose"][0])
+    entries = [(proj, pose0, pose, {"row_offset": 0.0, "fov_dist": -1.0, "sample": b, "img_w": c["img"][0], "img_h": c["img"][1],
+                                    "flags": 0, "first": r * n, "src": 0}) for r, b in enumerate(sample)]
+    out, s64, s32, counts = B.tiaf_fov_cloud(p, rows_index32([n] * n_rec, p.device), TF._frame_records(entries, p.device), 3, c["crop"])
+    assert counts.tolist() == [100 * k, 7 * k, 113 * k]
+    assert torch.equal(out[:n_rec * k].view(torch.int32), want.repeat(n_rec, 1).view(torch.int32))
+    want_s = torch.tensor(sample, device=p.device).repeat_interleave(k)
+    assert torch.equal(s64[:n_rec * k], want_s) and torch.equal(s32[:n_rec * k], want_s.int())
+
+
 def test_fov_cloud_checks_its_arguments(g):
     from taseg_amd import backend as B
     p = torch.zeros((4, 4), device="cuda")
