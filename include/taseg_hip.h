@@ -1150,6 +1150,50 @@ int ts_tiaf_fov_cloud(const float *points, int64_t n_points, const int32_t *fram
                       float *out, int64_t *out_sample, int32_t *out_sample32, int64_t capacity, int64_t *counts, void *ws,
                       size_t ws_bytes, ts_stream_t stream);
 
+/* The camera side of the nuScenes TIAF stage for a whole batch (csrc/nusc_tiaf_stage.hip; taseg_amd/data/nuscenes_tiaf.py).
+ *
+ * ts_nusc_fov_cloud: the FOV cloud of a whole batch as one stable compaction over VIRTUAL rows, a virtual row being a (point row,
+ * camera record) pair (nuscenes_ms_mm.py:297-305, 329-398 per keyframe and view; nuscenes_voxel_ms_mm.py:92-135 per sample).
+ * points [n_points, 4] float32: the clouds of the batch's image keyframes, each in ITS keyframe's lidar frame - what ONE
+ * ts_fuse_sweeps call over every keyframe's interval predecessors leaves (:246-295); labels [n_points] int64; pre_keep [n_points]
+ * uint8 or NULL: that call's ego-box byte.  frame [n_rows] int32 ASCENDING names the record of every virtual row, and virtual row
+ * i of record f reads point row records[f].src + (i - records[f].first) - the views of a keyframe, and the votes of a TTA batch,
+ * read the same point rows.  records [n_frames <= TS_TIAF_MAX_FRAMES] TsNuscCamFrame on the device (their samples ascending; inside
+ * a sample keyframe-major, view-minor: the order of the reference's loops), aug [n_samples, TS_AUG_RECORD] doubles or NULL, lo
+ * [n_samples, 3] float32 - the minimum of the sample's AUGMENTED single-frame cloud - or NULL, 1 <= n_samples <=
+ * TS_TIAF_MAX_SAMPLES.  Per virtual row, in this order:
+ *   a  pre_keep[point row] != 0                                                                            (:288 / :306)
+ *   b  paint_dist > 0: sqrt(x * x + y * y) <= paint_dist, float32 multiply, add, sqrt                      (:297-300)
+ *   c  the camera chain, frustum test, half-resolution pixel and top-row cut of ts_project_cam with the record's cam, img_w,
+ *      img_h, crop_top                                                                                     (:349-398)
+ *   d  p = f32(p . B + b) with the record's move, as ts_fuse_sweeps' flagB - ALWAYS: the current keyframe's move is the
+ *      rounded identity relative_transform(current, current) gives                                         (:305)
+ *   e  aug: the arithmetic of ts_stage_augment on xyz with the sample's record          (nuscenes_voxel_ms_mm.py:92-125)
+ *   f  lo: x >= lo[s][0] && y >= lo[s][1] && z >= lo[s][2], NaN on either side fails                       (... :133-135)
+ * A row whose sample or point row is out of range does not survive.  out [capacity, 6] float32 = (x, y, z, intensity, row +
+ * row_offset, col) of the survivors in input order, out_labels int64 their labels, out_sample int64 / out_sample32 int32 their
+ * samples (the rows behind the survivors are not written); counts [n_samples] int64 the survivors of every sample - the caller's
+ * one host read.  capacity >= n_rows bounds every store.  Three launches (counts per block of 256 rows from wave ballots, the
+ * shared scan, the scatter by rank - pass 3 recomputes the decision of pass 1 on the same bits); no atomics: the same bits every
+ * run.  A wave walks the records its rows name one after the other, so the 69 doubles of a record are read through a wave-uniform
+ * address. */
+typedef struct TsNuscCamFrame {
+  double cam[57];          /* the camera chain, the layout of ts_project_cam */
+  double move[12];         /* B[9] row-major, b[3]: relative_transform(current keyframe, the record's keyframe) */
+  float row_offset;        /* HEIGHT * position of the image in its sample's stack */
+  float paint_dist;        /* <= 0: off */
+  int32_t sample;
+  int32_t img_w, img_h;    /* the full-size camera image */
+  int32_t crop_top;        /* rows cut from the top of the half-resolution image */
+  int32_t first;           /* the record's first virtual row */
+  int32_t src;             /* the point row it reads */
+} TsNuscCamFrame;
+size_t ts_nusc_fov_cloud_workspace_bytes(int64_t n_rows, int32_t n_samples);
+int ts_nusc_fov_cloud(const float *points, const int64_t *labels, const uint8_t *pre_keep, int64_t n_points, const int32_t *frame,
+                      int64_t n_rows, const TsNuscCamFrame *records, int32_t n_frames, const double *aug, const float *lo,
+                      int32_t n_samples, float *out, int64_t *out_labels, int64_t *out_sample, int32_t *out_sample32,
+                      int64_t capacity, int64_t *counts, void *ws, size_t ws_bytes, ts_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

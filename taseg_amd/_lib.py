@@ -184,6 +184,8 @@ SIGNATURES = {
     "ts_tiaf_image_stack": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _i32, _i64, _i64, _vp, _vp, _vp]),
     "ts_tiaf_fov_cloud_workspace_bytes": (_sz, [_i64, _i32]),
     "ts_tiaf_fov_cloud": (_i32, [_vp, _i64, _vp, _i64, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _sz, _vp]),
+    "ts_nusc_fov_cloud_workspace_bytes": (_sz, [_i64, _i32]),
+    "ts_nusc_fov_cloud": (_i32, [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _sz, _vp]),
     "ts_segment_min3": (_i32, [_vp, _i64, _i32, _vp, _i32, _vp, _vp]),
     "ts_stage_keep_flags": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp]),
     "ts_stage_augment": (_i32, [_vp, _i64, _i32, _vp, _vp, _i32, _vp, _vp]),

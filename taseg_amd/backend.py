@@ -1558,6 +1558,61 @@ def tiaf_fov_cloud(points, frame, records, n_samples, crop, aug=None, lo=None):
     return out, out_sample, out_sample32, counts
 
 
+NUSC_CAM_FRAME_BYTES = 584                             # sizeof(TsNuscCamFrame), include/taseg_hip.h
+
+
+def nusc_fov_cloud(points, labels, frame, records, n_samples, pre_keep=None, aug=None, lo=None):
+    """csrc/nusc_tiaf_stage.hip: the nuScenes FOV cloud of a batch as one stable compaction in three launches.  points [n, 4]
+    float32: the clouds of the batch's image keyframes, each in its keyframe's lidar frame; labels [n] int64; pre_keep [n] uint8 /
+    bool (the ego-box byte of the fuse that made `points`) or None; frame [m] int32 ascending: the record of every VIRTUAL row (a
+    point row seen by one camera record); records: uint8 [F, 584] on the device, the TsNuscCamFrame table
+    (taseg_amd.data.nuscenes_tiaf.CAM_FRAME_DTYPE); aug: float64 [B, 8] on the device or None; lo: float32 [B, 3] or None.
+    Returns (out [m, 6], out_labels [m] int64, out_sample [m] int64, out_sample32 [m] int32, counts [B] int64): the survivors in
+    input order in the first sum(counts) rows - the caller reads counts.  No host read here."""
+    L.require_device(points, labels, frame, records, pre_keep, aug, lo)
+    points, frame = _f32(points, "points"), _i32(frame, "frame")
+    if points.ndim != 2 or points.shape[1] != 4:
+        raise TypeError("points must be a float32 [n, 4] tensor")
+    if labels.dtype != torch.int64 or labels.ndim != 1 or labels.shape[0] != points.shape[0]:
+        raise TypeError("labels must be int64 [n]")
+    labels = labels.contiguous()
+    if pre_keep is not None:
+        if pre_keep.dtype == torch.bool:
+            pre_keep = pre_keep.view(torch.uint8) if pre_keep.is_contiguous() else pre_keep.contiguous().view(torch.uint8)
+        if pre_keep.dtype != torch.uint8 or pre_keep.ndim != 1 or pre_keep.shape[0] != points.shape[0]:
+            raise TypeError("pre_keep must be uint8 or bool [n]")
+        pre_keep = pre_keep.contiguous()
+    if records.dtype != torch.uint8 or records.ndim != 2 or records.shape[1] != NUSC_CAM_FRAME_BYTES:
+        raise TypeError("records must be the uint8 [F, 584] camera record table")
+    records = records.contiguous()
+    nb, nf = int(n_samples), records.shape[0]
+    if not 1 <= nb <= TIAF_MAX_SAMPLES or not 1 <= nf <= TIAF_MAX_FRAMES:
+        raise ValueError("nusc_fov_cloud: at most %d samples and %d camera records per call" % (TIAF_MAX_SAMPLES, TIAF_MAX_FRAMES))
+    if frame.ndim != 1:
+        raise ValueError("nusc_fov_cloud: frame must be [m]")
+    if aug is not None:
+        if aug.dtype != torch.float64 or tuple(aug.shape) != (nb, 8):
+            raise TypeError("aug must be float64 [B, 8]")
+        aug = aug.contiguous()
+    if lo is not None:
+        lo = _f32(lo, "lo")
+        if tuple(lo.shape) != (nb, 3):
+            raise ValueError("nusc_fov_cloud: lo must be [B, 3]")
+    dev, n, m = points.device, points.shape[0], frame.shape[0]
+    out = torch.empty((m, 6), dtype=torch.float32, device=dev)
+    out_labels = torch.empty(m, dtype=torch.int64, device=dev)
+    out_sample = torch.empty(m, dtype=torch.int64, device=dev)
+    out_sample32 = torch.empty(m, dtype=torch.int32, device=dev)
+    counts = torch.empty(nb, dtype=torch.int64, device=dev)
+    lib = L.load()
+    ws_bytes = lib.ts_nusc_fov_cloud_workspace_bytes(m, nb)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    L.check(lib.ts_nusc_fov_cloud(L.ptr(points), L.ptr(labels), L.ptr(pre_keep), n, L.ptr(frame), m, L.ptr(records), nf, L.ptr(aug),
+                                  L.ptr(lo), nb, L.ptr(out), L.ptr(out_labels), L.ptr(out_sample), L.ptr(out_sample32), m,
+                                  L.ptr(counts), L.ptr(ws), ws_bytes, L.stream()), "ts_nusc_fov_cloud")
+    return out, out_labels, out_sample, out_sample32, counts
+
+
 def stage_split_voxels(coords4, index, inverse, row_sample, n_samples):
     """csrc/stage.hip: after sparse_quantize on a whole batch -> (vox [m, 4] int32 = coords4[index], offset [B] int32 cumulative
     voxel counts, inverse_local [n] int64 = voxel index inside the point's own sample)."""

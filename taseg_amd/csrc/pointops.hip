@@ -7,6 +7,7 @@
 // All four feature kernels are HBM-bound row movers: a group of lanes owns one
 // row and walks its channels with 16-byte accesses where C % 4 == 0.
 #include "common.h"
+#include "stage_rules.h"
 
 // four consecutive channels of a row stored as float32 or IEEE half; arithmetic is float32 either way and a half
 // result is rounded once at the store (what `.half()` of the float32 result gives)
@@ -413,18 +414,7 @@ __global__ __launch_bounds__(256) void fuse_sweeps_kernel(const float *__restric
 #pragma unroll
       for (int j = 0; j < 3; ++j) q[j] = (float)((double)r[j] + P[9 + j]);
     }
-    if (P[25] != 0.0) {        // p @ B + b : out_j = sum_k p_k B[k][j] + b_j
-      const double d0 = q[0], d1 = q[1], d2 = q[2];
-      const double *B = P + 13;
-      float r[3];
-#pragma unroll
-      for (int j = 0; j < 3; ++j) {
-        const double acc = __builtin_fma(d2, B[6 + j], __builtin_fma(d1, B[3 + j], d0 * B[j]));
-        r[j] = (float)(acc + B[9 + j]);
-      }
-#pragma unroll
-      for (int j = 0; j < 3; ++j) q[j] = r[j];
-    }
+    if (P[25] != 0.0) sr_move(P + 13, q);        // p @ B + b : out_j = sum_k p_k B[k][j] + b_j
     float *o = out + i * 5;
     o[0] = q[0];
     o[1] = q[1];
@@ -502,43 +492,12 @@ __global__ __launch_bounds__(256) void project_cam_kernel(const float4 *__restri
                                                           int crop_top, float row_offset, float2 *__restrict__ pix,
                                                           uint8_t *__restrict__ keep) {
 #pragma clang fp contract(off)
-  double C[57];
-#pragma unroll
-  for (int i = 0; i < 57; ++i) C[i] = cam[i];
-  auto mat = [](const double *M, const double *v, double *o) {
-#pragma unroll
-    for (int j = 0; j < 3; ++j) o[j] = __builtin_fma(M[3 * j + 2], v[2], __builtin_fma(M[3 * j + 1], v[1], M[3 * j] * v[0]));
-  };
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t step = (int64_t)gridDim.x * blockDim.x;
   for (; i < n; i += step) {
     const float4 p = pts[i];
-    double a[3] = {(double)p.x, (double)p.y, (double)p.z}, b[3];
-    mat(C, a, b);
-#pragma unroll
-    for (int j = 0; j < 3; ++j) b[j] = b[j] + C[9 + j];
-    mat(C + 12, b, a);
-#pragma unroll
-    for (int j = 0; j < 3; ++j) a[j] = (a[j] + C[21 + j]) - C[24 + j];
-    mat(C + 27, a, b);
-#pragma unroll
-    for (int j = 0; j < 3; ++j) b[j] = b[j] - C[36 + j];
-    mat(C + 39, b, a);
-    const double depth = a[2];
-    // viewpad @ (x, y, z, 1): the 4th column of the padded intrinsic is zero, fma(0, 1, acc) = acc + 0
-    double q[3];
-#pragma unroll
-    for (int j = 0; j < 3; ++j)
-      q[j] = __builtin_fma(0.0, 1.0, __builtin_fma(C[48 + 3 * j + 2], a[2], __builtin_fma(C[48 + 3 * j + 1], a[1], C[48 + 3 * j] * a[0])));
-    const float u = (float)(q[0] / q[2]), v = (float)(q[1] / q[2]);
-    bool ok = depth > 0.0 && u > 0.f && u < (float)img_w && v > 0.f && v < (float)img_h;
-    int row = 0, col = 0;
-    if (ok) {
-      row = ((int)v) >> 1;           // astype(int), then floor(0.5 * .) written back into the integer array
-      col = ((int)u) >> 1;
-      ok = row >= crop_top;
-      row -= crop_top;
-    }
+    int row, col;
+    const bool ok = sr_project_cam(cam, p.x, p.y, p.z, img_w, img_h, crop_top, row, col);
     keep[i] = ok ? 1 : 0;
     pix[i] = make_float2(__fadd_rn((float)row, row_offset), (float)col);
   }

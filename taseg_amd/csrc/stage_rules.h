@@ -28,6 +28,65 @@ __device__ __forceinline__ double3 sr_rotate_z(double X, double Y, double Z, dou
   return make_double3(rx, ry, rz);
 }
 
+// o = M v for a row-major 3 x 3: dgemm's fused-multiply-add chain in k order, one row of M per output.  (Ptr, here and below: a
+// pointer to const double in whichever address space the caller's table lies.)
+template <typename Ptr>
+__device__ __forceinline__ void sr_mat3(Ptr M, const double (&v)[3], double (&o)[3]) {
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int j = 0; j < 3; ++j) o[j] = __builtin_fma(M[3 * j + 2], v[2], __builtin_fma(M[3 * j + 1], v[1], M[3 * j] * v[0]));
+}
+
+// The camera chain, frustum test, half-resolution pixel and top-row cut of ts_project_cam (nuscenes_ms_mm.py:349-398; the layout of
+// the 57 doubles: include/taseg_hip.h).  row / col are 0 where the frustum test fails; a pixel above the cut rows fails with its
+// row - crop_top < 0 left in `row`.
+template <typename Ptr>
+__device__ __forceinline__ bool sr_project_cam(Ptr C, float x, float y, float z, int img_w, int img_h,
+                                               int crop_top, int &row, int &col) {
+#pragma clang fp contract(off)
+  double a[3] = {(double)x, (double)y, (double)z}, b[3];
+  sr_mat3(C, a, b);
+#pragma unroll
+  for (int j = 0; j < 3; ++j) b[j] = b[j] + C[9 + j];
+  sr_mat3(C + 12, b, a);
+#pragma unroll
+  for (int j = 0; j < 3; ++j) a[j] = (a[j] + C[21 + j]) - C[24 + j];
+  sr_mat3(C + 27, a, b);
+#pragma unroll
+  for (int j = 0; j < 3; ++j) b[j] = b[j] - C[36 + j];
+  sr_mat3(C + 39, b, a);
+  const double depth = a[2];
+  // viewpad @ (x, y, z, 1): the 4th column of the padded intrinsic is zero, fma(0, 1, acc) = acc + 0
+  double q[3];
+#pragma unroll
+  for (int j = 0; j < 3; ++j)
+    q[j] = __builtin_fma(0.0, 1.0, __builtin_fma(C[48 + 3 * j + 2], a[2], __builtin_fma(C[48 + 3 * j + 1], a[1], C[48 + 3 * j] * a[0])));
+  const float u = (float)(q[0] / q[2]), v = (float)(q[1] / q[2]);
+  bool ok = depth > 0.0 && u > 0.f && u < (float)img_w && v > 0.f && v < (float)img_h;
+  row = 0;
+  col = 0;
+  if (ok) {
+    row = ((int)v) >> 1;           // astype(int), then floor(0.5 * .) written back into the integer array
+    col = ((int)u) >> 1;
+    ok = row >= crop_top;
+    row -= crop_top;
+  }
+  return ok;
+}
+
+// p @ B + b of ts_fuse_sweeps (flagB; transform_point, nuscenes_ms.py:348-373): Bb = B[9] row-major, b[3]; out_j = sum_k p_k B[k][j]
+// as dgemm's chain, the translation added in float64, ONE rounding to float32
+template <typename Ptr>
+__device__ __forceinline__ void sr_move(Ptr Bb, float (&q)[3]) {
+#pragma clang fp contract(off)
+  const double d0 = q[0], d1 = q[1], d2 = q[2];
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    const double acc = __builtin_fma(d2, Bb[6 + j], __builtin_fma(d1, Bb[3 + j], d0 * Bb[j]));
+    q[j] = (float)(acc + Bb[9 + j]);
+  }
+}
+
 // Point augmentation (R/tools/utils/common/seg_utils.py:102-166 aug_points_ms, :43-100 aug_points) of one row by one record of
 // TS_AUG_RECORD doubles:
 //   { c, s, scale, tx, ty, tz, bits, flip }   bits: 1 rotate, 2 scale, 4 flip, 8 translate, 16 scale in float32 ; flip: 0 .. 3

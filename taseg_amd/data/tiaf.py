@@ -34,7 +34,7 @@ Reproduced rather than repaired: the TTA scale comes from SCALE_AUG_RANGE (the `
 names an attribute nothing reads); the flip mirrors the full-width image BEFORE the crop, so a wide image shows its right part.
 Not here: file decoding (PNG, .npy semantic maps); IMAGE_JITTER (`color_jitter` needs mmcv's photometric distortion; no golden can
 be made without it); `depth_map_ms` / `lidar_map_ms` (all zeros in the reference); PolarMix / LaserMix inside the TIAF dataset
-(the recipe sets AUGMENT 'none'); the nuScenes TIAF stage (data/nuscenes_tiaf.py has no augmentation).  Bit-exact against the
+(the recipe sets AUGMENT 'none').  The nuScenes recipe's stage: data/nuscenes_tiaf.py.  Bit-exact against the
 reference's dataset code: tests/golden/tiaf_data.npz, tests/golden/tiaf_aug.npz.
 """
 from functools import lru_cache
