@@ -1517,6 +1517,38 @@ def tiaf_image_stack(images, semantic, flips, table, crop):
     return out, out_sem
 
 
+def _fov_cloud_args(who, what, record_bytes, points, frame, records, n_samples, aug, lo, n_outputs):
+    """What tiaf_fov_cloud and nusc_fov_cloud (`who`) check of the arguments they share, and what they allocate: returns the
+    checked (points, frame, records, aug, lo), the outputs [out [m, 6] float32, n_outputs - 2 int64 [m], out_sample32 [m] int32],
+    counts [B] int64 and the workspace of ts_<who>.  `what`: how the texts call a record of record_bytes bytes."""
+    points, frame = _f32(points, "points"), _i32(frame, "frame")
+    if points.ndim != 2 or points.shape[1] != 4:
+        raise TypeError("points must be a float32 [n, 4] tensor")
+    if records.dtype != torch.uint8 or records.ndim != 2 or records.shape[1] != record_bytes:
+        raise TypeError("records must be the uint8 [F, %d] %s table" % (record_bytes, what))
+    records = records.contiguous()
+    nb, nf = int(n_samples), records.shape[0]
+    if not 1 <= nb <= TIAF_MAX_SAMPLES or not 1 <= nf <= TIAF_MAX_FRAMES:
+        raise ValueError("%s: at most %d samples and %d %ss per call" % (who, TIAF_MAX_SAMPLES, TIAF_MAX_FRAMES, what))
+    if frame.ndim != 1:
+        raise ValueError("%s: frame must be [m]" % who)
+    if aug is not None:
+        if aug.dtype != torch.float64 or tuple(aug.shape) != (nb, 8):
+            raise TypeError("aug must be float64 [B, 8]")
+        aug = aug.contiguous()
+    if lo is not None:
+        lo = _f32(lo, "lo")
+        if tuple(lo.shape) != (nb, 3):
+            raise ValueError("%s: lo must be [B, 3]" % who)
+    dev, m = points.device, frame.shape[0]
+    outs = [torch.empty((m, 6), dtype=torch.float32, device=dev)]
+    outs += [torch.empty(m, dtype=torch.int64, device=dev) for _ in range(n_outputs - 2)]
+    outs.append(torch.empty(m, dtype=torch.int32, device=dev))
+    counts = torch.empty(nb, dtype=torch.int64, device=dev)
+    ws = torch.empty(getattr(L.load(), "ts_%s_workspace_bytes" % who)(m, nb), dtype=torch.uint8, device=dev)
+    return (points, frame, records, aug, lo), outs, counts, ws
+
+
 def tiaf_fov_cloud(points, frame, records, n_samples, crop, aug=None, lo=None):
     """csrc/tiaf_stage.hip: the FOV cloud of a batch as one stable compaction in three launches.  points [n, 4] float32: the rows of
     every camera frame of every sample, sample-major, newest frame first; frame [m] int32 ascending: the record of every VIRTUAL
@@ -1525,37 +1557,13 @@ def tiaf_fov_cloud(points, frame, records, n_samples, crop, aug=None, lo=None):
     Returns (out [m, 6], out_sample [m] int64, out_sample32 [m] int32, counts [B] int64): the survivors in input order in the first
     sum(counts) rows - the caller reads counts.  No host read here."""
     L.require_device(points, frame, records, aug, lo)
-    points, frame = _f32(points, "points"), _i32(frame, "frame")
-    if points.ndim != 2 or points.shape[1] != 4:
-        raise TypeError("points must be a float32 [n, 4] tensor")
-    if records.dtype != torch.uint8 or records.ndim != 2 or records.shape[1] != TIAF_FRAME_BYTES:
-        raise TypeError("records must be the uint8 [F, 256] frame table")
-    records = records.contiguous()
-    nb, nf = int(n_samples), records.shape[0]
-    if not 1 <= nb <= TIAF_MAX_SAMPLES or not 1 <= nf <= TIAF_MAX_FRAMES:
-        raise ValueError("tiaf_fov_cloud: at most %d samples and %d frame records per call" % (TIAF_MAX_SAMPLES, TIAF_MAX_FRAMES))
-    if frame.ndim != 1:
-        raise ValueError("tiaf_fov_cloud: frame must be [m]")
-    if aug is not None:
-        if aug.dtype != torch.float64 or tuple(aug.shape) != (nb, 8):
-            raise TypeError("aug must be float64 [B, 8]")
-        aug = aug.contiguous()
-    if lo is not None:
-        lo = _f32(lo, "lo")
-        if tuple(lo.shape) != (nb, 3):
-            raise ValueError("tiaf_fov_cloud: lo must be [B, 3]")
-    dev, n, m = points.device, points.shape[0], frame.shape[0]
-    out = torch.empty((m, 6), dtype=torch.float32, device=dev)
-    out_sample = torch.empty(m, dtype=torch.int64, device=dev)
-    out_sample32 = torch.empty(m, dtype=torch.int32, device=dev)
-    counts = torch.empty(nb, dtype=torch.int64, device=dev)
-    lib = L.load()
-    ws_bytes = lib.ts_tiaf_fov_cloud_workspace_bytes(m, nb)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    L.check(lib.ts_tiaf_fov_cloud(L.ptr(points), n, L.ptr(frame), m, L.ptr(records), nf, L.ptr(aug), L.ptr(lo), nb, int(crop[0]),
-                                  int(crop[1]), L.ptr(out), L.ptr(out_sample), L.ptr(out_sample32), m, L.ptr(counts), L.ptr(ws),
-                                  ws_bytes, L.stream()), "ts_tiaf_fov_cloud")
-    return out, out_sample, out_sample32, counts
+    (points, frame, records, aug, lo), outs, counts, ws = _fov_cloud_args("tiaf_fov_cloud", "frame record", TIAF_FRAME_BYTES, points,
+                                                                          frame, records, n_samples, aug, lo, 3)
+    m = frame.shape[0]
+    L.check(L.load().ts_tiaf_fov_cloud(L.ptr(points), points.shape[0], L.ptr(frame), m, L.ptr(records), records.shape[0], L.ptr(aug),
+                                       L.ptr(lo), counts.shape[0], int(crop[0]), int(crop[1]), *map(L.ptr, outs), m, L.ptr(counts),
+                                       L.ptr(ws), ws.shape[0], L.stream()), "ts_tiaf_fov_cloud")
+    return (*outs, counts)
 
 
 NUSC_CAM_FRAME_BYTES = 584                             # sizeof(TsNuscCamFrame), include/taseg_hip.h
@@ -1570,9 +1578,8 @@ def nusc_fov_cloud(points, labels, frame, records, n_samples, pre_keep=None, aug
     Returns (out [m, 6], out_labels [m] int64, out_sample [m] int64, out_sample32 [m] int32, counts [B] int64): the survivors in
     input order in the first sum(counts) rows - the caller reads counts.  No host read here."""
     L.require_device(points, labels, frame, records, pre_keep, aug, lo)
-    points, frame = _f32(points, "points"), _i32(frame, "frame")
-    if points.ndim != 2 or points.shape[1] != 4:
-        raise TypeError("points must be a float32 [n, 4] tensor")
+    (points, frame, records, aug, lo), outs, counts, ws = _fov_cloud_args("nusc_fov_cloud", "camera record", NUSC_CAM_FRAME_BYTES,
+                                                                          points, frame, records, n_samples, aug, lo, 4)
     if labels.dtype != torch.int64 or labels.ndim != 1 or labels.shape[0] != points.shape[0]:
         raise TypeError("labels must be int64 [n]")
     labels = labels.contiguous()
@@ -1582,35 +1589,11 @@ def nusc_fov_cloud(points, labels, frame, records, n_samples, pre_keep=None, aug
         if pre_keep.dtype != torch.uint8 or pre_keep.ndim != 1 or pre_keep.shape[0] != points.shape[0]:
             raise TypeError("pre_keep must be uint8 or bool [n]")
         pre_keep = pre_keep.contiguous()
-    if records.dtype != torch.uint8 or records.ndim != 2 or records.shape[1] != NUSC_CAM_FRAME_BYTES:
-        raise TypeError("records must be the uint8 [F, 584] camera record table")
-    records = records.contiguous()
-    nb, nf = int(n_samples), records.shape[0]
-    if not 1 <= nb <= TIAF_MAX_SAMPLES or not 1 <= nf <= TIAF_MAX_FRAMES:
-        raise ValueError("nusc_fov_cloud: at most %d samples and %d camera records per call" % (TIAF_MAX_SAMPLES, TIAF_MAX_FRAMES))
-    if frame.ndim != 1:
-        raise ValueError("nusc_fov_cloud: frame must be [m]")
-    if aug is not None:
-        if aug.dtype != torch.float64 or tuple(aug.shape) != (nb, 8):
-            raise TypeError("aug must be float64 [B, 8]")
-        aug = aug.contiguous()
-    if lo is not None:
-        lo = _f32(lo, "lo")
-        if tuple(lo.shape) != (nb, 3):
-            raise ValueError("nusc_fov_cloud: lo must be [B, 3]")
-    dev, n, m = points.device, points.shape[0], frame.shape[0]
-    out = torch.empty((m, 6), dtype=torch.float32, device=dev)
-    out_labels = torch.empty(m, dtype=torch.int64, device=dev)
-    out_sample = torch.empty(m, dtype=torch.int64, device=dev)
-    out_sample32 = torch.empty(m, dtype=torch.int32, device=dev)
-    counts = torch.empty(nb, dtype=torch.int64, device=dev)
-    lib = L.load()
-    ws_bytes = lib.ts_nusc_fov_cloud_workspace_bytes(m, nb)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    L.check(lib.ts_nusc_fov_cloud(L.ptr(points), L.ptr(labels), L.ptr(pre_keep), n, L.ptr(frame), m, L.ptr(records), nf, L.ptr(aug),
-                                  L.ptr(lo), nb, L.ptr(out), L.ptr(out_labels), L.ptr(out_sample), L.ptr(out_sample32), m,
-                                  L.ptr(counts), L.ptr(ws), ws_bytes, L.stream()), "ts_nusc_fov_cloud")
-    return out, out_labels, out_sample, out_sample32, counts
+    m = frame.shape[0]
+    L.check(L.load().ts_nusc_fov_cloud(L.ptr(points), L.ptr(labels), L.ptr(pre_keep), points.shape[0], L.ptr(frame), m,
+                                       L.ptr(records), records.shape[0], L.ptr(aug), L.ptr(lo), counts.shape[0], *map(L.ptr, outs), m,
+                                       L.ptr(counts), L.ptr(ws), ws.shape[0], L.stream()), "ts_nusc_fov_cloud")
+    return (*outs, counts)
 
 
 def stage_split_voxels(coords4, index, inverse, row_sample, n_samples):

@@ -4,38 +4,55 @@
 // semantickitti/semantickitti_voxel_ms.py:121-124 - `point_ms[(point_ms[:, :3] >= point[:, :3].min(0)).all(1)]`.
 //
 // After a mix the current scan is no prefix of the fused cloud, so EVERY fused row is compared with its sample's minimum: the
-// three passes of csrc/compact.h with the clamp of csrc/stage_rules.h as the row rule, one tally per sample.
+// one-cloud driver of csrc/compact.h (cp_compact) with the clamp of csrc/stage_rules.h as the row rule, one tally per sample.
 #include "compact.h"
 #include "stage_rules.h"
 
 namespace {
 
-__device__ __forceinline__ bool cc_keeps(float x, float y, float z, const float *__restrict__ lo, int s, int n_samples) {
-  return s >= 0 && s < n_samples && sr_clamp_keeps(x, y, z, lo, s);
+// the strided store: (x, y, z) as pass 3 read them, the further columns from the input row (q and o never overlap: as parameters
+// they can say so, as members of a struct passed by value they cannot, and every load of q[k] would wait for the store before it)
+__device__ __forceinline__ void cc_copy_row(const float *__restrict__ q, float *__restrict__ o, const float4 &p, int f) {
+  o[0] = p.x;
+  o[1] = p.y;
+  o[2] = p.z;
+  for (int k = 3; k < f; ++k) o[k] = q[k];
 }
 
-__global__ __launch_bounds__(CP_ROWS) void cc_count_kernel(const float *__restrict__ pts, int64_t n, int f,
-                                                           const int *__restrict__ sample, const float *__restrict__ lo,
-                                                           int n_samples, int *__restrict__ blk_cnt,
-                                                           int *__restrict__ blk_tally) {
-  __shared__ int wcnt[CP_WAVES];
-  __shared__ int scnt[CP_WAVES][TS_WAVE];
-  const int64_t i = (int64_t)blockIdx.x * CP_ROWS + threadIdx.x;
-  cp_tally_clear<1>(scnt);
-  __syncthreads();
-  int s = -1;
-  bool keep[1] = {false};
-  if (i < n) {
-    const float *p = pts + i * f;
-    s = sample[i];
-    keep[0] = cc_keeps(p[0], p[1], p[2], lo, s, n_samples);
+// VEC4: rows of four floats, 16-byte aligned - one 16-byte load and one 16-byte store per row, in both passes
+template <bool VEC4>
+struct CcRule : CpRule {
+  typedef float4 Row;
+  const float *pts;
+  const int64_t *lab;
+  const int *sample;
+  const float *lo;
+  float *out;
+  int64_t *out_lab;
+  int f;
+
+  __device__ __forceinline__ bool keeps(int64_t i, bool in, float4 &p, int *s) const {
+    *s = -1;
+    if (!in) return false;
+    *s = sample[i];
+    if (VEC4) {
+      p = reinterpret_cast<const float4 *>(pts)[i];
+    } else {
+      const float *q = pts + i * f;
+      p = make_float4(q[0], q[1], q[2], 0.f);
+    }
+    return *s >= 0 && *s < n_samples && sr_clamp_keeps(p.x, p.y, p.z, lo, *s);
   }
-  cp_ballot(keep[0], wcnt);
-  cp_tally_wave<1>(s, keep, scnt);
-  __syncthreads();
-  if (threadIdx.x == 0) blk_cnt[blockIdx.x] = cp_block_sum(wcnt);
-  cp_tally_store<1>(scnt, n_samples, blk_tally);
-}
+
+  __device__ __forceinline__ void store(int64_t dst, int64_t i, const float4 &p) const {
+    if (VEC4) {
+      reinterpret_cast<float4 *>(out)[dst] = p;
+    } else {
+      cc_copy_row(pts + i * f, out + dst * f, p, f);
+    }
+    out_lab[dst] = lab[i];
+  }
+};
 
 // blocks 0 .. n_clouds - 1: offs [n_clouds][n_blocks] = exclusive scans of blk_cnt, one block per cloud - every thread sums a
 // contiguous chunk, the 256 chunk sums are scanned in LDS, every thread writes its chunk's running sums (a single wave walking
@@ -77,48 +94,6 @@ __global__ __launch_bounds__(256) void cp_scan_kernel(int n_blocks, int n_clouds
   }
 }
 
-template <bool VEC4>
-__global__ __launch_bounds__(CP_ROWS) void cc_scatter_kernel(const float *__restrict__ pts, int64_t n, int f,
-                                                             const int64_t *__restrict__ lab, const int *__restrict__ sample,
-                                                             const float *__restrict__ lo, int n_samples,
-                                                             const int *__restrict__ offs, float *__restrict__ out,
-                                                             int64_t *__restrict__ out_lab, int64_t *__restrict__ out_sample,
-                                                             int *__restrict__ out_sample32) {
-  __shared__ int wcnt[CP_WAVES];
-  const int64_t i = (int64_t)blockIdx.x * CP_ROWS + threadIdx.x;
-  int s = -1;
-  bool keep = false;
-  float4 p = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (i < n) {
-    s = sample[i];
-    if (VEC4) {
-      p = reinterpret_cast<const float4 *>(pts)[i];
-    } else {
-      const float *q = pts + i * f;
-      p = make_float4(q[0], q[1], q[2], 0.f);
-    }
-    keep = cc_keeps(p.x, p.y, p.z, lo, s, n_samples);       // the comparison of pass 1 on the same bits
-  }
-  const CpBallot b = cp_ballot(keep, wcnt);
-  __syncthreads();
-  if (!keep) return;
-  const int64_t dst = offs[blockIdx.x] + cp_rank(b, wcnt);
-  if (dst >= n) return;                                     // (cannot happen: survivors <= rows; bounds every store)
-  if (VEC4) {
-    reinterpret_cast<float4 *>(out)[dst] = p;
-  } else {
-    const float *q = pts + i * f;
-    float *o = out + dst * f;
-    o[0] = p.x;
-    o[1] = p.y;
-    o[2] = p.z;
-    for (int k = 3; k < f; ++k) o[k] = q[k];
-  }
-  out_lab[dst] = lab[i];
-  out_sample[dst] = s;
-  out_sample32[dst] = s;
-}
-
 }  // namespace
 
 void ts_compact_scan(const CpWorkspace &c, int n_blocks, int n_clouds, int n_tallies, int64_t *counts, hipStream_t stream) {
@@ -126,39 +101,22 @@ void ts_compact_scan(const CpWorkspace &c, int n_blocks, int n_clouds, int n_tal
                                                                                         c.blk_tally, c.offs, counts);
 }
 
-extern "C" size_t ts_stage_clamp_compact_workspace_bytes(int64_t n, int32_t n_samples) {
-  return cp_carve(nullptr, ts_cdiv(std::max<int64_t>(n, 0), CP_ROWS), 1, std::max(n_samples, 0)).bytes;
-}
+extern "C" size_t ts_stage_clamp_compact_workspace_bytes(int64_t n, int32_t n_samples) { return cp_compact_bytes(n, n_samples); }
 
 extern "C" int ts_stage_clamp_compact(const float *points, int64_t n, int32_t point_stride, const int64_t *labels,
                                       const int32_t *sample, const float *lo, int32_t n_samples, float *out, int64_t *out_labels,
                                       int64_t *out_sample, int32_t *out_sample32, int64_t *counts, void *ws, size_t ws_bytes,
                                       ts_stream_t stream) {
-  static_assert(TS_CLAMP_MAX_SAMPLES == TS_WAVE, "cc_count_kernel keeps one LDS counter per (wave, sample)");
+  static_assert(TS_CLAMP_MAX_SAMPLES == TS_WAVE, "cp_count_kernel keeps one LDS counter per (wave, sample)");
   TS_REQUIRE(n >= 0 && n < (int64_t)1 << 30 && point_stride >= 3 && n_samples >= 1 && n_samples <= TS_CLAMP_MAX_SAMPLES,
              TS_ERR_INVALID_ARGUMENT, "ts_stage_clamp_compact: bad sizes");
   TS_REQUIRE(lo && counts && ws && ((uintptr_t)ws & 3) == 0, TS_ERR_INVALID_ARGUMENT, "ts_stage_clamp_compact: null pointer");
   TS_REQUIRE(n == 0 || (points && labels && sample && out && out_labels && out_sample && out_sample32), TS_ERR_INVALID_ARGUMENT,
              "ts_stage_clamp_compact: null pointer");
-  const int64_t n_blocks = ts_cdiv(n, CP_ROWS);
-  const CpWorkspace c = cp_carve(ws, n_blocks, 1, n_samples);
-  TS_REQUIRE(ws_bytes >= c.bytes, TS_ERR_INVALID_ARGUMENT, "ts_stage_clamp_compact: workspace too small");
-  hipStream_t st = (hipStream_t)stream;
-  if (n_blocks > 0) {
-    cc_count_kernel<<<(int)n_blocks, CP_ROWS, 0, st>>>(points, n, point_stride, sample, lo, n_samples, c.blk_cnt, c.blk_tally);
-    TS_CHECK_LAUNCH("ts_stage_clamp_compact (count)");
-  }
-  ts_compact_scan(c, (int)n_blocks, 1, n_samples, counts, st);
-  TS_CHECK_LAUNCH("ts_stage_clamp_compact (scan)");
-  if (n_blocks > 0) {
-    if (point_stride == 4 && ((((uintptr_t)points) | ((uintptr_t)out)) & 15) == 0) {
-      cc_scatter_kernel<true><<<(int)n_blocks, CP_ROWS, 0, st>>>(points, n, point_stride, labels, sample, lo, n_samples, c.offs, out,
-                                                                 out_labels, out_sample, out_sample32);
-    } else {
-      cc_scatter_kernel<false><<<(int)n_blocks, CP_ROWS, 0, st>>>(points, n, point_stride, labels, sample, lo, n_samples, c.offs,
-                                                                  out, out_labels, out_sample, out_sample32);
-    }
-    TS_CHECK_LAUNCH("ts_stage_clamp_compact (scatter)");
-  }
-  return TS_OK;
+  const CpRule base = {n, n, n_samples, out_sample, out_sample32};          // (survivors <= rows: the outputs hold n rows)
+  if (point_stride == 4 && ((((uintptr_t)points) | ((uintptr_t)out)) & 15) == 0)
+    return cp_compact(CcRule<true>{base, points, labels, sample, lo, out, out_labels, point_stride}, "ts_stage_clamp_compact", counts,
+                      ws, ws_bytes, (hipStream_t)stream);
+  return cp_compact(CcRule<false>{base, points, labels, sample, lo, out, out_labels, point_stride}, "ts_stage_clamp_compact", counts,
+                    ws, ws_bytes, (hipStream_t)stream);
 }

@@ -4,8 +4,8 @@
 // (`aug_points_rgb_ms` on the FOV cloud), :133-135 (its clamp).
 //
 //   ts_nusc_fov_cloud     ego-box byte -> PAINT_DIST -> camera chain, frustum, half-resolution pixel, top rows cut -> move ->
-//                         augmentation -> clamp per virtual row, the survivors as one stable compaction: the three passes of
-//                         csrc/compact.h with nf_row as the row rule, one tally per sample; the projection, the move, the
+//                         augmentation -> clamp per virtual row, the survivors as one stable compaction: the one-cloud driver of
+//                         csrc/compact.h (cp_compact) with nf_wave / nf_row as the row rule, one tally per sample; the projection, the move, the
 //                         augmentation and the clamp inside nf_row are those of csrc/stage_rules.h.
 //
 // A record carries 69 doubles.  Read through a per-lane pointer they would occupy 138 VGPRs of every lane; the rows of a record
@@ -16,7 +16,11 @@
 
 namespace {
 
-struct NfRule {
+struct NfRule : CpRule {
+  struct Row {
+    float o[5];                    // x, y, z, row + row_offset, col
+    int64_t srow;                  // the point row it read: store takes the intensity and the label from there
+  };
   const float4 *pts;
   const int64_t *labels;
   const unsigned char *pre_keep;   // [n_points] or NULL
@@ -24,14 +28,25 @@ struct NfRule {
   const TsNuscCamFrame *rec;
   const double *aug;               // [n_samples, TS_AUG_RECORD] or NULL
   const float *lo;                 // [n_samples, 3] or NULL
-  int64_t n_rows, n_points;
-  int n_frames, n_samples;
+  float *out;                      // [capacity, 6]
+  int64_t *out_labels;             // [capacity]
+  int64_t n_points;
+  int n_frames;
+
+  __device__ __forceinline__ bool keeps(int64_t i, bool in, Row &row, int *sample) const;
+  __device__ __forceinline__ void store(int64_t dst, int64_t, const Row &row) const {
+    float2 *d = reinterpret_cast<float2 *>(out + dst * 6);    // rows of 24 bytes: 8-byte aligned
+    d[0] = make_float2(row.o[0], row.o[1]);
+    d[1] = make_float2(row.o[2], pts[row.srow].w);            // (a survivor's srow is in [0, n_points))
+    d[2] = make_float2(row.o[3], row.o[4]);
+    out_labels[dst] = labels[row.srow];
+  }
 };
 
 typedef const __attribute__((address_space(4))) TsNuscCamFrame *NfRecord;      // a record read through scalar loads
 
 // Does virtual row i of record *R (a wave-uniform pointer) survive, and as which output row?  o = (x, y, z, row + row_offset,
-// col), *srow the point row it read - the scatter takes the intensity and the label from there.  Both passes call it, so pass 3 decides on the bits pass 1 counted.
+// col), *srow the point row it read - NfRule::store takes the intensity and the label from there.
 __device__ __forceinline__ bool nf_row(const NfRule &r, NfRecord R, int64_t i, float (&o)[5], int64_t *srow) {
 #pragma clang fp contract(off)  // (build.py compiles this file with -ffp-contract=off, as pointops.hip: __fmul_rn / __fadd_rn keep
                                 // their roundings)
@@ -85,59 +100,20 @@ __device__ __forceinline__ bool nf_wave(const NfRule &r, int64_t i, bool in, flo
   return keep;
 }
 
-__global__ __launch_bounds__(CP_ROWS) void nf_count_kernel(NfRule r, int *__restrict__ blk_cnt, int *__restrict__ blk_tally) {
-  __shared__ int wcnt[CP_WAVES];
-  __shared__ int scnt[CP_WAVES][TS_WAVE];
-  const int64_t i = (int64_t)blockIdx.x * CP_ROWS + threadIdx.x;
-  cp_tally_clear<1>(scnt);
-  __syncthreads();
-  int s;
-  int64_t srow;
-  float o[5];
-  bool keep[1];
-  keep[0] = nf_wave(r, i, i < r.n_rows, o, &s, &srow);
-  cp_ballot(keep[0], wcnt);
-  cp_tally_wave<1>(s, keep, scnt);
-  __syncthreads();
-  if (threadIdx.x == 0) blk_cnt[blockIdx.x] = cp_block_sum(wcnt);
-  cp_tally_store<1>(scnt, r.n_samples, blk_tally);
-}
-
-__global__ __launch_bounds__(CP_ROWS) void nf_scatter_kernel(NfRule r, const int *__restrict__ offs, float *__restrict__ out,
-                                                             int64_t *__restrict__ out_labels, int64_t *__restrict__ out_sample,
-                                                             int *__restrict__ out_sample32, int64_t capacity) {
-  __shared__ int wcnt[CP_WAVES];
-  const int64_t i = (int64_t)blockIdx.x * CP_ROWS + threadIdx.x;
-  int s;
-  int64_t srow;
-  float o[5];
-  const bool keep = nf_wave(r, i, i < r.n_rows, o, &s, &srow);      // the decision of pass 1 on the same bits
-  const CpBallot b = cp_ballot(keep, wcnt);
-  __syncthreads();
-  if (!keep) return;
-  const int64_t dst = offs[blockIdx.x] + cp_rank(b, wcnt);
-  if (dst < 0 || dst >= capacity) return;                   // (cannot happen: survivors <= rows <= capacity; bounds every store)
-  float2 *d = reinterpret_cast<float2 *>(out + dst * 6);    // rows of 24 bytes: 8-byte aligned
-  d[0] = make_float2(o[0], o[1]);
-  d[1] = make_float2(o[2], r.pts[srow].w);                  // (a survivor's srow is in [0, n_points))
-  d[2] = make_float2(o[3], o[4]);
-  out_labels[dst] = r.labels[srow];
-  out_sample[dst] = s;
-  out_sample32[dst] = s;
+__device__ __forceinline__ bool NfRule::keeps(int64_t i, bool in, Row &row, int *sample) const {
+  return nf_wave(*this, i, in, row.o, sample, &row.srow);
 }
 
 }  // namespace
 
-extern "C" size_t ts_nusc_fov_cloud_workspace_bytes(int64_t n_rows, int32_t n_samples) {
-  return cp_carve(nullptr, ts_cdiv(std::max<int64_t>(n_rows, 0), CP_ROWS), 1, std::max(n_samples, 0)).bytes;
-}
+extern "C" size_t ts_nusc_fov_cloud_workspace_bytes(int64_t n_rows, int32_t n_samples) { return cp_compact_bytes(n_rows, n_samples); }
 
 extern "C" int ts_nusc_fov_cloud(const float *points, const int64_t *labels, const uint8_t *pre_keep, int64_t n_points,
                                  const int32_t *frame, int64_t n_rows, const TsNuscCamFrame *records, int32_t n_frames,
                                  const double *aug, const float *lo, int32_t n_samples, float *out, int64_t *out_labels,
                                  int64_t *out_sample, int32_t *out_sample32, int64_t capacity, int64_t *counts, void *ws,
                                  size_t ws_bytes, ts_stream_t stream) {
-  static_assert(TS_TIAF_MAX_SAMPLES == TS_WAVE, "nf_count_kernel keeps one LDS counter per (wave, sample)");
+  static_assert(TS_TIAF_MAX_SAMPLES == TS_WAVE, "cp_count_kernel keeps one LDS counter per (wave, sample)");
   static_assert(sizeof(TsNuscCamFrame) == 584, "the camera record is 584 bytes (taseg_amd/data/nuscenes_tiaf.py CAM_FRAME_DTYPE)");
   TS_REQUIRE(n_points >= 0 && n_rows >= 0 && n_rows < (int64_t)1 << 30 && n_points < (int64_t)1 << 30 && n_frames >= 1 &&
                  n_frames <= TS_TIAF_MAX_FRAMES && n_samples >= 1 && n_samples <= TS_TIAF_MAX_SAMPLES && capacity >= n_rows,
@@ -150,20 +126,7 @@ extern "C" int ts_nusc_fov_cloud(const float *points, const int64_t *labels, con
   TS_REQUIRE((((uintptr_t)points) & 15) == 0 && (((uintptr_t)out) & 7) == 0 && (((uintptr_t)labels) & 7) == 0 &&
                  (((uintptr_t)out_labels) & 7) == 0,
              TS_ERR_INVALID_ARGUMENT, "ts_nusc_fov_cloud: points must be 16-byte, out and the labels 8-byte aligned");
-  const int64_t n_blocks = ts_cdiv(n_rows, CP_ROWS);
-  const CpWorkspace c = cp_carve(ws, n_blocks, 1, n_samples);
-  TS_REQUIRE(ws_bytes >= c.bytes, TS_ERR_INVALID_ARGUMENT, "ts_nusc_fov_cloud: workspace too small");
-  hipStream_t st = (hipStream_t)stream;
-  const NfRule r = {(const float4 *)points, labels, pre_keep, frame, records, aug, lo, n_rows, n_points, n_frames, n_samples};
-  if (n_blocks > 0) {
-    nf_count_kernel<<<(int)n_blocks, CP_ROWS, 0, st>>>(r, c.blk_cnt, c.blk_tally);
-    TS_CHECK_LAUNCH("ts_nusc_fov_cloud (count)");
-  }
-  ts_compact_scan(c, (int)n_blocks, 1, n_samples, counts, st);
-  TS_CHECK_LAUNCH("ts_nusc_fov_cloud (scan)");
-  if (n_blocks > 0) {
-    nf_scatter_kernel<<<(int)n_blocks, CP_ROWS, 0, st>>>(r, c.offs, out, out_labels, out_sample, out_sample32, capacity);
-    TS_CHECK_LAUNCH("ts_nusc_fov_cloud (scatter)");
-  }
-  return TS_OK;
+  const NfRule r = {{n_rows, capacity, n_samples, out_sample, out_sample32}, (const float4 *)points, labels, pre_keep, frame, records,
+                    aug, lo, out, out_labels, n_points, n_frames};
+  return cp_compact(r, "ts_nusc_fov_cloud", counts, ws, ws_bytes, (hipStream_t)stream);
 }

@@ -270,12 +270,10 @@ extern "C" int ts_devoxelize_backward(const float *grad_out, const int32_t *idx,
 }
 
 // ------------------------------------------------------------------ multi-scan pose fuse
-// new = sum_k hp[k] * pose^T[k][:]  (k = 0..3, summed in k order like np.sum(axis=1));
-// out = sum_k (new - t0)[k] * R0[k][:]  (k = 0..2).  float32 throughout.
+// sr_fuse_pose (csrc/stage_rules.h) per row.  float32 throughout.
 __global__ __launch_bounds__(256) void fuse_scan_kernel(const float4 *__restrict__ pts, int64_t n,
                                                         const float *__restrict__ pose0,
                                                         const float *__restrict__ pose, float4 *__restrict__ out) {
-#pragma clang fp contract(off)  // numpy multiplies, then adds: no fused multiply-add anywhere below
   // 32 wave-uniform scalars
   float P[16], Q[16];
 #pragma unroll
@@ -287,31 +285,12 @@ __global__ __launch_bounds__(256) void fuse_scan_kernel(const float4 *__restrict
   int64_t step = (int64_t)gridDim.x * blockDim.x;
   for (; i < n; i += step) {
     float4 p = pts[i];
-    float h[4] = {p.x, p.y, p.z, 1.0f};
-    float nw[3];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      // (hpoints[:, k, None] * pose.T[k, j]) summed over k;  pose.T[k][j] = pose[j][k]
-      float s = __fmul_rn(h[0], P[j * 4 + 0]);
-      s = __fadd_rn(s, __fmul_rn(h[1], P[j * 4 + 1]));
-      s = __fadd_rn(s, __fmul_rn(h[2], P[j * 4 + 2]));
-      s = __fadd_rn(s, __fmul_rn(h[3], P[j * 4 + 3]));
-      nw[j] = __fsub_rn(s, Q[j * 4 + 3]);  // - pose0[:3, 3]
-    }
-    float o[3];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      // sum_k new[k] * pose0[:3, :3][k][j]
-      float s = __fmul_rn(nw[0], Q[0 * 4 + j]);
-      s = __fadd_rn(s, __fmul_rn(nw[1], Q[1 * 4 + j]));
-      s = __fadd_rn(s, __fmul_rn(nw[2], Q[2 * 4 + j]));
-      o[j] = s;
-    }
-    out[i] = make_float4(o[0], o[1], o[2], p.w);
+    sr_fuse_pose(P, Q, p.x, p.y, p.z);
+    out[i] = p;
   }
 }
 
-// All history scans of a sample in one launch: point i uses poses[scan_idx[i]].  Same arithmetic, same order.
+// All history scans of a sample in one launch: point i uses poses[scan_idx[i]].  Same rule.
 // PER_SCAN: pose0 is a table too (pose0[scan_idx[i]]) - the history scans of a whole BATCH of samples in one launch, every scan
 // with the current-frame pose of its own sample.
 template <bool PER_SCAN>
@@ -320,39 +299,21 @@ __global__ __launch_bounds__(256) void fuse_scans_kernel(const float4 *__restric
                                                          const float *__restrict__ pose0,
                                                          const float *__restrict__ poses, int n_scans,
                                                          float4 *__restrict__ out) {
-#pragma clang fp contract(off)
   float Q[16];
 #pragma unroll
   for (int i = 0; i < 16; ++i) Q[i] = PER_SCAN ? 0.f : pose0[i];
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   int64_t step = (int64_t)gridDim.x * blockDim.x;
   for (; i < n; i += step) {
-    const float4 p = pts[i];
+    float4 p = pts[i];
     const int sidx = min(max(scan_idx[i], 0), n_scans - 1);
     const float *P = poses + 16 * sidx;
     if (PER_SCAN) {
 #pragma unroll
       for (int q = 0; q < 16; ++q) Q[q] = pose0[16 * sidx + q];
     }
-    const float h[4] = {p.x, p.y, p.z, 1.0f};
-    float nw[3];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      float s = __fmul_rn(h[0], P[j * 4 + 0]);
-      s = __fadd_rn(s, __fmul_rn(h[1], P[j * 4 + 1]));
-      s = __fadd_rn(s, __fmul_rn(h[2], P[j * 4 + 2]));
-      s = __fadd_rn(s, __fmul_rn(h[3], P[j * 4 + 3]));
-      nw[j] = __fsub_rn(s, Q[j * 4 + 3]);
-    }
-    float o[3];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      float s = __fmul_rn(nw[0], Q[0 * 4 + j]);
-      s = __fadd_rn(s, __fmul_rn(nw[1], Q[1 * 4 + j]));
-      s = __fadd_rn(s, __fmul_rn(nw[2], Q[2 * 4 + j]));
-      o[j] = s;
-    }
-    out[i] = make_float4(o[0], o[1], o[2], p.w);
+    sr_fuse_pose(P, Q, p.x, p.y, p.z);
+    out[i] = p;
   }
 }
 
@@ -441,7 +402,6 @@ __global__ __launch_bounds__(256) void project_fov_kernel(const float4 *__restri
                                                           const double *__restrict__ proj, int img_w, int img_h,
                                                           int crop_h, int crop_w, float row_offset,
                                                           float2 *__restrict__ pix, uint8_t *__restrict__ keep) {
-#pragma clang fp contract(off)
   double P[12];
 #pragma unroll
   for (int i = 0; i < 12; ++i) P[i] = proj[i];
@@ -449,19 +409,8 @@ __global__ __launch_bounds__(256) void project_fov_kernel(const float4 *__restri
   const int64_t step = (int64_t)gridDim.x * blockDim.x;
   for (; i < n; i += step) {
     const float4 p = pts[i];
-    const double x = p.x, y = p.y, z = p.z;
-    double uvz[3];
-#pragma unroll
-    for (int j = 0; j < 3; ++j)      // sum_k P[j][k] * (x, y, z, 1)[k], accumulated with FMAs in k order
-      uvz[j] = __builtin_fma(P[4 * j + 3], 1.0, __builtin_fma(P[4 * j + 2], z, __builtin_fma(P[4 * j + 1], y, P[4 * j] * x)));
-    const double u = uvz[0] / uvz[2], v = uvz[1] / uvz[2];
-    bool ok = p.x > 0.f && u > 0.0 && v > 0.0 && u < (double)img_w && v < (double)img_h;
-    int row = 0, col = 0;
-    if (ok) {
-      row = (int)v;                  // astype(int): truncation
-      col = (int)u;
-      ok = row < crop_h && col < crop_w;
-    }
+    int row, col;
+    const bool ok = sr_project_fov(P, p.x, p.y, p.z, img_w, img_h, row, col) && row < crop_h && col < crop_w;
     keep[i] = ok ? 1 : 0;
     pix[i] = make_float2(__fadd_rn((float)row, row_offset), (float)col);
   }

@@ -37,6 +37,58 @@ __device__ __forceinline__ void sr_mat3(Ptr M, const double (&v)[3], double (&o)
   for (int j = 0; j < 3; ++j) o[j] = __builtin_fma(M[3 * j + 2], v[2], __builtin_fma(M[3 * j + 1], v[1], M[3 * j] * v[0]));
 }
 
+// The multi-scan pose fuse of ts_fuse_scan (semantickitti_ms.py fuse_multi_scan) in place on (x, y, z): P = the scan's pose, Q = the
+// current frame's, both [16] row-major, float32 throughout - numpy multiplies, then adds, in k order:
+//   new_j = ((h0 P[j][0] + h1 P[j][1]) + h2 P[j][2]) + h3 P[j][3] - Q[j][3]      h = (x, y, z, 1)
+//   out_j = (new0 Q[0][j] + new1 Q[1][j]) + new2 Q[2][j]
+// __fmul_rn / __fadd_rn are inline functions of the HIP headers: no `#pragma clang fp contract(off)` here or in the caller reaches
+// them, so every operation keeps its own rounding ONLY in a file that csrc/build.py compiles with -ffp-contract=off (EXTRA).
+template <typename PtrP, typename PtrQ>
+__device__ __forceinline__ void sr_fuse_pose(PtrP P, PtrQ Q, float &x, float &y, float &z) {
+  const float h[4] = {x, y, z, 1.0f};
+  float nw[3], o[3];
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    float s = __fmul_rn(h[0], P[j * 4 + 0]);
+    s = __fadd_rn(s, __fmul_rn(h[1], P[j * 4 + 1]));
+    s = __fadd_rn(s, __fmul_rn(h[2], P[j * 4 + 2]));
+    s = __fadd_rn(s, __fmul_rn(h[3], P[j * 4 + 3]));
+    nw[j] = __fsub_rn(s, Q[j * 4 + 3]);
+  }
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    float s = __fmul_rn(nw[0], Q[0 * 4 + j]);
+    s = __fadd_rn(s, __fmul_rn(nw[1], Q[1 * 4 + j]));
+    s = __fadd_rn(s, __fmul_rn(nw[2], Q[2 * 4 + j]));
+    o[j] = s;
+  }
+  x = o[0];
+  y = o[1];
+  z = o[2];
+}
+
+// The KITTI camera projection, frustum test and pixel of ts_project_fov (semantickitti_ms_mm.py:419-434): P = P2 Tr [12] row-major,
+// sum_k P[j][k] (x, y, z, 1)[k] as dgemm's chain in k order, the two divisions, astype(int).  row / col are 0 where the frustum
+// test fails.  The flip and the crop test are the caller's.  (The image size by reference: a caller that holds it in a record reads
+// it where the test uses it, after the divisions - by value the loads move up and tf_row holds 6 VGPRs more.)
+template <typename Ptr>
+__device__ __forceinline__ bool sr_project_fov(Ptr P, float x, float y, float z, const int &img_w, const int &img_h, int &row,
+                                               int &col) {
+#pragma clang fp contract(off)
+  const double X = x, Y = y, Z = z;
+  double uvz[3];
+#pragma unroll
+  for (int j = 0; j < 3; ++j)
+    uvz[j] = __builtin_fma(P[4 * j + 3], 1.0, __builtin_fma(P[4 * j + 2], Z, __builtin_fma(P[4 * j + 1], Y, P[4 * j] * X)));
+  const double u = uvz[0] / uvz[2], v = uvz[1] / uvz[2];
+  row = 0;
+  col = 0;
+  if (!(x > 0.f && u > 0.0 && v > 0.0 && u < (double)img_w && v < (double)img_h)) return false;
+  row = (int)v;                      // astype(int): truncation
+  col = (int)u;
+  return true;
+}
+
 // The camera chain, frustum test, half-resolution pixel and top-row cut of ts_project_cam (nuscenes_ms_mm.py:349-398; the layout of
 // the 57 doubles: include/taseg_hip.h).  row / col are 0 where the frustum test fails; a pixel above the cut rows fails with its
 // row - crop_top < 0 left in `row`.

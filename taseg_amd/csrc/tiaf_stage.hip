@@ -7,8 +7,9 @@
 //                         255 through the host's table, the flip, the top-left crop and the zero padding in the one store that
 //                         writes every output element.  Frame pointers, sizes and flip bytes travel in the kernel arguments.
 //   ts_tiaf_fov_cloud     projection -> flip -> crop test -> FOV_DIST -> pose fuse -> augmentation -> clamp per row, the survivors
-//                         as one stable compaction: the three passes of csrc/compact.h with tf_row as the row rule, one tally per
-//                         sample; the augmentation and the clamp inside tf_row are those of csrc/stage_rules.h.
+//                         as one stable compaction: the one-cloud driver of csrc/compact.h (cp_compact) with tf_row as the row rule,
+//                         one tally per sample; the projection, the pose fuse, the augmentation and the clamp inside tf_row are
+//                         those of csrc/stage_rules.h.
 #include "compact.h"
 #include "stage_rules.h"
 
@@ -102,22 +103,28 @@ __global__ __launch_bounds__(256) void tf_image_kernel(TfFrames f, const float *
 }
 
 // ------------------------------------------------------------------------------------------------ FOV cloud
-struct TfRule {
+struct TfRule : CpRule {
+  typedef float Row[6];
   const float4 *pts;
   const int *frame;
   const TsTiafFrame *rec;
   const double *aug;       // [n_samples, TS_AUG_RECORD] or NULL
   const float *lo;         // [n_samples, 3] or NULL
-  int64_t n_rows, n_points;
-  int n_frames, n_samples, crop_h, crop_w;
+  float *out;              // [capacity, 6]
+  int64_t n_points;
+  int n_frames, crop_h, crop_w;
+
+  __device__ __forceinline__ bool keeps(int64_t i, bool in, Row &o, int *sample) const;
+  __device__ __forceinline__ void store(int64_t dst, int64_t, const Row &o) const {
+    float2 *d = reinterpret_cast<float2 *>(out + dst * 6);    // rows of 24 bytes: 8-byte aligned
+    d[0] = make_float2(o[0], o[1]);
+    d[1] = make_float2(o[2], o[3]);
+    d[2] = make_float2(o[4], o[5]);
+  }
 };
 
 // Does virtual row i survive, and as which output row?  o = (x, y, z, intensity, row + row_offset, col); *sample its sample.
-// Steps 1 - 5 restate project_fov_kernel / fuse_scan_kernel (csrc/pointops.hip) with the same explicit intrinsics; both passes
-// call it, so pass 3 decides on the bits pass 1 counted.
 __device__ __forceinline__ bool tf_row(const TfRule &r, int64_t i, float (&o)[6], int *sample) {
-#pragma clang fp contract(off)  // only the explicit fma() below fuse (__fmul_rn / __fadd_rn are inline functions of the HIP headers:
-                                // they keep their roundings because build.py compiles this file with -ffp-contract=off, as pointops.hip)
   const int f = min(max(r.frame[i], 0), r.n_frames - 1);
   const TsTiafFrame *__restrict__ R = r.rec + f;
   const int b = R->sample;
@@ -125,48 +132,20 @@ __device__ __forceinline__ bool tf_row(const TfRule &r, int64_t i, float (&o)[6]
   const int64_t srow = (int64_t)R->src + (i - (int64_t)R->first);
   if (b < 0 || b >= r.n_samples || srow < 0 || srow >= r.n_points) return false;
   const float4 p = r.pts[srow];
-  // 1  ts_project_fov: sum_k P[j][k] * (x, y, z, 1)[k], float64 FMA chain in k order (numpy's dgemm)
-  const double x = p.x, y = p.y, z = p.z;
-  const double *P = R->proj;
-  double uvz[3];
-#pragma unroll
-  for (int j = 0; j < 3; ++j)
-    uvz[j] = __builtin_fma(P[4 * j + 3], 1.0, __builtin_fma(P[4 * j + 2], z, __builtin_fma(P[4 * j + 1], y, P[4 * j] * x)));
-  const double u = uvz[0] / uvz[2], v = uvz[1] / uvz[2];
-  if (!(p.x > 0.f && u > 0.0 && v > 0.0 && u < (double)R->img_w && v < (double)R->img_h)) return false;
-  const int row = (int)v;                        // astype(int): truncation
-  int col = (int)u;
+  // 1  ts_project_fov
+  int row, col;
+  if (!sr_project_fov(R->proj, p.x, p.y, p.z, R->img_w, R->img_h, row, col)) return false;
   // 2  IMAGE_FLIP (:441), 3  the crop test on the flipped column (:454)
   if (R->flags & TS_TIAF_FLIP) col = R->img_w - 1 - col;
   if (!(row < r.crop_h && col < r.crop_w)) return false;
-  // 4  FOV_DIST on the un-fused x, y: float32 multiply, add, sqrt (:365-367)
+  // 4  FOV_DIST on the un-fused x, y: float32 multiply, add, sqrt (:365-367; build.py compiles this file with -ffp-contract=off)
   if (R->fov_dist > 0.f) {
     const float radius = __fsqrt_rn(__fadd_rn(__fmul_rn(p.x, p.x), __fmul_rn(p.y, p.y)));
     if (!(radius <= R->fov_dist)) return false;
   }
   float q[3] = {p.x, p.y, p.z};
-  // 5  ts_fuse_scan: float32, numpy multiplies, then adds, in k order
-  if (R->flags & TS_TIAF_FUSE) {
-    const float *Pt = R->pose, *Q = R->pose0;
-    const float hh[4] = {p.x, p.y, p.z, 1.0f};
-    float nw[3];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      float s = __fmul_rn(hh[0], Pt[j * 4 + 0]);
-      s = __fadd_rn(s, __fmul_rn(hh[1], Pt[j * 4 + 1]));
-      s = __fadd_rn(s, __fmul_rn(hh[2], Pt[j * 4 + 2]));
-      s = __fadd_rn(s, __fmul_rn(hh[3], Pt[j * 4 + 3]));
-      nw[j] = __fsub_rn(s, Q[j * 4 + 3]);
-    }
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      float s = __fmul_rn(nw[0], Q[0 * 4 + j]);
-      s = __fadd_rn(s, __fmul_rn(nw[1], Q[1 * 4 + j]));
-      s = __fadd_rn(s, __fmul_rn(nw[2], Q[2 * 4 + j]));
-      q[j] = s;
-    }
-  }
-  // 6  ts_stage_augment, 7  the clamp of ts_stage_clamp_compact
+  // 5  ts_fuse_scan, 6  ts_stage_augment, 7  the clamp of ts_stage_clamp_compact
+  if (R->flags & TS_TIAF_FUSE) sr_fuse_pose(R->pose, R->pose0, q[0], q[1], q[2]);
   if (r.aug) sr_augment(r.aug + (int64_t)TS_AUG_RECORD * b, q[0], q[1], q[2]);
   if (r.lo && !sr_clamp_keeps(q[0], q[1], q[2], r.lo, b)) return false;
   o[0] = q[0];
@@ -178,45 +157,9 @@ __device__ __forceinline__ bool tf_row(const TfRule &r, int64_t i, float (&o)[6]
   return true;
 }
 
-__global__ __launch_bounds__(CP_ROWS) void tf_count_kernel(TfRule r, int *__restrict__ blk_cnt, int *__restrict__ blk_tally) {
-  __shared__ int wcnt[CP_WAVES];
-  __shared__ int scnt[CP_WAVES][TS_WAVE];
-  const int64_t i = (int64_t)blockIdx.x * CP_ROWS + threadIdx.x;
-  cp_tally_clear<1>(scnt);
-  __syncthreads();
-  int s = -1;
-  bool keep[1] = {false};
-  if (i < r.n_rows) {
-    float o[6];
-    keep[0] = tf_row(r, i, o, &s);
-  }
-  cp_ballot(keep[0], wcnt);
-  cp_tally_wave<1>(s, keep, scnt);
-  __syncthreads();
-  if (threadIdx.x == 0) blk_cnt[blockIdx.x] = cp_block_sum(wcnt);
-  cp_tally_store<1>(scnt, r.n_samples, blk_tally);
-}
-
-__global__ __launch_bounds__(CP_ROWS) void tf_scatter_kernel(TfRule r, const int *__restrict__ offs, float *__restrict__ out,
-                                                             int64_t *__restrict__ out_sample, int *__restrict__ out_sample32,
-                                                             int64_t capacity) {
-  __shared__ int wcnt[CP_WAVES];
-  const int64_t i = (int64_t)blockIdx.x * CP_ROWS + threadIdx.x;
-  int s = -1;
-  bool keep = false;
-  float o[6];
-  if (i < r.n_rows) keep = tf_row(r, i, o, &s);             // the decision of pass 1 on the same bits
-  const CpBallot b = cp_ballot(keep, wcnt);
-  __syncthreads();
-  if (!keep) return;
-  const int64_t dst = offs[blockIdx.x] + cp_rank(b, wcnt);
-  if (dst < 0 || dst >= capacity) return;                   // (cannot happen: survivors <= rows <= capacity; bounds every store)
-  float2 *d = reinterpret_cast<float2 *>(out + dst * 6);    // rows of 24 bytes: 8-byte aligned
-  d[0] = make_float2(o[0], o[1]);
-  d[1] = make_float2(o[2], o[3]);
-  d[2] = make_float2(o[4], o[5]);
-  out_sample[dst] = s;
-  out_sample32[dst] = s;
+__device__ __forceinline__ bool TfRule::keeps(int64_t i, bool in, Row &o, int *sample) const {
+  *sample = -1;
+  return in && tf_row(*this, i, o, sample);
 }
 
 }  // namespace
@@ -259,15 +202,13 @@ extern "C" int ts_tiaf_image_stack(const uint8_t *const *images, const float *co
   return TS_OK;
 }
 
-extern "C" size_t ts_tiaf_fov_cloud_workspace_bytes(int64_t n_rows, int32_t n_samples) {
-  return cp_carve(nullptr, ts_cdiv(std::max<int64_t>(n_rows, 0), CP_ROWS), 1, std::max(n_samples, 0)).bytes;
-}
+extern "C" size_t ts_tiaf_fov_cloud_workspace_bytes(int64_t n_rows, int32_t n_samples) { return cp_compact_bytes(n_rows, n_samples); }
 
 extern "C" int ts_tiaf_fov_cloud(const float *points, int64_t n_points, const int32_t *frame, int64_t n_rows,
                                  const TsTiafFrame *records, int32_t n_frames, const double *aug, const float *lo, int32_t n_samples,
                                  int32_t crop_h, int32_t crop_w, float *out, int64_t *out_sample, int32_t *out_sample32,
                                  int64_t capacity, int64_t *counts, void *ws, size_t ws_bytes, ts_stream_t stream) {
-  static_assert(TS_TIAF_MAX_SAMPLES == TS_WAVE, "tf_count_kernel keeps one LDS counter per (wave, sample)");
+  static_assert(TS_TIAF_MAX_SAMPLES == TS_WAVE, "cp_count_kernel keeps one LDS counter per (wave, sample)");
   static_assert(sizeof(TsTiafFrame) == 256, "the frame record is 256 bytes (taseg_amd/data/tiaf.py FRAME_DTYPE)");
   TS_REQUIRE(n_points >= 0 && n_rows >= 0 && n_rows < (int64_t)1 << 30 && n_points < (int64_t)1 << 30 && n_frames >= 1 &&
                  n_frames <= TS_TIAF_MAX_FRAMES && n_samples >= 1 && n_samples <= TS_TIAF_MAX_SAMPLES && crop_h > 0 && crop_w > 0 &&
@@ -279,20 +220,7 @@ extern "C" int ts_tiaf_fov_cloud(const float *points, int64_t n_points, const in
              "ts_tiaf_fov_cloud: null pointer");
   TS_REQUIRE((((uintptr_t)points) & 15) == 0 && (((uintptr_t)out) & 7) == 0, TS_ERR_INVALID_ARGUMENT,
              "ts_tiaf_fov_cloud: points must be 16-byte, out 8-byte aligned");
-  const int64_t n_blocks = ts_cdiv(n_rows, CP_ROWS);
-  const CpWorkspace c = cp_carve(ws, n_blocks, 1, n_samples);
-  TS_REQUIRE(ws_bytes >= c.bytes, TS_ERR_INVALID_ARGUMENT, "ts_tiaf_fov_cloud: workspace too small");
-  hipStream_t st = (hipStream_t)stream;
-  const TfRule r = {(const float4 *)points, frame, records, aug, lo, n_rows, n_points, n_frames, n_samples, crop_h, crop_w};
-  if (n_blocks > 0) {
-    tf_count_kernel<<<(int)n_blocks, CP_ROWS, 0, st>>>(r, c.blk_cnt, c.blk_tally);
-    TS_CHECK_LAUNCH("ts_tiaf_fov_cloud (count)");
-  }
-  ts_compact_scan(c, (int)n_blocks, 1, n_samples, counts, st);
-  TS_CHECK_LAUNCH("ts_tiaf_fov_cloud (scan)");
-  if (n_blocks > 0) {
-    tf_scatter_kernel<<<(int)n_blocks, CP_ROWS, 0, st>>>(r, c.offs, out, out_sample, out_sample32, capacity);
-    TS_CHECK_LAUNCH("ts_tiaf_fov_cloud (scatter)");
-  }
-  return TS_OK;
+  const TfRule r = {{n_rows, capacity, n_samples, out_sample, out_sample32}, (const float4 *)points, frame, records, aug, lo, out,
+                    n_points, n_frames, crop_h, crop_w};
+  return cp_compact(r, "ts_tiaf_fov_cloud", counts, ws, ws_bytes, (hipStream_t)stream);
 }

@@ -56,10 +56,10 @@ import torch
 
 from .. import backend as B
 from ..torchsparse import SparseTensor
-from .augment import augment_points, draw_tta_params, pack_params
+from .augment import augment_points, draw_tta_params
 from .nuscenes import NuscSequence, _current_keyframe, fuse_sweeps, relative_transform, rotation_matrix
-from .stage import _aug_records, _one_aug, _quantize, collate_batch, rows_index32, voxelize_fov, voxelize_sample_ms
-from .tiaf import _unit_table, bgr_unit
+from .stage import _aug_records, _one_aug, clamp_corner, rows_index32, voxelize_fov, voxelize_sample_ms
+from .tiaf import _camera_batch_head, _camera_batch_tail, _unit_table, bgr_unit, build_tiaf_batch
 
 __all__ = ["select_image_keyframes", "camera_chain", "frame_cloud", "fov_points", "half_image", "build_nusc_tiaf_sample",
            "build_nusc_tiaf_batch", "build_nusc_tiaf_batch_from_keyframes", "build_nusc_tiaf_tta_batch", "CAM_FRAME_DTYPE"]
@@ -246,9 +246,7 @@ def build_nusc_tiaf_sample(fsa: Dict, seq: NuscSequence, index: int, key_points:
     sample, point = _lidar_side(fsa, steps, in_feature_dim, voxel_size, name, rec)
     if rec is not None:
         fov = augment_points(fov, rec)
-    fov_lab = voxelize_fov(sample, point, fov, voxel_size, fov_lab)     # clamp_fov_mask (:133-135), lidar_fov_ms
-    # (the reference pairs the FOV labels with the FUSED cloud's coordinates, :197 - kept as it is)
-    sample["targets_fov_ms"] = SparseTensor(fov_lab, sample["lidar_ms"].C)
+    _pair_fov_labels(sample, voxelize_fov(sample, point, fov, voxel_size, fov_lab))     # clamp_fov_mask (:133-135), lidar_fov_ms
     sample["image_ms"] = torch.stack(images, 0)
     sample["semantic_map_ms"] = torch.stack(semantic, 0)
     n_img = len(images)
@@ -259,20 +257,15 @@ def build_nusc_tiaf_sample(fsa: Dict, seq: NuscSequence, index: int, key_points:
     return sample
 
 
+def _pair_fov_labels(sample: Dict, fov_lab: torch.Tensor) -> None:
+    """targets_fov_ms: the reference pairs the FOV labels with the FUSED cloud's coordinates (:197) - kept as it is"""
+    sample["targets_fov_ms"] = SparseTensor(fov_lab, sample["lidar_ms"].C)
+
+
 def build_nusc_tiaf_batch(samples: List[Dict]) -> Dict:
     """collate_batch of nuscenes_voxel_ms_mm.py:225-262 on device tensors (samples built with zero_maps=False: without the two
-    all-zero maps)."""
-    stacks = {k: [s.pop(k) for s in samples] for k in ("image_ms", "depth_map_ms", "lidar_map_ms", "semantic_map_ms")
-              if k in samples[0]}
-    for s in samples:
-        for k in ("_image_keyframes", "_fov_points", "_fov_labels"):
-            s.pop(k, None)
-    out = collate_batch(samples)
-    dev = stacks["image_ms"][0].device
-    out["offset_img"] = torch.cumsum(torch.tensor([i.shape[0] for i in stacks["image_ms"]]), 0).int().to(dev)
-    for k, v in stacks.items():
-        out[k] = torch.cat(v, 0).permute(0, 3, 1, 2).contiguous()
-    return out
+    all-zero maps): tiaf.build_tiaf_batch."""
+    return build_tiaf_batch(samples)
 
 
 _SAMPLE_DEFAULTS = {"in_feature_dim": 4, "crop_top": 2, "name": ""}
@@ -349,15 +342,13 @@ def _camera_records(inputs: List[Dict], frames_of: List[List[int]], entry_input:
 def _build_camera_batch(inputs: List[Dict], frames_of: List[List[int]], votes: Optional[int], aug, zero_maps: bool) -> Dict:
     """build_nusc_tiaf_batch_from_keyframes (votes None) and build_nusc_tiaf_tta_batch (votes: the number of views of the ONE sample
     of `inputs`): entry b of the batch is sample b, or view b of the sample"""
-    nb = len(inputs) if votes is None else votes
-    entry_input = list(range(nb)) if votes is None else [0] * nb
     dev = inputs[0]["fsa"]["points"].device
+    nb, rec_dev = _camera_batch_head(len(inputs), votes, aug, dev)
+    entry_input = list(range(nb)) if votes is None else [0] * nb
     # the image planes and the zero maps of a batch are ONE tensor each: what shapes them has to agree between the samples
     shaping = {(tuple(inp["full_image_size"]), inp.get("crop_top", _SAMPLE_DEFAULTS["crop_top"])) for inp in inputs}
     if len(shaping) != 1:
         raise ValueError("the samples of a batch share full_image_size and crop_top (got %s)" % sorted(shaping))
-    rec = None if aug is None else _aug_records(aug, nb)
-    rec_dev = None if rec is None else torch.from_numpy(rec).to(dev, non_blocking=True)
     # LiDAR side, per entry: the FSA fuse, both clouds through the entry's record, the two voxelisations
     samples, los = [], []
     for b, k in enumerate(entry_input):
@@ -366,7 +357,7 @@ def _build_camera_batch(inputs: List[Dict], frames_of: List[List[int]], votes: O
                                     inp["voxel_size"], inp.get("name", _SAMPLE_DEFAULTS["name"]),
                                     None if rec_dev is None else rec_dev[b:b + 1])
         samples.append(sample)
-        los.append(point[:, :3].t().contiguous().min(1).values)      # (voxelize_fov: the row-wise minimum of the transposed copy)
+        los.append(clamp_corner(point))
     # camera side: every image keyframe's cloud once, into ITS lidar frame in one launch; a record per (entry, keyframe, view)
     points5, labels, sweep, params, table, virt, images_of = _camera_records(inputs, frames_of, entry_input, dev)
     moved, no_ego = B.fuse_sweeps(points5.contiguous(), sweep, params)
@@ -385,20 +376,9 @@ def _build_camera_batch(inputs: List[Dict], frames_of: List[List[int]], votes: O
     if len(planes) != 1:
         raise ValueError("the half-resolution camera images of a batch share one size (got %s)" % sorted(planes))
     image_ms, semantic_ms = B.tiaf_image_stack(images, semantic, None, _unit_table(dev), planes.pop())
-    at = 0
-    for s, k, n in zip(samples, entry_input, counts.tolist()):          # the one host read of the camera side
-        cloud, lab = fov[at:at + n], fov_lab[at:at + n]
-        at += n
-        pc_fov, _, inds_fov, _ = _quantize(cloud, inputs[k]["voxel_size"], shift=s.pop("_shift"))
-        s["lidar_fov_ms"] = SparseTensor(cloud[inds_fov], pc_fov[inds_fov])
-        # (the reference pairs the FOV labels with the FUSED cloud's coordinates, :197 - kept as it is)
-        s["targets_fov_ms"] = SparseTensor(lab[inds_fov], s["lidar_ms"].C)
-    out = collate_batch(samples)
-    if votes is not None:                                               # the same images for every view: built once, repeated
-        per_entry = per_entry * votes
-        image_ms, semantic_ms = image_ms.repeat(votes, 1, 1, 1), semantic_ms.repeat(votes, 1, 1, 1)
-    out["offset_img"] = torch.cumsum(torch.tensor(per_entry), 0).int().to(dev)
-    out["image_ms"], out["semantic_map_ms"] = image_ms, semantic_ms
+    out = _camera_batch_tail(samples, [inputs[k]["voxel_size"] for k in entry_input], fov, fov_lab, counts, per_entry, votes, image_ms,
+                             semantic_ms, labelled=_pair_fov_labels)
+    image_ms = out["image_ms"]
     if zero_maps:                                                       # (:346-347: all zeros at FULL resolution)
         inp = inputs[0]
         w_full, h_full = inp["full_image_size"]
@@ -410,6 +390,14 @@ def _build_camera_batch(inputs: List[Dict], frames_of: List[List[int]], votes: O
 
 def _records_of(inputs: List[Dict], frames_of: List[List[int]], entries: int) -> int:
     return sum(len(_valid_keyframes(inp["seq"], inp["index"], fr)) * len(inp["used_view"]) for inp, fr in zip(inputs, frames_of)) * entries
+
+
+def _per_sample_batch(inputs: List[Dict], frames_of: List[List[int]], aug, zero_maps: bool) -> Dict:
+    """The cross-check path as the fallback of both builders: entry b from inputs[b] with the b-th record of `aug`"""
+    rec = None if aug is None else _aug_records(aug, len(inputs))
+    return build_nusc_tiaf_batch([build_nusc_tiaf_sample(**{**inp, "image_keyframes": fr, "zero_maps": zero_maps},
+                                                         aug=None if rec is None else rec[b:b + 1])
+                                  for b, (inp, fr) in enumerate(zip(inputs, frames_of))])
 
 
 def _select(inp: Dict) -> List[int]:
@@ -439,10 +427,7 @@ def build_nusc_tiaf_batch_from_keyframes(inputs: List[Dict], aug=None, zero_maps
         raise ValueError("no samples")
     frames_of = [_select(inp) for inp in inputs]
     if nb > B.TIAF_MAX_SAMPLES or _records_of(inputs, frames_of, 1) > B.TIAF_MAX_FRAMES:
-        rec = None if aug is None else _aug_records(aug, nb)
-        return build_nusc_tiaf_batch([build_nusc_tiaf_sample(**{**inp, "image_keyframes": fr, "zero_maps": zero_maps},
-                                                             aug=None if rec is None else rec[b:b + 1])
-                                      for b, (inp, fr) in enumerate(zip(inputs, frames_of))])
+        return _per_sample_batch(inputs, frames_of, aug, zero_maps)
     return _build_camera_batch(inputs, frames_of, None, aug, zero_maps)
 
 
@@ -461,7 +446,5 @@ def build_nusc_tiaf_tta_batch(inp: Dict, votes_min: int, votes_max: int, rng: np
     aug = [draw_tta_params(rng, v, scale_range) for v in votes]
     frames = _select(inp)
     if len(votes) > B.TIAF_MAX_SAMPLES or _records_of([inp], [frames], len(votes)) > B.TIAF_MAX_FRAMES:
-        rec = pack_params(aug)
-        return build_nusc_tiaf_batch([build_nusc_tiaf_sample(**{**inp, "image_keyframes": frames, "zero_maps": zero_maps},
-                                                             aug=rec[i:i + 1]) for i in range(len(votes))])
+        return _per_sample_batch([inp] * len(votes), [frames] * len(votes), aug, zero_maps)
     return _build_camera_batch([inp], [frames], len(votes), aug, zero_maps)

@@ -165,6 +165,12 @@ def _one_aug(aug):
     return rec
 
 
+def clamp_corner(points) -> torch.Tensor:
+    """points[:, :3].min(0), the corner a sample's fused and FOV clouds are clamped to.  (The min over dim 0 of the [n, 3] slice runs
+    in one of torch's slow few-column reductions, 175 us for 35k points: the row-wise minimum of the transposed copy takes ~10 us.)"""
+    return points[:, :3].t().contiguous().min(1).values
+
+
 def voxelize_sample(points, labels, voxel_size, name="", aug=None) -> Dict:
     """Single-frame sample (semantickitti_voxel.py:119-150); aug: the sample's AugParams, applied first (:89-99)."""
     if aug is not None:
@@ -184,10 +190,7 @@ def voxelize_sample_ms(points, labels, points_ms, labels_ms, voxel_size, name=""
     if aug is not None:
         rec = torch.from_numpy(_one_aug(aug)).to(points.device, non_blocking=True)
         points, points_ms = augment_points(points, rec), augment_points(points_ms, rec)
-    # (min over dim 0 of the [n, 3] slice runs in one of torch's slow few-column reductions: 175 us for 35k points;
-    #  the same minimum along the rows of the transposed copy takes ~10 us)
-    lo = points[:, :3].t().contiguous().min(1).values
-    clamp = (points_ms[:, :3] >= lo).all(1)                               # :121-124
+    clamp = (points_ms[:, :3] >= clamp_corner(points)).all(1)             # :121-124
     if keep is not None:
         clamp = clamp & keep
     points_ms, labels_ms = points_ms[clamp].contiguous(), labels_ms[clamp]
@@ -207,19 +210,19 @@ def voxelize_sample_ms(points, labels, points_ms, labels_ms, voxel_size, name=""
     }
 
 
-def voxelize_fov(sample: Dict, point, fov, voxel_size, fov_labels=None):
-    """The camera samples' third cloud (semantickitti_voxel_ms_mm.py:124-204 / nuscenes_voxel_ms_mm.py:133-204): `fov` [m, 6] clamped
-    to the corner of the single-frame cloud `point`, rounded and shifted like the other two - `sample` is voxelize_sample_ms's with
-    return_shift=True, whose "_shift" is taken out - and grouped per voxel into sample["lidar_fov_ms"].  Returns fov_labels of the
-    voxels' representatives (None without labels)."""
-    lo = point[:, :3].t().contiguous().min(1).values       # (row-wise minimum of the transposed copy: see voxelize_sample_ms)
-    inside = (fov[:, :3] >= lo).all(1)
-    fov = fov[inside].contiguous()
-    if fov_labels is not None:
-        fov_labels = fov_labels[inside]
+def voxelize_fov_cloud(sample: Dict, fov, voxel_size, fov_labels=None):
+    """The camera samples' third cloud, clamped already: `fov` [m, 6] rounded and shifted like the other two - `sample` is
+    voxelize_sample_ms's with return_shift=True, whose "_shift" is taken out - and grouped per voxel into sample["lidar_fov_ms"].
+    Returns fov_labels of the voxels' representatives (None without labels)."""
     pc_fov, _, inds_fov, _ = _quantize(fov, voxel_size, shift=sample.pop("_shift"))
     sample["lidar_fov_ms"] = SparseTensor(fov[inds_fov], pc_fov[inds_fov])
     return None if fov_labels is None else fov_labels[inds_fov]
+
+
+def voxelize_fov(sample: Dict, point, fov, voxel_size, fov_labels=None):
+    """voxelize_fov_cloud of `fov` clamped to the single-frame cloud `point`'s corner (semantickitti_voxel_ms_mm.py:124-204 / nuscenes_: 133-204)"""
+    inside = (fov[:, :3] >= clamp_corner(point)).all(1)
+    return voxelize_fov_cloud(sample, fov[inside].contiguous(), voxel_size, None if fov_labels is None else fov_labels[inside])
 
 
 def _stack_sparse(items: List[SparseTensor]) -> SparseTensor:

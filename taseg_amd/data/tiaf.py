@@ -44,11 +44,10 @@ import numpy as np
 import torch
 
 from .. import backend as B
-from ..torchsparse import SparseTensor
-from .augment import augment_points, draw_tta_params, pack_params
+from .augment import augment_points, draw_tta_params
 from .mix import draw_coin
-from .stage import (_aug_records, _fuse_history, _one_aug, _quantize, collate_batch, rows_index32, voxelize_fov,
-                    voxelize_sample_ms)
+from .stage import (_aug_records, _fuse_history, _one_aug, clamp_corner, collate_batch, rows_index32, voxelize_fov,
+                    voxelize_fov_cloud, voxelize_sample_ms)
 
 __all__ = ["ring_id", "fov_points", "crop_image", "draw_image_flips", "build_tiaf_sample", "build_tiaf_batch",
            "build_tiaf_batch_from_frames", "build_tiaf_tta_batch", "FRAME_DTYPE"]
@@ -183,14 +182,19 @@ def build_tiaf_sample(frames: Dict[int, Dict], steps: Sequence[int], multiscan: 
 
 
 def build_tiaf_batch(samples: List[Dict]) -> Dict:
-    """collate_batch of semantickitti_voxel_ms_mm.py:223-266 on device tensors."""
-    images = [s.pop("image_ms") for s in samples]
-    semantic = [s.pop("semantic_map_ms") for s in samples]
+    """collate_batch of semantickitti_voxel_ms_mm.py:223-266 / nuscenes_voxel_ms_mm.py:225-262 on device tensors: the sparse
+    collate, the image stacks the samples carry (any of image_ms, depth_map_ms, lidar_map_ms, semantic_map_ms) concatenated along
+    the frame axis as NCHW, offset_img; the samples' diagnostic keys ("_...") are left out."""
+    stacks = {k: [s.pop(k) for s in samples] for k in ("image_ms", "depth_map_ms", "lidar_map_ms", "semantic_map_ms")
+              if k in samples[0]}
+    for s in samples:
+        for k in ("_image_keyframes", "_fov_points", "_fov_labels"):
+            s.pop(k, None)
     out = collate_batch(samples)
-    dev = images[0].device
-    out["offset_img"] = torch.cumsum(torch.tensor([i.shape[0] for i in images]), 0).int().to(dev)
-    out["image_ms"] = torch.cat(images, 0).permute(0, 3, 1, 2).contiguous()
-    out["semantic_map_ms"] = torch.cat(semantic, 0).permute(0, 3, 1, 2).contiguous()
+    dev = stacks["image_ms"][0].device
+    out["offset_img"] = torch.cumsum(torch.tensor([i.shape[0] for i in stacks["image_ms"]]), 0).int().to(dev)
+    for k, v in stacks.items():
+        out[k] = torch.cat(v, 0).permute(0, 3, 1, 2).contiguous()
     return out
 
 
@@ -211,13 +215,36 @@ def _frame_records(entries, dev) -> torch.Tensor:
     return torch.cat([proj.view(torch.uint8), pose0.view(torch.uint8), pose.view(torch.uint8), tail], 1)
 
 
+def _camera_batch_head(n_inputs: int, votes: Optional[int], aug, dev):
+    """(nb, the [nb, 8] augmentation records on the device or None): entry b of the batch is input b, or view b of the ONE input"""
+    nb = n_inputs if votes is None else votes
+    return nb, None if aug is None else torch.from_numpy(_aug_records(aug, nb)).to(dev, non_blocking=True)
+
+
+def _camera_batch_tail(samples, voxel_sizes, fov, fov_lab, counts, per_input, votes, image_ms, semantic_ms, labelled=None) -> Dict:
+    """The end of both datasets' batched camera side.  samples: voxelize_sample_ms's per entry; fov (fov_lab, or None): the compacted
+    FOV cloud of the batch, counts [nb]: its rows per entry, on the device; labelled(sample, the labels of its FOV voxels): what a
+    dataset with FOV labels adds; per_input: the images per input; image_ms / semantic_ms: their planes, repeated under `votes`."""
+    at = 0
+    for s, voxel_size, n in zip(samples, voxel_sizes, counts.tolist()):     # the one host read of the camera side
+        lab = voxelize_fov_cloud(s, fov[at:at + n], voxel_size, None if fov_lab is None else fov_lab[at:at + n])
+        if labelled is not None:
+            labelled(s, lab)
+        at += n
+    out = collate_batch(samples)
+    if votes is not None:                                               # the same images for every view: built once, repeated
+        per_input = per_input * votes
+        image_ms, semantic_ms = image_ms.repeat(votes, 1, 1, 1), semantic_ms.repeat(votes, 1, 1, 1)
+    out["offset_img"] = torch.cumsum(torch.tensor(per_input), 0).int().to(image_ms.device)
+    out["image_ms"], out["semantic_map_ms"] = image_ms, semantic_ms
+    return out
+
+
 def _build_camera_batch(frames_list, votes, steps, multiscan, step_image, projs, crop, voxel_size, names, fov_dist, aug, flips) -> Dict:
     """build_tiaf_batch_from_frames (votes None) and build_tiaf_tta_batch (votes: the number of views of the ONE sample of
     frames_list): entry b of the batch is sample b, or view b of the sample"""
-    nb = len(frames_list) if votes is None else votes
     dev = frames_list[0][0]["points"].device
-    rec = None if aug is None else _aug_records(aug, nb)
-    rec_dev = None if rec is None else torch.from_numpy(rec).to(dev, non_blocking=True)
+    nb, rec_dev = _camera_batch_head(len(frames_list), votes, aug, dev)
     # LiDAR side, per sample: the current scan and the fused history through the sample's record, the two voxelisations
     samples, los, lidar = [], [], {}
     for b in range(nb):
@@ -228,7 +255,7 @@ def _build_camera_batch(frames_list, votes, steps, multiscan, step_image, projs,
         if rec_dev is not None:
             point, raw_all = augment_points(point, rec_dev[b:b + 1]), augment_points(raw_all, rec_dev[b:b + 1])
         samples.append(voxelize_sample_ms(point, labels, raw_all, lab_all, voxel_size, names[b], keep=keep, return_shift=True))
-        los.append(point[:, :3].t().contiguous().min(1).values)      # (voxelize_sample_ms: the row-wise minimum of the transposed copy)
+        los.append(clamp_corner(point))
     # camera side: the rows of every camera frame of every sample once, a record per (batch entry, frame)
     rows, lengths, images, semantic, img_flips, per_sample, starts = [], [], [], [], [], [], {}
     for frames in frames_list:
@@ -259,19 +286,15 @@ def _build_camera_batch(frames_list, votes, steps, multiscan, step_image, projs,
     fov, _, _, counts = B.tiaf_fov_cloud(torch.cat(rows, 0), rows_index32(virt, dev), _frame_records(entries, dev), nb, crop,
                                          aug=rec_dev, lo=torch.stack(los, 0))
     image_ms, semantic_ms = B.tiaf_image_stack(images, semantic, img_flips, _unit_table(dev), crop)
-    at = 0
-    for s, n in zip(samples, counts.tolist()):                          # the one host read of the camera side
-        cloud = fov[at:at + n]
-        at += n
-        pc_fov, _, inds_fov, _ = _quantize(cloud, voxel_size, shift=s.pop("_shift"))
-        s["lidar_fov_ms"] = SparseTensor(cloud[inds_fov], pc_fov[inds_fov])
-    out = collate_batch(samples)
-    if votes is not None:                                               # the same images for every view: built once, repeated
-        per_sample = per_sample * votes
-        image_ms, semantic_ms = image_ms.repeat(votes, 1, 1, 1), semantic_ms.repeat(votes, 1, 1, 1)
-    out["offset_img"] = torch.cumsum(torch.tensor(per_sample), 0).int().to(dev)
-    out["image_ms"], out["semantic_map_ms"] = image_ms, semantic_ms
-    return out
+    return _camera_batch_tail(samples, [voxel_size] * nb, fov, None, counts, per_sample, votes, image_ms, semantic_ms)
+
+
+def _per_sample_batch(frames_list, steps, multiscan, step_image, projs, crop, voxel_size, names, fov_dist, aug, flips) -> Dict:
+    """The cross-check path as the fallback of both builders: entry b from frames_list[b] with the b-th record of `aug`"""
+    rec = None if aug is None else _aug_records(aug, len(frames_list))
+    return build_tiaf_batch([build_tiaf_sample(f, steps, multiscan, step_image, projs[b], crop, voxel_size, names[b], fov_dist,
+                                               aug=None if rec is None else rec[b:b + 1], flips=None if flips is None else flips[b])
+                             for b, f in enumerate(frames_list)])
 
 
 def build_tiaf_batch_from_frames(frames_list: List[Dict[int, Dict]], steps: Sequence[int], multiscan: int, step_image: int, projs,
@@ -293,10 +316,7 @@ def build_tiaf_batch_from_frames(frames_list: List[Dict[int, Dict]], steps: Sequ
         raise ValueError("names, projs and flips hold one entry per sample")
     n_frames = sum(len(_camera_deltas(f)) for f in frames_list)
     if nb == 0 or nb > B.TIAF_MAX_SAMPLES or n_frames > B.TIAF_MAX_FRAMES:
-        rec = None if aug is None else _aug_records(aug, nb)
-        return build_tiaf_batch([build_tiaf_sample(f, steps, multiscan, step_image, projs[b], crop, voxel_size, names[b], fov_dist,
-                                                   aug=None if rec is None else rec[b:b + 1], flips=None if flips is None else flips[b])
-                                 for b, f in enumerate(frames_list)])
+        return _per_sample_batch(frames_list, steps, multiscan, step_image, projs, crop, voxel_size, names, fov_dist, aug, flips)
     return _build_camera_batch(frames_list, None, steps, multiscan, step_image, projs, crop, voxel_size, names, fov_dist, aug, flips)
 
 
@@ -312,8 +332,7 @@ def build_tiaf_tta_batch(frames: Dict[int, Dict], votes_min: int, votes_max: int
     votes = list(range(votes_min, votes_max))
     aug = [(draw_coin(rng), draw_tta_params(rng, v, scale_range))[1] for v in votes]
     if not votes or len(votes) > B.TIAF_MAX_SAMPLES or len(votes) * len(_camera_deltas(frames)) > B.TIAF_MAX_FRAMES:
-        rec = pack_params(aug) if votes else None
-        return build_tiaf_batch([build_tiaf_sample(frames, steps, multiscan, step_image, proj, crop, voxel_size, name, fov_dist,
-                                                   aug=rec[i:i + 1]) for i in range(len(votes))])
+        return _per_sample_batch([frames] * len(votes), steps, multiscan, step_image, [proj] * len(votes), crop, voxel_size,
+                                 [name] * len(votes), fov_dist, aug, None)
     return _build_camera_batch([frames], len(votes), steps, multiscan, step_image, [proj], crop, voxel_size, [name] * len(votes),
                                fov_dist, aug, None)

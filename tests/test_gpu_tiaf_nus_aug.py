@@ -269,6 +269,13 @@ def _case(name):
         pts, nb = _points(rs, 64 * 10), 64
         recs = [_record(rs, 10 * b, 10, b, yaw=45.0 * b) for b in range(64)]
         aug = [A.draw_train_params(np.random.RandomState(b), rotate=bool(b % 2)) for b in range(64)]
+    elif name == "three_samples_past_256_blocks":
+        # 66 000 virtual rows = 258 blocks: the shared scan's threads sum chunks of two block counts (one up to 256 blocks)
+        pts, nb = _points(rs, 22000), 3
+        recs = [_record(rs, 0, 22000, 0, identity=True), _record(rs, 0, 22000, 1, yaw=120.0), _record(rs, 0, 22000, 2, yaw=240.0)]
+        aug = [A.AugParams(scale=1.05, scale_on=True, translate=(0.1, -0.2, 0.05), translate_on=True),
+               A.draw_tta_params(np.random.RandomState(3), 3), A.AugParams(flip=3, flip_on=True)]
+        lo = np.array([[8.0, -80.0, -80.0], [-80.0, -80.0, -0.6], [-80.0, -80.0, 0.1]], dtype=np.float32)
     elif name == "sample_and_point_rows_out_of_range":
         pts, nb = _points(rs, 300), 2
         recs = [_record(rs, 0, 100, 0), _record(rs, 100, 100, -1), _record(rs, 100, 100, 2), _record(rs, 280, 50, 1),
@@ -338,7 +345,7 @@ def _chain(d, recs):
 CASES = ["rows_1", "rows_255", "rows_256", "rows_257", "rows_%d" % (64 * 256 + 3), "boundary_in_a_wave_and_an_empty_record",
          "a_view_and_a_whole_sample_keep_nothing", "a_block_without_survivors", "pre_keep_paint_and_nan",
          "clamp_rejects_only_after_the_augmentation", "views_of_a_tta_batch_share_the_point_rows", "sixty_four_samples",
-         "sample_and_point_rows_out_of_range"]
+         "sample_and_point_rows_out_of_range", "three_samples_past_256_blocks"]
 
 
 @pytest.mark.parametrize("name", CASES)
@@ -368,6 +375,9 @@ def test_fov_cloud_kernel_equals_the_chain_it_replaces(name):
         assert (counts < free).all() and (counts > 0).all()                   # ... and not every augmented one
     if name == "sample_and_point_rows_out_of_range":
         assert int(counts[0]) > 0
+    if name == "three_samples_past_256_blocks":                               # every sample keeps some rows and loses some to its corner
+        free = torch.bincount(_chain({**d, "lo": None}, case[3])[2], minlength=3)
+        assert d["frame"].shape[0] == 66000 and (counts > 0).all() and (counts < free).all()
 
 
 def _raw_call(d, out, capacity):
