@@ -3,11 +3,14 @@
 // The reference runs nn.BatchNorm1d / nn.SyncBatchNorm on the feature matrix of every sparse conv
 // (R/pcseg/model/segmentor/voxel/minkunet/minkunet.py:23-29, TS/torchsparse/nn/utils/apply.py:10-16), followed by
 // the residual add and the ReLU as separate passes.  This file holds
-//   * the elementwise halves: BN apply (+ residual) (+ ReLU) forward / backward (ts_bn_act_forward / _backward),
-//     statistics finalisation (ts_bn_finalize);
-//   * the sliced reductions + finish kernels and the one-call-per-direction training entry points
-//     (ts_bn_act_train_forward / _backward, fp32 and half storage);
-//   * the SyncBatchNorm reduction halves whose double sums the host all-reduces (ts_bn_sync_*).
+//   * ONE kernel set on <T, VE> for fp32 rows (<float, 4>) and IEEE half rows (<_Float16, 8>): sliced partial sums
+//     (bn_partial_kernel), BN apply (+ residual) (+ ReLU) forward (bn_act_fwd_kernel) and its backward from two float
+//     coefficients per channel (bn_act_bwd_coef_kernel); a thread owns one 16-byte chunk of a row, BnVec<T, VE>;
+//   * the precision-free pieces: the finish kernels that add the slices' partials in double, statistics finalisation
+//     (ts_bn_finalize), the fp32 backward from double sums (bn_act_bwd_kernel, ts_bn_act_backward);
+//   * one host driver per operation on <T, VE> (bn_train_forward, bn_train_backward, bn_sync_stats,
+//     bn_sync_backward_reduce, bn_apply_forward, bn_apply_backward_coef); the extern "C" entry points pick an instantiation;
+//   * LeakyReLU -> BatchNorm2d of the dense 2-D branch (lbn_*), which shares the slice rule, the LDS fold and the finishes.
 // Accumulation: float per lane over one slice (<= ~350 rows), double across slices.
 #include <stdlib.h>
 
@@ -45,40 +48,66 @@ extern "C" int ts_bn_finalize(const double *sums, const double *total_dev, doubl
   return TS_OK;
 }
 
+// One 16-byte chunk of a row: 4 floats or 8 halves.
+template <typename T, int VE>
+struct alignas(VE * sizeof(T)) BnVec {
+  T x[VE];
+};
+
+// A thread's VE channels of a per-channel fp32 vector.  The fp32 kernels take them as one 16-byte load (their entry points demand
+// the alignment); the half kernels read 8 scalars and demand none.
+template <int VE>
+__device__ __forceinline__ BnVec<float, VE> bn_load_ch(const float *__restrict__ p) {
+  if constexpr (VE == 4) {
+    return *(const BnVec<float, 4> *)p;
+  } else {
+    BnVec<float, VE> v;
+#pragma unroll
+    for (int i = 0; i < VE; ++i) v.x[i] = p[i];
+    return v;
+  }
+}
+
 // ------------------------------------------------------------------------------------------------------
 // Fused BatchNorm-apply (+ residual add) (+ ReLU) and its backward: one pass each instead of
 // batch_norm_elemt -> add -> relu (forward) and relu-backward -> reduce -> batch_norm_backward_elemt (backward).
 //   forward   out = act((x - mean) * invstd * w + b [+ res])
-//   backward  g = gout * (out > 0)          (act = relu; the forward stores a 4-bit sign mask per float4)
+//   backward  g = gout * (out > 0)          (act = relu; the forward stores one sign bit per element, a byte per chunk of 8
+//                                            halves, the low 4 bits of a byte per chunk of 4 floats)
 //             sums[0] = sum g, sums[1] = sum g (x - mean)                            (ts_bn_act_backward_reduce)
 //             gx = (g - sums[0]/N - (x - mean) invstd^2 sums[1]/N) invstd w ,  gres = g   (ts_bn_act_backward)
-__global__ __launch_bounds__(256) void bn_act_fwd_kernel(const float4 *__restrict__ X, const float4 *__restrict__ RES,
-                                                         const float *__restrict__ mean,
-                                                         const float *__restrict__ invstd,
-                                                         const float *__restrict__ w, const float *__restrict__ b,
-                                                         int64_t total4, int cq, int relu, float4 *__restrict__ OUT,
+// Activations, residual and gradients are T in HBM; every reduction / normalisation runs in fp32 (statistics, affine parameters
+// and parameter gradients stay fp32, as under torch.autocast).
+template <typename T, int VE>
+__global__ __launch_bounds__(256) void bn_act_fwd_kernel(const BnVec<T, VE> *__restrict__ X, const BnVec<T, VE> *__restrict__ RES,
+                                                         const float *__restrict__ mean, const float *__restrict__ invstd,
+                                                         const float *__restrict__ w, const float *__restrict__ b, int64_t total,
+                                                         int cq, int relu, BnVec<T, VE> *__restrict__ OUT,
                                                          unsigned char *__restrict__ MASK) {
+  using V = BnVec<T, VE>;
   int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t step = (int64_t)gridDim.x * blockDim.x;
-  for (; e < total4; e += step) {
-    const int q = (int)(e % cq) * 4;
-    const float4 x = X[e];
-    const float4 m = *(const float4 *)(mean + q), s = *(const float4 *)(invstd + q);
-    const float4 ww = *(const float4 *)(w + q), bb = *(const float4 *)(b + q);
-    float4 y;
-    y.x = (x.x - m.x) * s.x * ww.x + bb.x;
-    y.y = (x.y - m.y) * s.y * ww.y + bb.y;
-    y.z = (x.z - m.z) * s.z * ww.z + bb.z;
-    y.w = (x.w - m.w) * s.w * ww.w + bb.w;
-    if (RES) {
-      const float4 r = RES[e];
-      y.x += r.x; y.y += r.y; y.z += r.z; y.w += r.w;
+  for (; e < total; e += step) {
+    const int q = (int)(e % cq) * VE;
+    const V x = X[e];
+    const BnVec<float, VE> m = bn_load_ch<VE>(mean + q), s = bn_load_ch<VE>(invstd + q);
+    const BnVec<float, VE> ww = bn_load_ch<VE>(w + q), bb = bn_load_ch<VE>(b + q);
+    V r;
+    if (RES) r = RES[e];
+    V y;
+    unsigned mk = 0;
+#pragma unroll
+    for (int i = 0; i < VE; ++i) {
+      float v = ((float)x.x[i] - m.x[i]) * s.x[i] * ww.x[i] + bb.x[i];
+      if (RES) v += (float)r.x[i];
+      if (relu) v = fmaxf(v, 0.f);
+      const T h = (T)v;
+      // the mask bit is the sign of the STORED value (what torch's ReLU backward looks at): a positive fp32 value below half's
+      // smallest subnormal rounds to zero and passes no gradient
+      if (relu) mk |= (h > (T)0 ? 1u : 0u) << i;
+      y.x[i] = h;
     }
-    if (relu) {
-      // 4-bit sign mask per float4 (1 byte per 16 bytes of activations): all the backward needs of `out`
-      if (MASK) MASK[e] = (unsigned char)((y.x > 0.f) | ((y.y > 0.f) << 1) | ((y.z > 0.f) << 2) | ((y.w > 0.f) << 3));
-      y.x = fmaxf(y.x, 0.f); y.y = fmaxf(y.y, 0.f); y.z = fmaxf(y.z, 0.f); y.w = fmaxf(y.w, 0.f);
-    }
+    if (relu && MASK) MASK[e] = (unsigned char)mk;
     OUT[e] = y;
   }
 }
@@ -120,110 +149,105 @@ __global__ __launch_bounds__(256) void bn_act_bwd_kernel(const float4 *__restric
 }
 
 static bool bn_aligned(const void *p) { return (((uintptr_t)p) & 15) == 0; }
+// the per-channel vectors that bn_load_ch<4> reads 16 bytes at a time
+template <int VE>
+static bool bn_ch_aligned(const float *p) { return VE != 4 || bn_aligned(p); }
 
-extern "C" int ts_bn_act_forward(const float *x, const float *residual, const float *mean, const float *invstd,
-                                 const float *weight, const float *bias, int64_t n, int32_t c, int32_t relu, float *out,
-                                 uint8_t *mask, ts_stream_t stream) {
-  TS_REQUIRE(n >= 0 && c > 0 && (c & 3) == 0, TS_ERR_UNSUPPORTED, "ts_bn_act_forward: C must be a multiple of 4");
-  if (n == 0) return TS_OK;
-  TS_REQUIRE(x && mean && invstd && weight && bias && out, TS_ERR_INVALID_ARGUMENT, "ts_bn_act_forward: null pointer");
-  TS_REQUIRE(bn_aligned(x) && bn_aligned(out) && bn_aligned(mean) && bn_aligned(invstd) && bn_aligned(weight) &&
-                 bn_aligned(bias) && (!residual || bn_aligned(residual)),
-             TS_ERR_INVALID_ARGUMENT, "ts_bn_act_forward: pointers must be 16-byte aligned");
-  const int64_t total4 = n * (c / 4);
-  const unsigned grid = (unsigned)std::min<int64_t>(ts_cdiv(total4, 256), 1 << 16);
-  bn_act_fwd_kernel<<<grid, 256, 0, (hipStream_t)stream>>>((const float4 *)x, (const float4 *)residual, mean, invstd,
-                                                           weight, bias, total4, c / 4, relu, (float4 *)out, mask);
-  TS_CHECK_LAUNCH("ts_bn_act_forward");
-  return TS_OK;
-}
-
-extern "C" int ts_bn_act_backward(const float *grad_out, const uint8_t *mask, const float *x, const float *mean,
-                                  const float *invstd, const float *weight, const double *sums, const double *total_dev,
-                                  double total_host, int64_t n, int32_t c, float *grad_x, float *grad_residual,
-                                  ts_stream_t stream) {
-  TS_REQUIRE(n >= 0 && c > 0 && (c & 3) == 0, TS_ERR_UNSUPPORTED, "ts_bn_act_backward: C must be a multiple of 4");
-  if (n == 0) return TS_OK;
-  TS_REQUIRE(grad_out && x && mean && invstd && weight && sums && grad_x, TS_ERR_INVALID_ARGUMENT,
-             "ts_bn_act_backward: null pointer");
-  TS_REQUIRE(total_dev || total_host > 0.0, TS_ERR_INVALID_ARGUMENT, "ts_bn_act_backward: empty batch");
-  TS_REQUIRE(bn_aligned(grad_out) && bn_aligned(x) && bn_aligned(grad_x) &&
-                 (!grad_residual || bn_aligned(grad_residual)) && bn_aligned(mean) && bn_aligned(invstd) &&
-                 bn_aligned(weight),
-             TS_ERR_INVALID_ARGUMENT, "ts_bn_act_backward: pointers must be 16-byte aligned");
-  const int64_t total4 = n * (c / 4);
-  const unsigned grid = (unsigned)std::min<int64_t>(ts_cdiv(total4, 256), 1 << 16);
-  bn_act_bwd_kernel<<<grid, 256, 0, (hipStream_t)stream>>>((const float4 *)grad_out, mask,
-                                                           (const float4 *)x, mean, invstd, weight, sums, total_dev,
-                                                           total_host, total4, c, (float4 *)grad_x,
-                                                           (float4 *)grad_residual);
-  TS_CHECK_LAUNCH("ts_bn_act_backward");
-  return TS_OK;
-}
-
-typedef _Float16 bn_h8 __attribute__((ext_vector_type(8)));
+// grid of an elementwise kernel over `total` chunks (grid-stride past 2^16 workgroups)
+static unsigned bn_grid(int64_t total) { return (unsigned)std::min<int64_t>(ts_cdiv(total, 256), 1 << 16); }
 
 // ------------------------------------------------------------------------------------------------------
 // Single-process training BatchNorm (+ residual) (+ ReLU), one host call per direction.
 //
-// The reductions above end in 2 C double atomics per workgroup into a zeroed buffer and are sized at 512 rows per
-// workgroup - 59 workgroups for a 30k-row matrix on a 256-CU device.  Here every launch is cut into <= 512
-// slices of at least 32 rows, each slice writes its float partial sums to scratch (no memset, no atomics, and the
-// result does not depend on the order workgroups finish in), and a small second kernel adds the partials in
-// double and finishes the per-channel math: mean / invstd / running statistics in the forward pass; grad_weight,
-// grad_bias and the two coefficients of the input gradient in the backward pass (which the elementwise kernel
-// then reads as floats instead of dividing doubles per element).
-//   forward   ts_bn_act_train_forward  = bn_partial<0> -> bn_fwd_finish -> bn_act_fwd
-//   backward  ts_bn_act_train_backward = bn_partial<1|2> -> bn_bwd_finish -> bn_act_bwd_coef
+// Every launch is cut into <= 512 slices of at least 32 rows, each slice writes its float partial sums to scratch (no
+// memset, no atomics, and the result does not depend on the order workgroups finish in), and a small second kernel adds
+// the partials in double and finishes the per-channel math: mean / invstd / running statistics in the forward pass;
+// grad_weight, grad_bias and the two coefficients of the input gradient in the backward pass (which the elementwise
+// kernel then reads as floats instead of dividing doubles per element).
+//   forward   bn_train_forward  = bn_partial<0> -> bn_fwd_finish -> bn_act_fwd
+//   backward  bn_train_backward = bn_partial<1|2> -> bn_bwd_finish -> bn_act_bwd_coef
 #define BN_MAX_SLICES 512
 
-// MODE 0: (x, x^2)   1: (dy, dy (x - mean))   2: same with the ReLU mask applied to dy
-template <int MODE>
-__global__ __launch_bounds__(256) void bn_partial_kernel(const float *__restrict__ X, const float *__restrict__ DY,
-                                                         const unsigned char *__restrict__ MASK,
-                                                         const float *__restrict__ mean, int64_t n, int c,
-                                                         int rows_per_wg, float *__restrict__ part) {
-  __shared__ float red[2][256 * 4];
-  const int cq = c >> 2, rpp = 256 / cq;
-  const int tid = threadIdx.x, ty = tid / cq, tx = tid - ty * cq;
-  const bool active = ty < rpp;
-  float4 s0 = make_float4(0.f, 0.f, 0.f, 0.f), s1 = s0, mu = s0;
-  if (MODE != 0 && active) mu = *(const float4 *)(mean + 4 * tx);
-  const int64_t r_beg = (int64_t)blockIdx.x * rows_per_wg, r_end = min(n, r_beg + rows_per_wg);
-  if (active) {
-#pragma unroll 4
-    for (int64_t r = r_beg + ty; r < r_end; r += rpp) {
-      const float4 x = *(const float4 *)(X + r * c + 4 * tx);
-      if (MODE == 0) {
-        s0.x += x.x; s0.y += x.y; s0.z += x.z; s0.w += x.w;
-        s1.x += x.x * x.x; s1.y += x.y * x.y; s1.z += x.z * x.z; s1.w += x.w * x.w;
-      } else {
-        float4 d = *(const float4 *)(DY + r * c + 4 * tx);
-        if (MODE == 2) {
-          const unsigned mk = MASK[r * cq + tx];
-          d.x = (mk & 1) ? d.x : 0.f; d.y = (mk & 2) ? d.y : 0.f;
-          d.z = (mk & 4) ? d.z : 0.f; d.w = (mk & 8) ? d.w : 0.f;
-        }
-        s0.x += d.x; s0.y += d.y; s0.z += d.z; s0.w += d.w;
-        s1.x += d.x * (x.x - mu.x); s1.y += d.y * (x.y - mu.y);
-        s1.z += d.z * (x.z - mu.z); s1.w += d.w * (x.w - mu.w);
-      }
-    }
-  }
-  *(float4 *)&red[0][tid * 4] = s0;
-  *(float4 *)&red[1][tid * 4] = s1;
+// rows per slice: whole passes of a workgroup, whose 256 threads cover 256 / (C / VE) rows at a time
+template <int VE>
+static inline int bn_rows_per_slice(int64_t n, int c) {
+  const int rpp = 256 / (c / VE);
+  const int64_t rows = std::max<int64_t>(ts_cdiv(n, BN_MAX_SLICES), 32);
+  return (int)(ts_cdiv(rows, rpp) * rpp);
+}
+
+// Tail of a partial-sums kernel: every lane's VE sums to LDS, the rpp lanes of a channel added in float in ascending order, two
+// floats per channel to the slice's partials [2][C].
+template <int VE>
+__device__ __forceinline__ void bn_fold_slice(const BnVec<float, VE> &s0, const BnVec<float, VE> &s1, float (&red)[2][256 * VE],
+                                              int c, int cq, int rpp, float *__restrict__ part) {
+  const int tid = threadIdx.x;
+  *(BnVec<float, VE> *)&red[0][tid * VE] = s0;
+  *(BnVec<float, VE> *)&red[1][tid * VE] = s1;
   __syncthreads();
   float *out = part + (int64_t)blockIdx.x * 2 * c;
   for (int ch = tid; ch < c; ch += 256) {
-    const int q = ch >> 2, l = ch & 3;
+    const int q = (unsigned)ch / VE, l = (unsigned)ch % VE;
     float a = 0.f, b = 0.f;
     for (int y = 0; y < rpp; ++y) {
-      a += red[0][(y * cq + q) * 4 + l];
-      b += red[1][(y * cq + q) * 4 + l];
+      a += red[0][(y * cq + q) * VE + l];
+      b += red[1][(y * cq + q) * VE + l];
     }
     out[ch] = a;
     out[c + ch] = b;
   }
+}
+
+// row-loop unroll depth of bn_partial_kernel: 64 bytes of a column in flight per thread and stream
+template <typename T>
+constexpr int bn_row_unroll = sizeof(T) == 4 ? 4 : 2;
+// waves per SIMD the compiler plans bn_partial_kernel for.  Half rows under the mask: 5 (94 VGPRs) - planning for 7 it fits 71
+// VGPRs by waiting for each row's loads before it issues the next one's, 0.0285 against 0.0259 ms at 178k x 32
+template <typename T, int MODE>
+constexpr int bn_partial_waves = sizeof(T) == 2 && MODE == 2 ? 5 : 8;
+
+// MODE 0: (x, x^2)   1: (dy, dy (x - mean))   2: same with the ReLU mask applied to dy
+// The second sum takes every product by a fused multiply-add, written out so that the rounding does not hang on what the compiler
+// contracts (left to it, the half form once kept two channels of eight on a multiply and an add).
+template <typename T, int VE, int MODE>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, bn_partial_waves<T, MODE>)))
+void bn_partial_kernel(const T *__restrict__ X, const T *__restrict__ DY, const unsigned char *__restrict__ MASK,
+                       const float *__restrict__ mean, int64_t n, int c, int rows_per_wg, float *__restrict__ part) {
+  using V = BnVec<T, VE>;
+  __shared__ float red[2][256 * VE];
+  const int cq = c / VE, rpp = 256 / cq;
+  const int tid = threadIdx.x, ty = tid / cq, tx = tid - ty * cq;
+  const bool active = ty < rpp;
+  BnVec<float, VE> s0 = {}, s1 = {}, mu = {};
+  if (MODE != 0 && active) mu = bn_load_ch<VE>(mean + VE * tx);
+  const int64_t r_beg = (int64_t)blockIdx.x * rows_per_wg, r_end = min(n, r_beg + rows_per_wg);
+  if (active) {
+#pragma unroll bn_row_unroll<T>
+    for (int64_t r = r_beg + ty; r < r_end; r += rpp) {
+      // the row is read in place: with a local copy of the chunk in this loop the compiler no longer counts its trips and unrolls it
+      // with an exit test between the rows instead of a remainder loop (4 to 10 VGPRs more, an occupancy step in MODE 1 and 2)
+      const V &x = *(const V *)(X + r * c + VE * tx);
+      if (MODE == 0) {
+#pragma unroll
+        for (int i = 0; i < VE; ++i) {
+          const float v = (float)x.x[i];
+          s0.x[i] += v;
+          s1.x[i] = __builtin_fmaf(v, v, s1.x[i]);
+        }
+      } else {
+        const V &d = *(const V *)(DY + r * c + VE * tx);
+        const unsigned mk = MODE == 2 ? MASK[r * cq + tx] : 0xFFu;
+#pragma unroll
+        for (int i = 0; i < VE; ++i) {
+          const float dy = (float)d.x[i];                       // read before the test: every lane loads its whole chunk
+          const float dv = ((mk >> i) & 1) ? dy : 0.f;
+          s0.x[i] += dv;
+          s1.x[i] = __builtin_fmaf(dv, (float)x.x[i] - mu.x[i], s1.x[i]);
+        }
+      }
+    }
+  }
+  bn_fold_slice<VE>(s0, s1, red, c, cq, rpp, part);
 }
 
 // 8 channels per workgroup, 32 lanes per channel over the slices (<= 16 partials per lane, all loads issued
@@ -303,123 +327,33 @@ __global__ __launch_bounds__(256) void bn_bwd_finish_kernel(const float *__restr
   if (grad_weight) grad_weight[ch] = (float)s1 * is;
 }
 
-__global__ __launch_bounds__(256) void bn_act_bwd_coef_kernel(const float4 *__restrict__ GOUT,
+template <typename T, int VE>
+__global__ __launch_bounds__(256) void bn_act_bwd_coef_kernel(const BnVec<T, VE> *__restrict__ GOUT,
                                                               const unsigned char *__restrict__ MASK,
-                                                              const float4 *__restrict__ X,
-                                                              const float *__restrict__ mean,
-                                                              const float *__restrict__ invstd,
-                                                              const float *__restrict__ w,
-                                                              const float *__restrict__ coef, int64_t total4, int c,
-                                                              float4 *__restrict__ GX, float4 *__restrict__ GRES) {
-  const int cq = c >> 2;
+                                                              const BnVec<T, VE> *__restrict__ X, const float *__restrict__ mean,
+                                                              const float *__restrict__ invstd, const float *__restrict__ w,
+                                                              const float *__restrict__ coef, int64_t total, int c,
+                                                              BnVec<T, VE> *__restrict__ GX, BnVec<T, VE> *__restrict__ GRES) {
+  using V = BnVec<T, VE>;
+  const int cq = c / VE;
   int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t step = (int64_t)gridDim.x * blockDim.x;
-  for (; e < total4; e += step) {
-    const int q = (int)(e % cq) * 4;
-    float4 g = GOUT[e];
-    if (MASK) {
-      const unsigned mk = MASK[e];
-      g.x = (mk & 1) ? g.x : 0.f; g.y = (mk & 2) ? g.y : 0.f;
-      g.z = (mk & 4) ? g.z : 0.f; g.w = (mk & 8) ? g.w : 0.f;
+  for (; e < total; e += step) {
+    const int q = (int)(e % cq) * VE;
+    const V gin = GOUT[e], x = X[e];
+    const unsigned mk = MASK ? MASK[e] : 0xFFu;
+    const BnVec<float, VE> m = bn_load_ch<VE>(mean + q), s = bn_load_ch<VE>(invstd + q), ww = bn_load_ch<VE>(w + q);
+    const BnVec<float, VE> c0 = bn_load_ch<VE>(coef + q), c1 = bn_load_ch<VE>(coef + c + q);
+    V g, gx;
+#pragma unroll
+    for (int i = 0; i < VE; ++i) {
+      const float gv = ((mk >> i) & 1) ? (float)gin.x[i] : 0.f;
+      g.x[i] = (T)gv;
+      gx.x[i] = (T)((gv - c0.x[i] - ((float)x.x[i] - m.x[i]) * c1.x[i]) * s.x[i] * ww.x[i]);
     }
     if (GRES) GRES[e] = g;
-    const float4 x = X[e];
-    const float4 m = *(const float4 *)(mean + q), s = *(const float4 *)(invstd + q), ww = *(const float4 *)(w + q);
-    const float4 c0 = *(const float4 *)(coef + q), c1 = *(const float4 *)(coef + c + q);
-    float4 gx;
-    gx.x = (g.x - c0.x - (x.x - m.x) * c1.x) * s.x * ww.x;
-    gx.y = (g.y - c0.y - (x.y - m.y) * c1.y) * s.y * ww.y;
-    gx.z = (g.z - c0.z - (x.z - m.z) * c1.z) * s.z * ww.z;
-    gx.w = (g.w - c0.w - (x.w - m.w) * c1.w) * s.w * ww.w;
     GX[e] = gx;
   }
-}
-
-static inline int bn_rows_per_slice(int64_t n, int c) {
-  const int rpp = 256 / (c >> 2);                       // rows one pass of a workgroup covers
-  int64_t rows = std::max<int64_t>(ts_cdiv(n, BN_MAX_SLICES), 32);
-  rows = ts_cdiv(rows, rpp) * rpp;                      // whole passes
-  return (int)rows;
-}
-
-// TS_OPT_DEBUG_BN_ABLATE (diagnostic, fp32 path).  Bits 0 / 1 (WRONG results, timing only): skip the forward statistics pass
-// (bn_partial<0>) / the forward elementwise pass of the blocks without a residual.  Garbage activations also change what the
-// chip draws, so the CLEAN measurement is bits 2 / 3: run the same pass TWICE (same results) - the step's slow-down is what one such
-// pass costs in the step, launch gap included: the most "statistics in the epilogue of the pass that produces y" / "normalise where
-// the consumer gathers the row" could save.
-static int bn_debug_ablate() { return (int)ts_get_option(TS_OPT_DEBUG_BN_ABLATE); }
-
-extern "C" size_t ts_bn_train_workspace_bytes(int32_t c) {
-  // float partials [BN_MAX_SLICES][2][C] + float coefficients [2][C]
-  return ((size_t)BN_MAX_SLICES * 2 * c + 2 * (size_t)c) * sizeof(float);
-}
-
-extern "C" int ts_bn_act_train_forward(const float *x, const float *residual, const float *weight, const float *bias,
-                                       float *running_mean, float *running_var, int64_t *num_batches_tracked,
-                                       int64_t n, int32_t c, float eps, float momentum, int32_t relu, float *mean,
-                                       float *invstd, float *out, uint8_t *mask, void *ws, size_t ws_bytes,
-                                       ts_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  TS_REQUIRE(n > 0 && c > 0 && (c & 3) == 0 && c <= 1024, TS_ERR_UNSUPPORTED,
-             "ts_bn_act_train_forward: need N > 0 and C a multiple of 4, <= 1024");
-  TS_REQUIRE(x && weight && bias && mean && invstd && out && ws, TS_ERR_INVALID_ARGUMENT,
-             "ts_bn_act_train_forward: null pointer");
-  TS_REQUIRE(ws_bytes >= ts_bn_train_workspace_bytes(c), TS_ERR_INVALID_ARGUMENT,
-             "ts_bn_act_train_forward: workspace too small");
-  TS_REQUIRE(bn_aligned(x) && bn_aligned(out) && bn_aligned(mean) && bn_aligned(invstd) && bn_aligned(weight) &&
-                 bn_aligned(bias) && (!residual || bn_aligned(residual)) && bn_aligned(ws),
-             TS_ERR_INVALID_ARGUMENT, "ts_bn_act_train_forward: pointers must be 16-byte aligned");
-  float *part = (float *)ws;
-  const int rows = bn_rows_per_slice(n, c);
-  const int slices = (int)ts_cdiv(n, rows);
-  const int ablate = bn_debug_ablate();       // diagnostic (wrong results, timing only): upper bounds of two fusions, see below
-  if (!(ablate & 1)) bn_partial_kernel<0><<<slices, 256, 0, stream>>>(x, nullptr, nullptr, nullptr, n, c, rows, part);
-  if (ablate & 4) bn_partial_kernel<0><<<slices, 256, 0, stream>>>(x, nullptr, nullptr, nullptr, n, c, rows, part);   // the pass once more
-  bn_fwd_finish_kernel<<<(unsigned)ts_cdiv(c, BN_FIN_CH), 256, 0, stream>>>(part, slices, (double)n, c, eps, momentum,
-                                                                     running_mean, running_var, mean, invstd,
-                                                                     num_batches_tracked);
-  const int64_t total4 = n * (c / 4);
-  const unsigned grid = (unsigned)std::min<int64_t>(ts_cdiv(total4, 256), 1 << 16);
-  if (!((ablate & 2) && !residual && relu))
-    bn_act_fwd_kernel<<<grid, 256, 0, stream>>>((const float4 *)x, (const float4 *)residual, mean, invstd, weight, bias,
-                                                total4, c / 4, relu, (float4 *)out, mask);
-  if ((ablate & 8) && !residual && relu)          // the same pass once more (same results)
-    bn_act_fwd_kernel<<<grid, 256, 0, stream>>>((const float4 *)x, (const float4 *)residual, mean, invstd, weight, bias,
-                                                total4, c / 4, relu, (float4 *)out, mask);
-  TS_CHECK_LAUNCH("ts_bn_act_train_forward");
-  return TS_OK;
-}
-
-extern "C" int ts_bn_act_train_backward(const float *grad_out, const uint8_t *mask, const float *x, const float *mean,
-                                        const float *invstd, const float *weight, int64_t n, int32_t c, float *grad_x,
-                                        float *grad_residual, float *grad_weight, float *grad_bias, void *ws,
-                                        size_t ws_bytes, ts_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  TS_REQUIRE(n > 0 && c > 0 && (c & 3) == 0 && c <= 1024, TS_ERR_UNSUPPORTED,
-             "ts_bn_act_train_backward: need N > 0 and C a multiple of 4, <= 1024");
-  TS_REQUIRE(grad_out && x && mean && invstd && weight && grad_x && ws, TS_ERR_INVALID_ARGUMENT,
-             "ts_bn_act_train_backward: null pointer");
-  TS_REQUIRE(ws_bytes >= ts_bn_train_workspace_bytes(c), TS_ERR_INVALID_ARGUMENT,
-             "ts_bn_act_train_backward: workspace too small");
-  TS_REQUIRE(bn_aligned(grad_out) && bn_aligned(x) && bn_aligned(grad_x) && bn_aligned(mean) && bn_aligned(invstd) &&
-                 bn_aligned(weight) && (!grad_residual || bn_aligned(grad_residual)) && bn_aligned(ws),
-             TS_ERR_INVALID_ARGUMENT, "ts_bn_act_train_backward: pointers must be 16-byte aligned");
-  float *part = (float *)ws;
-  float *coef = part + (size_t)BN_MAX_SLICES * 2 * c;
-  const int rows = bn_rows_per_slice(n, c);
-  const int slices = (int)ts_cdiv(n, rows);
-  if (mask)
-    bn_partial_kernel<2><<<slices, 256, 0, stream>>>(x, grad_out, mask, mean, n, c, rows, part);
-  else
-    bn_partial_kernel<1><<<slices, 256, 0, stream>>>(x, grad_out, nullptr, mean, n, c, rows, part);
-  bn_bwd_finish_kernel<<<(unsigned)ts_cdiv(c, BN_FIN_CH), 256, 0, stream>>>(part, slices, (double)n, c, invstd, coef,
-                                                                     grad_weight, grad_bias);
-  const int64_t total4 = n * (c / 4);
-  const unsigned grid = (unsigned)std::min<int64_t>(ts_cdiv(total4, 256), 1 << 16);
-  bn_act_bwd_coef_kernel<<<grid, 256, 0, stream>>>((const float4 *)grad_out, mask, (const float4 *)x, mean, invstd,
-                                                   weight, coef, total4, c, (float4 *)grad_x, (float4 *)grad_residual);
-  TS_CHECK_LAUNCH("ts_bn_act_train_backward");
-  return TS_OK;
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -444,245 +378,7 @@ __global__ __launch_bounds__(256) void bn_sums_finish_kernel(const float *__rest
   if (grad_weight) grad_weight[ch] = (float)s1 * invstd[ch];
 }
 
-extern "C" int ts_bn_sync_stats(const float *x, int64_t n, int32_t c, double *pack, void *ws, size_t ws_bytes,
-                                ts_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  TS_REQUIRE(n > 0 && c > 0 && (c & 3) == 0 && c <= 1024, TS_ERR_UNSUPPORTED,
-             "ts_bn_sync_stats: need N > 0 and C a multiple of 4, <= 1024");
-  TS_REQUIRE(x && pack && ws && bn_aligned(x) && bn_aligned(ws), TS_ERR_INVALID_ARGUMENT, "ts_bn_sync_stats: bad pointer");
-  TS_REQUIRE(ws_bytes >= ts_bn_train_workspace_bytes(c), TS_ERR_INVALID_ARGUMENT, "ts_bn_sync_stats: workspace too small");
-  float *part = (float *)ws;
-  const int rows = bn_rows_per_slice(n, c);
-  const int slices = (int)ts_cdiv(n, rows);
-  bn_partial_kernel<0><<<slices, 256, 0, stream>>>(x, nullptr, nullptr, nullptr, n, c, rows, part);
-  bn_sums_finish_kernel<<<(unsigned)ts_cdiv(c, BN_FIN_CH), 256, 0, stream>>>(part, slices, c, (double)n, nullptr, pack,
-                                                                           nullptr, nullptr);
-  TS_CHECK_LAUNCH("ts_bn_sync_stats");
-  return TS_OK;
-}
-
-extern "C" int ts_bn_sync_backward_reduce(const float *grad_out, const uint8_t *mask, const float *x, const float *mean,
-                                          const float *invstd, int64_t n, int32_t c, double *sums, float *grad_weight,
-                                          float *grad_bias, void *ws, size_t ws_bytes, ts_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  TS_REQUIRE(n > 0 && c > 0 && (c & 3) == 0 && c <= 1024, TS_ERR_UNSUPPORTED,
-             "ts_bn_sync_backward_reduce: need N > 0 and C a multiple of 4, <= 1024");
-  TS_REQUIRE(grad_out && x && mean && invstd && sums && ws, TS_ERR_INVALID_ARGUMENT,
-             "ts_bn_sync_backward_reduce: null pointer");
-  TS_REQUIRE(bn_aligned(grad_out) && bn_aligned(x) && bn_aligned(mean) && bn_aligned(ws), TS_ERR_INVALID_ARGUMENT,
-             "ts_bn_sync_backward_reduce: pointers must be 16-byte aligned");
-  TS_REQUIRE(ws_bytes >= ts_bn_train_workspace_bytes(c), TS_ERR_INVALID_ARGUMENT,
-             "ts_bn_sync_backward_reduce: workspace too small");
-  float *part = (float *)ws;
-  const int rows = bn_rows_per_slice(n, c);
-  const int slices = (int)ts_cdiv(n, rows);
-  if (mask)
-    bn_partial_kernel<2><<<slices, 256, 0, stream>>>(x, grad_out, mask, mean, n, c, rows, part);
-  else
-    bn_partial_kernel<1><<<slices, 256, 0, stream>>>(x, grad_out, nullptr, mean, n, c, rows, part);
-  bn_sums_finish_kernel<<<(unsigned)ts_cdiv(c, BN_FIN_CH), 256, 0, stream>>>(part, slices, c, -1.0, invstd, sums,
-                                                                           grad_weight, grad_bias);
-  TS_CHECK_LAUNCH("ts_bn_sync_backward_reduce");
-  return TS_OK;
-}
-
-// ------------------------------------------------------------------------------------------------------
-// Half-storage variants of the single-process training BatchNorm (+ residual) (+ ReLU): activations, residual and
-// gradients are IEEE half in HBM, every reduction / normalisation runs in fp32 (statistics, affine parameters and
-// parameter gradients stay fp32, as under torch.autocast).  One thread handles 8 channels (one 16-byte chunk);
-// the ReLU mask keeps 1 bit per element (one byte per chunk).
-
-template <int MODE>
-__global__ __launch_bounds__(256) void bn_partial_h_kernel(const _Float16 *__restrict__ X,
-                                                           const _Float16 *__restrict__ DY,
-                                                           const unsigned char *__restrict__ MASK,
-                                                           const float *__restrict__ mean, int64_t n, int c,
-                                                           int rows_per_wg, float *__restrict__ part) {
-  __shared__ float red[2][256 * 8];
-  const int cq = c >> 3, rpp = 256 / cq;
-  const int tid = threadIdx.x, ty = tid / cq, tx = tid - ty * cq;
-  const bool active = ty < rpp;
-  float s0[8], s1[8], mu[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) s0[i] = s1[i] = mu[i] = 0.f;
-  if (MODE != 0 && active) {
-#pragma unroll
-    for (int i = 0; i < 8; ++i) mu[i] = mean[8 * tx + i];
-  }
-  const int64_t r_beg = (int64_t)blockIdx.x * rows_per_wg, r_end = min(n, r_beg + rows_per_wg);
-  if (active) {
-#pragma unroll 2
-    for (int64_t r = r_beg + ty; r < r_end; r += rpp) {
-      const bn_h8 x = *(const bn_h8 *)(X + r * c + 8 * tx);
-      if (MODE == 0) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          const float v = (float)x[i];
-          s0[i] += v;
-          s1[i] += v * v;
-        }
-      } else {
-        const bn_h8 d = *(const bn_h8 *)(DY + r * c + 8 * tx);
-        const unsigned mk = MODE == 2 ? MASK[r * cq + tx] : 0xFFu;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          const float dv = ((mk >> i) & 1) ? (float)d[i] : 0.f;
-          s0[i] += dv;
-          s1[i] += dv * ((float)x[i] - mu[i]);
-        }
-      }
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    red[0][tid * 8 + i] = s0[i];
-    red[1][tid * 8 + i] = s1[i];
-  }
-  __syncthreads();
-  float *out = part + (int64_t)blockIdx.x * 2 * c;
-  for (int ch = tid; ch < c; ch += 256) {
-    const int q = ch >> 3, l = ch & 7;
-    float a = 0.f, b = 0.f;
-    for (int y = 0; y < rpp; ++y) {
-      a += red[0][(y * cq + q) * 8 + l];
-      b += red[1][(y * cq + q) * 8 + l];
-    }
-    out[ch] = a;
-    out[c + ch] = b;
-  }
-}
-
-__global__ __launch_bounds__(256) void bn_act_fwd_h_kernel(const bn_h8 *__restrict__ X, const bn_h8 *__restrict__ RES,
-                                                           const float *__restrict__ mean,
-                                                           const float *__restrict__ invstd,
-                                                           const float *__restrict__ w, const float *__restrict__ b,
-                                                           int64_t total8, int cq, int relu, bn_h8 *__restrict__ OUT,
-                                                           unsigned char *__restrict__ MASK) {
-  int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int64_t step = (int64_t)gridDim.x * blockDim.x;
-  for (; e < total8; e += step) {
-    const int q = (int)(e % cq) * 8;
-    const bn_h8 x = X[e];
-    bn_h8 r;
-    if (RES) r = RES[e];
-    bn_h8 y;
-    unsigned mk = 0;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      float v = ((float)x[i] - mean[q + i]) * invstd[q + i] * w[q + i] + b[q + i];
-      if (RES) v += (float)r[i];
-      if (relu) v = fmaxf(v, 0.f);
-      const _Float16 h = (_Float16)v;
-      // the mask bit is the sign of the STORED value (what torch's ReLU backward looks at): a positive fp32 value below half's
-      // smallest subnormal rounds to zero and passes no gradient
-      if (relu) mk |= (h > (_Float16)0 ? 1u : 0u) << i;
-      y[i] = h;
-    }
-    if (relu && MASK) MASK[e] = (unsigned char)mk;
-    OUT[e] = y;
-  }
-}
-
-__global__ __launch_bounds__(256) void bn_act_bwd_coef_h_kernel(const bn_h8 *__restrict__ GOUT,
-                                                                const unsigned char *__restrict__ MASK,
-                                                                const bn_h8 *__restrict__ X,
-                                                                const float *__restrict__ mean,
-                                                                const float *__restrict__ invstd,
-                                                                const float *__restrict__ w,
-                                                                const float *__restrict__ coef, int64_t total8, int c,
-                                                                bn_h8 *__restrict__ GX, bn_h8 *__restrict__ GRES) {
-  const int cq = c >> 3;
-  int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int64_t step = (int64_t)gridDim.x * blockDim.x;
-  for (; e < total8; e += step) {
-    const int q = (int)(e % cq) * 8;
-    const bn_h8 gin = GOUT[e], x = X[e];
-    const unsigned mk = MASK ? MASK[e] : 0xFFu;
-    bn_h8 g, gx;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const float gv = ((mk >> i) & 1) ? (float)gin[i] : 0.f;
-      g[i] = (_Float16)gv;
-      const float is = invstd[q + i];
-      gx[i] = (_Float16)((gv - coef[q + i] - ((float)x[i] - mean[q + i]) * coef[c + q + i]) * is * w[q + i]);
-    }
-    if (GRES) GRES[e] = g;
-    GX[e] = gx;
-  }
-}
-
-static inline int bn_rows_per_slice_h(int64_t n, int c) {
-  const int rpp = 256 / (c >> 3);
-  int64_t rows = std::max<int64_t>(ts_cdiv(n, BN_MAX_SLICES), 32);
-  rows = ts_cdiv(rows, rpp) * rpp;
-  return (int)rows;
-}
-
-extern "C" int ts_bn_act_train_forward_f16(const void *x, const void *residual, const float *weight, const float *bias,
-                                           float *running_mean, float *running_var, int64_t *num_batches_tracked,
-                                           int64_t n, int32_t c, float eps, float momentum, int32_t relu, float *mean,
-                                           float *invstd, void *out, uint8_t *mask, void *ws, size_t ws_bytes,
-                                           ts_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  TS_REQUIRE(n > 0 && c > 0 && (c & 7) == 0 && c <= 2048, TS_ERR_UNSUPPORTED,
-             "ts_bn_act_train_forward_f16: need N > 0 and C a multiple of 8, <= 2048");
-  TS_REQUIRE(x && weight && bias && mean && invstd && out && ws, TS_ERR_INVALID_ARGUMENT,
-             "ts_bn_act_train_forward_f16: null pointer");
-  TS_REQUIRE(ws_bytes >= ts_bn_train_workspace_bytes(c), TS_ERR_INVALID_ARGUMENT,
-             "ts_bn_act_train_forward_f16: workspace too small");
-  TS_REQUIRE(bn_aligned(x) && bn_aligned(out) && (!residual || bn_aligned(residual)) && bn_aligned(ws),
-             TS_ERR_INVALID_ARGUMENT, "ts_bn_act_train_forward_f16: pointers must be 16-byte aligned");
-  float *part = (float *)ws;
-  const int rows = bn_rows_per_slice_h(n, c);
-  const int slices = (int)ts_cdiv(n, rows);
-  bn_partial_h_kernel<0><<<slices, 256, 0, stream>>>((const _Float16 *)x, nullptr, nullptr, nullptr, n, c, rows, part);
-  bn_fwd_finish_kernel<<<(unsigned)ts_cdiv(c, BN_FIN_CH), 256, 0, stream>>>(part, slices, (double)n, c, eps, momentum,
-                                                                           running_mean, running_var, mean, invstd,
-                                                                           num_batches_tracked);
-  const int64_t total8 = n * (c / 8);
-  const unsigned grid = (unsigned)std::min<int64_t>(ts_cdiv(total8, 256), 1 << 16);
-  bn_act_fwd_h_kernel<<<grid, 256, 0, stream>>>((const bn_h8 *)x, (const bn_h8 *)residual, mean, invstd, weight, bias,
-                                                total8, c / 8, relu, (bn_h8 *)out, mask);
-  TS_CHECK_LAUNCH("ts_bn_act_train_forward_f16");
-  return TS_OK;
-}
-
-extern "C" int ts_bn_act_train_backward_f16(const void *grad_out, const uint8_t *mask, const void *x, const float *mean,
-                                            const float *invstd, const float *weight, int64_t n, int32_t c,
-                                            void *grad_x, void *grad_residual, float *grad_weight, float *grad_bias,
-                                            void *ws, size_t ws_bytes, ts_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  TS_REQUIRE(n > 0 && c > 0 && (c & 7) == 0 && c <= 2048, TS_ERR_UNSUPPORTED,
-             "ts_bn_act_train_backward_f16: need N > 0 and C a multiple of 8, <= 2048");
-  TS_REQUIRE(grad_out && x && mean && invstd && weight && grad_x && ws, TS_ERR_INVALID_ARGUMENT,
-             "ts_bn_act_train_backward_f16: null pointer");
-  TS_REQUIRE(ws_bytes >= ts_bn_train_workspace_bytes(c), TS_ERR_INVALID_ARGUMENT,
-             "ts_bn_act_train_backward_f16: workspace too small");
-  TS_REQUIRE(bn_aligned(grad_out) && bn_aligned(x) && bn_aligned(grad_x) && (!grad_residual || bn_aligned(grad_residual)) &&
-                 bn_aligned(ws), TS_ERR_INVALID_ARGUMENT, "ts_bn_act_train_backward_f16: pointers must be 16-byte aligned");
-  float *part = (float *)ws;
-  float *coef = part + (size_t)BN_MAX_SLICES * 2 * c;
-  const int rows = bn_rows_per_slice_h(n, c);
-  const int slices = (int)ts_cdiv(n, rows);
-  if (mask)
-    bn_partial_h_kernel<2><<<slices, 256, 0, stream>>>((const _Float16 *)x, (const _Float16 *)grad_out, mask, mean, n, c,
-                                                       rows, part);
-  else
-    bn_partial_h_kernel<1><<<slices, 256, 0, stream>>>((const _Float16 *)x, (const _Float16 *)grad_out, nullptr, mean, n,
-                                                       c, rows, part);
-  bn_bwd_finish_kernel<<<(unsigned)ts_cdiv(c, BN_FIN_CH), 256, 0, stream>>>(part, slices, (double)n, c, invstd, coef,
-                                                                           grad_weight, grad_bias);
-  const int64_t total8 = n * (c / 8);
-  const unsigned grid = (unsigned)std::min<int64_t>(ts_cdiv(total8, 256), 1 << 16);
-  bn_act_bwd_coef_h_kernel<<<grid, 256, 0, stream>>>((const bn_h8 *)grad_out, mask, (const bn_h8 *)x, mean, invstd, weight,
-                                                     coef, total8, c, (bn_h8 *)grad_x, (bn_h8 *)grad_residual);
-  TS_CHECK_LAUNCH("ts_bn_act_train_backward_f16");
-  return TS_OK;
-}
-
-// ------------------------------------------------------------------------------------------------------
-// SyncBatchNorm halves for half-storage activations (the reference's actual recipe is AMP + DDP + SyncBatchNorm,
-// R/dist_train.sh:17-19): the same double sums cross the ranks, activations and gradients stay half in HBM.
+// the two float coefficients of bn_act_bwd_coef_kernel from all-reduced double sums
 __global__ void bn_coef_from_sums_kernel(const double *__restrict__ sums, const double *__restrict__ total_dev,
                                          double total_host, const float *__restrict__ invstd, int c,
                                          float *__restrict__ coef) {
@@ -694,95 +390,290 @@ __global__ void bn_coef_from_sums_kernel(const double *__restrict__ sums, const 
   coef[c + ch] = (float)(sums[c + ch] / total) * is * is;
 }
 
-static int bn_h_check(const char *what, int64_t n, int32_t c) {
-  TS_REQUIRE(n > 0 && c > 0 && (c & 7) == 0 && c <= 2048, TS_ERR_UNSUPPORTED, "%s: need N > 0 and C a multiple of 8, <= 2048",
-             what);
+// ------------------------------------------------------------------------------------------------------
+// Host side: one driver per operation on <T, VE>; `what` is the entry point's name in every message.
+//   <float, 4>     C % 4, C <= 1024, the per-channel vectors a kernel reads 16-byte aligned
+//   <_Float16, 8>  C % 8, C <= 2048, no alignment demand on the per-channel vectors
+
+// TS_OPT_DEBUG_BN_ABLATE (diagnostic, fp32 path).  Bits 0 / 1 (WRONG results, timing only): skip the forward statistics pass
+// (bn_partial<0>) / the forward elementwise pass of the blocks without a residual.  Garbage activations also change what the
+// chip draws, so the CLEAN measurement is bits 2 / 3: run the same pass TWICE (same results) - the step's slow-down is what one such
+// pass costs in the step, launch gap included: the most "statistics in the epilogue of the pass that produces y" / "normalise where
+// the consumer gathers the row" could save.
+static int bn_debug_ablate() { return (int)ts_get_option(TS_OPT_DEBUG_BN_ABLATE); }
+
+extern "C" size_t ts_bn_train_workspace_bytes(int32_t c) {
+  // float partials [BN_MAX_SLICES][2][C] + float coefficients [2][C]
+  return ((size_t)BN_MAX_SLICES * 2 * c + 2 * (size_t)c) * sizeof(float);
+}
+
+template <int VE>
+static int bn_check_size(const char *what, int64_t n, int32_t c) {
+  TS_REQUIRE(n > 0 && c > 0 && c % VE == 0 && c <= 256 * VE, TS_ERR_UNSUPPORTED, "%s: need N > 0 and C a multiple of %d, <= %d", what,
+             VE, 256 * VE);
   return TS_OK;
 }
 
-extern "C" int ts_bn_sync_stats_f16(const void *x, int64_t n, int32_t c, double *pack, void *ws, size_t ws_bytes,
-                                    ts_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  int rc = bn_h_check("ts_bn_sync_stats_f16", n, c);
-  if (rc != TS_OK) return rc;
-  TS_REQUIRE(x && pack && ws && bn_aligned(x) && bn_aligned(ws), TS_ERR_INVALID_ARGUMENT, "ts_bn_sync_stats_f16: bad pointer");
-  TS_REQUIRE(ws_bytes >= ts_bn_train_workspace_bytes(c), TS_ERR_INVALID_ARGUMENT, "ts_bn_sync_stats_f16: workspace too small");
-  float *part = (float *)ws;
-  const int rows = bn_rows_per_slice_h(n, c);
+// the sliced sums of one matrix into part [slices][2][C]; MODE from the arguments: no dy = 0, dy = 1, dy and mask = 2
+template <typename T, int VE>
+static int bn_launch_partial(const void *x, const void *dy, const uint8_t *mask, const float *mean, int64_t n, int c, float *part,
+                             hipStream_t stream) {
+  const int rows = bn_rows_per_slice<VE>(n, c);
   const int slices = (int)ts_cdiv(n, rows);
-  bn_partial_h_kernel<0><<<slices, 256, 0, stream>>>((const _Float16 *)x, nullptr, nullptr, nullptr, n, c, rows, part);
-  bn_sums_finish_kernel<<<(unsigned)ts_cdiv(c, BN_FIN_CH), 256, 0, stream>>>(part, slices, c, (double)n, nullptr, pack,
-                                                                           nullptr, nullptr);
-  TS_CHECK_LAUNCH("ts_bn_sync_stats_f16");
+  if (!dy)
+    bn_partial_kernel<T, VE, 0><<<slices, 256, 0, stream>>>((const T *)x, nullptr, nullptr, nullptr, n, c, rows, part);
+  else if (mask)
+    bn_partial_kernel<T, VE, 2><<<slices, 256, 0, stream>>>((const T *)x, (const T *)dy, mask, mean, n, c, rows, part);
+  else
+    bn_partial_kernel<T, VE, 1><<<slices, 256, 0, stream>>>((const T *)x, (const T *)dy, nullptr, mean, n, c, rows, part);
+  return slices;
+}
+
+template <typename T, int VE>
+static void bn_launch_act_fwd(const void *x, const void *residual, const float *mean, const float *invstd, const float *weight,
+                              const float *bias, int64_t n, int c, int relu, void *out, uint8_t *mask, hipStream_t stream) {
+  using V = BnVec<T, VE>;
+  const int64_t total = n * (c / VE);
+  bn_act_fwd_kernel<T, VE><<<bn_grid(total), 256, 0, stream>>>((const V *)x, (const V *)residual, mean, invstd, weight, bias, total,
+                                                               c / VE, relu, (V *)out, mask);
+}
+
+template <typename T, int VE>
+static void bn_launch_act_bwd_coef(const void *grad_out, const uint8_t *mask, const void *x, const float *mean, const float *invstd,
+                                   const float *weight, const float *coef, int64_t n, int c, void *grad_x, void *grad_residual,
+                                   hipStream_t stream) {
+  using V = BnVec<T, VE>;
+  const int64_t total = n * (c / VE);
+  bn_act_bwd_coef_kernel<T, VE><<<bn_grid(total), 256, 0, stream>>>((const V *)grad_out, mask, (const V *)x, mean, invstd, weight,
+                                                                    coef, total, c, (V *)grad_x, (V *)grad_residual);
+}
+
+template <typename T, int VE>
+static int bn_train_forward(const char *what, const void *x, const void *residual, const float *weight, const float *bias,
+                            float *running_mean, float *running_var, int64_t *num_batches_tracked, int64_t n, int32_t c, float eps,
+                            float momentum, int32_t relu, float *mean, float *invstd, void *out, uint8_t *mask, void *ws,
+                            size_t ws_bytes, hipStream_t stream) {
+  const int rc = bn_check_size<VE>(what, n, c);
+  if (rc != TS_OK) return rc;
+  TS_REQUIRE(x && weight && bias && mean && invstd && out && ws, TS_ERR_INVALID_ARGUMENT, "%s: null pointer", what);
+  TS_REQUIRE(ws_bytes >= ts_bn_train_workspace_bytes(c), TS_ERR_INVALID_ARGUMENT, "%s: workspace too small", what);
+  TS_REQUIRE(bn_aligned(x) && bn_aligned(out) && bn_ch_aligned<VE>(mean) && bn_ch_aligned<VE>(invstd) && bn_ch_aligned<VE>(weight) &&
+                 bn_ch_aligned<VE>(bias) && (!residual || bn_aligned(residual)) && bn_aligned(ws),
+             TS_ERR_INVALID_ARGUMENT, "%s: pointers must be 16-byte aligned", what);
+  float *part = (float *)ws;
+  const int ablate = sizeof(T) == 4 ? bn_debug_ablate() : 0;   // diagnostic (wrong results, timing only), see above
+  int slices = (int)ts_cdiv(n, bn_rows_per_slice<VE>(n, c));
+  if (!(ablate & 1)) slices = bn_launch_partial<T, VE>(x, nullptr, nullptr, nullptr, n, c, part, stream);
+  if (ablate & 4) bn_launch_partial<T, VE>(x, nullptr, nullptr, nullptr, n, c, part, stream);   // the pass once more
+  bn_fwd_finish_kernel<<<(unsigned)ts_cdiv(c, BN_FIN_CH), 256, 0, stream>>>(part, slices, (double)n, c, eps, momentum, running_mean,
+                                                                           running_var, mean, invstd, num_batches_tracked);
+  if (!((ablate & 2) && !residual && relu))
+    bn_launch_act_fwd<T, VE>(x, residual, mean, invstd, weight, bias, n, c, relu, out, mask, stream);
+  if ((ablate & 8) && !residual && relu)          // the same pass once more (same results)
+    bn_launch_act_fwd<T, VE>(x, residual, mean, invstd, weight, bias, n, c, relu, out, mask, stream);
+  TS_CHECK_LAUNCH(what);
   return TS_OK;
+}
+
+template <typename T, int VE>
+static int bn_train_backward(const char *what, const void *grad_out, const uint8_t *mask, const void *x, const float *mean,
+                             const float *invstd, const float *weight, int64_t n, int32_t c, void *grad_x, void *grad_residual,
+                             float *grad_weight, float *grad_bias, void *ws, size_t ws_bytes, hipStream_t stream) {
+  const int rc = bn_check_size<VE>(what, n, c);
+  if (rc != TS_OK) return rc;
+  TS_REQUIRE(grad_out && x && mean && invstd && weight && grad_x && ws, TS_ERR_INVALID_ARGUMENT, "%s: null pointer", what);
+  TS_REQUIRE(ws_bytes >= ts_bn_train_workspace_bytes(c), TS_ERR_INVALID_ARGUMENT, "%s: workspace too small", what);
+  TS_REQUIRE(bn_aligned(grad_out) && bn_aligned(x) && bn_aligned(grad_x) && bn_ch_aligned<VE>(mean) && bn_ch_aligned<VE>(invstd) &&
+                 bn_ch_aligned<VE>(weight) && (!grad_residual || bn_aligned(grad_residual)) && bn_aligned(ws),
+             TS_ERR_INVALID_ARGUMENT, "%s: pointers must be 16-byte aligned", what);
+  float *part = (float *)ws;
+  float *coef = part + (size_t)BN_MAX_SLICES * 2 * c;
+  const int slices = bn_launch_partial<T, VE>(x, grad_out, mask, mean, n, c, part, stream);
+  bn_bwd_finish_kernel<<<(unsigned)ts_cdiv(c, BN_FIN_CH), 256, 0, stream>>>(part, slices, (double)n, c, invstd, coef, grad_weight,
+                                                                           grad_bias);
+  bn_launch_act_bwd_coef<T, VE>(grad_out, mask, x, mean, invstd, weight, coef, n, c, grad_x, grad_residual, stream);
+  TS_CHECK_LAUNCH(what);
+  return TS_OK;
+}
+
+template <typename T, int VE>
+static int bn_sync_stats(const char *what, const void *x, int64_t n, int32_t c, double *pack, void *ws, size_t ws_bytes,
+                         hipStream_t stream) {
+  const int rc = bn_check_size<VE>(what, n, c);
+  if (rc != TS_OK) return rc;
+  TS_REQUIRE(x && pack && ws && bn_aligned(x) && bn_aligned(ws), TS_ERR_INVALID_ARGUMENT, "%s: bad pointer", what);
+  TS_REQUIRE(ws_bytes >= ts_bn_train_workspace_bytes(c), TS_ERR_INVALID_ARGUMENT, "%s: workspace too small", what);
+  float *part = (float *)ws;
+  const int slices = bn_launch_partial<T, VE>(x, nullptr, nullptr, nullptr, n, c, part, stream);
+  bn_sums_finish_kernel<<<(unsigned)ts_cdiv(c, BN_FIN_CH), 256, 0, stream>>>(part, slices, c, (double)n, nullptr, pack, nullptr,
+                                                                            nullptr);
+  TS_CHECK_LAUNCH(what);
+  return TS_OK;
+}
+
+template <typename T, int VE>
+static int bn_sync_backward_reduce(const char *what, const void *grad_out, const uint8_t *mask, const void *x, const float *mean,
+                                   const float *invstd, int64_t n, int32_t c, double *sums, float *grad_weight, float *grad_bias,
+                                   void *ws, size_t ws_bytes, hipStream_t stream) {
+  const int rc = bn_check_size<VE>(what, n, c);
+  if (rc != TS_OK) return rc;
+  TS_REQUIRE(grad_out && x && mean && invstd && sums && ws, TS_ERR_INVALID_ARGUMENT, "%s: null pointer", what);
+  TS_REQUIRE(bn_aligned(grad_out) && bn_aligned(x) && bn_ch_aligned<VE>(mean) && bn_aligned(ws), TS_ERR_INVALID_ARGUMENT,
+             "%s: pointers must be 16-byte aligned", what);
+  TS_REQUIRE(ws_bytes >= ts_bn_train_workspace_bytes(c), TS_ERR_INVALID_ARGUMENT, "%s: workspace too small", what);
+  float *part = (float *)ws;
+  const int slices = bn_launch_partial<T, VE>(x, grad_out, mask, mean, n, c, part, stream);
+  bn_sums_finish_kernel<<<(unsigned)ts_cdiv(c, BN_FIN_CH), 256, 0, stream>>>(part, slices, c, -1.0, invstd, sums, grad_weight,
+                                                                            grad_bias);
+  TS_CHECK_LAUNCH(what);
+  return TS_OK;
+}
+
+// The size check is the caller's: ts_bn_act_forward takes an empty matrix and any C % 4, ts_bn_act_forward_f16 the training bounds.
+template <typename T, int VE>
+static int bn_apply_forward(const char *what, const void *x, const void *residual, const float *mean, const float *invstd,
+                            const float *weight, const float *bias, int64_t n, int32_t c, int32_t relu, void *out, uint8_t *mask,
+                            hipStream_t stream) {
+  TS_REQUIRE(x && mean && invstd && weight && bias && out, TS_ERR_INVALID_ARGUMENT, "%s: null pointer", what);
+  TS_REQUIRE(bn_aligned(x) && bn_aligned(out) && bn_ch_aligned<VE>(mean) && bn_ch_aligned<VE>(invstd) && bn_ch_aligned<VE>(weight) &&
+                 bn_ch_aligned<VE>(bias) && (!residual || bn_aligned(residual)),
+             TS_ERR_INVALID_ARGUMENT, "%s: pointers must be 16-byte aligned", what);
+  bn_launch_act_fwd<T, VE>(x, residual, mean, invstd, weight, bias, n, c, relu, out, mask, stream);
+  TS_CHECK_LAUNCH(what);
+  return TS_OK;
+}
+
+// Elementwise backward from all-reduced double sums, through two float coefficients per channel in ws (>= 2 C floats).  Only the half
+// entry point takes this form: fp32 ts_bn_act_backward has no workspace argument and divides the doubles per element.
+template <typename T, int VE>
+static int bn_apply_backward_coef(const char *what, const void *grad_out, const uint8_t *mask, const void *x, const float *mean,
+                                  const float *invstd, const float *weight, const double *sums, const double *total_dev,
+                                  double total_host, int64_t n, int32_t c, void *grad_x, void *grad_residual, void *ws,
+                                  size_t ws_bytes, hipStream_t stream) {
+  const int rc = bn_check_size<VE>(what, n, c);
+  if (rc != TS_OK) return rc;
+  TS_REQUIRE(grad_out && x && mean && invstd && weight && sums && grad_x && ws, TS_ERR_INVALID_ARGUMENT, "%s: null pointer", what);
+  TS_REQUIRE(total_dev || total_host > 0.0, TS_ERR_INVALID_ARGUMENT, "%s: empty batch", what);
+  TS_REQUIRE(ws_bytes >= 2 * (size_t)c * sizeof(float), TS_ERR_INVALID_ARGUMENT, "%s: workspace too small", what);
+  TS_REQUIRE(bn_aligned(grad_out) && bn_aligned(x) && bn_aligned(grad_x) && bn_ch_aligned<VE>(mean) && bn_ch_aligned<VE>(invstd) &&
+                 bn_ch_aligned<VE>(weight) && (!grad_residual || bn_aligned(grad_residual)) && bn_aligned(ws),
+             TS_ERR_INVALID_ARGUMENT, "%s: pointers must be 16-byte aligned", what);
+  float *coef = (float *)ws;
+  bn_coef_from_sums_kernel<<<(unsigned)ts_cdiv(c, 256), 256, 0, stream>>>(sums, total_dev, total_host, invstd, c, coef);
+  bn_launch_act_bwd_coef<T, VE>(grad_out, mask, x, mean, invstd, weight, coef, n, c, grad_x, grad_residual, stream);
+  TS_CHECK_LAUNCH(what);
+  return TS_OK;
+}
+
+// ---- the entry points (include/taseg_hip.h): fp32 rows, then half rows
+extern "C" int ts_bn_act_forward(const float *x, const float *residual, const float *mean, const float *invstd,
+                                 const float *weight, const float *bias, int64_t n, int32_t c, int32_t relu, float *out,
+                                 uint8_t *mask, ts_stream_t stream) {
+  TS_REQUIRE(n >= 0 && c > 0 && (c & 3) == 0, TS_ERR_UNSUPPORTED, "ts_bn_act_forward: C must be a multiple of 4");
+  if (n == 0) return TS_OK;
+  return bn_apply_forward<float, 4>("ts_bn_act_forward", x, residual, mean, invstd, weight, bias, n, c, relu, out, mask,
+                                    (hipStream_t)stream);
+}
+
+extern "C" int ts_bn_act_backward(const float *grad_out, const uint8_t *mask, const float *x, const float *mean,
+                                  const float *invstd, const float *weight, const double *sums, const double *total_dev,
+                                  double total_host, int64_t n, int32_t c, float *grad_x, float *grad_residual,
+                                  ts_stream_t stream) {
+  TS_REQUIRE(n >= 0 && c > 0 && (c & 3) == 0, TS_ERR_UNSUPPORTED, "ts_bn_act_backward: C must be a multiple of 4");
+  if (n == 0) return TS_OK;
+  TS_REQUIRE(grad_out && x && mean && invstd && weight && sums && grad_x, TS_ERR_INVALID_ARGUMENT,
+             "ts_bn_act_backward: null pointer");
+  TS_REQUIRE(total_dev || total_host > 0.0, TS_ERR_INVALID_ARGUMENT, "ts_bn_act_backward: empty batch");
+  TS_REQUIRE(bn_aligned(grad_out) && bn_aligned(x) && bn_aligned(grad_x) &&
+                 (!grad_residual || bn_aligned(grad_residual)) && bn_aligned(mean) && bn_aligned(invstd) &&
+                 bn_aligned(weight),
+             TS_ERR_INVALID_ARGUMENT, "ts_bn_act_backward: pointers must be 16-byte aligned");
+  const int64_t total4 = n * (c / 4);
+  bn_act_bwd_kernel<<<bn_grid(total4), 256, 0, (hipStream_t)stream>>>((const float4 *)grad_out, mask, (const float4 *)x, mean,
+                                                                      invstd, weight, sums, total_dev, total_host, total4, c,
+                                                                      (float4 *)grad_x, (float4 *)grad_residual);
+  TS_CHECK_LAUNCH("ts_bn_act_backward");
+  return TS_OK;
+}
+
+extern "C" int ts_bn_act_train_forward(const float *x, const float *residual, const float *weight, const float *bias,
+                                       float *running_mean, float *running_var, int64_t *num_batches_tracked,
+                                       int64_t n, int32_t c, float eps, float momentum, int32_t relu, float *mean,
+                                       float *invstd, float *out, uint8_t *mask, void *ws, size_t ws_bytes,
+                                       ts_stream_t stream) {
+  return bn_train_forward<float, 4>("ts_bn_act_train_forward", x, residual, weight, bias, running_mean, running_var,
+                                    num_batches_tracked, n, c, eps, momentum, relu, mean, invstd, out, mask, ws, ws_bytes,
+                                    (hipStream_t)stream);
+}
+
+extern "C" int ts_bn_act_train_backward(const float *grad_out, const uint8_t *mask, const float *x, const float *mean,
+                                        const float *invstd, const float *weight, int64_t n, int32_t c, float *grad_x,
+                                        float *grad_residual, float *grad_weight, float *grad_bias, void *ws,
+                                        size_t ws_bytes, ts_stream_t stream) {
+  return bn_train_backward<float, 4>("ts_bn_act_train_backward", grad_out, mask, x, mean, invstd, weight, n, c, grad_x,
+                                     grad_residual, grad_weight, grad_bias, ws, ws_bytes, (hipStream_t)stream);
+}
+
+extern "C" int ts_bn_sync_stats(const float *x, int64_t n, int32_t c, double *pack, void *ws, size_t ws_bytes,
+                                ts_stream_t stream) {
+  return bn_sync_stats<float, 4>("ts_bn_sync_stats", x, n, c, pack, ws, ws_bytes, (hipStream_t)stream);
+}
+
+extern "C" int ts_bn_sync_backward_reduce(const float *grad_out, const uint8_t *mask, const float *x, const float *mean,
+                                          const float *invstd, int64_t n, int32_t c, double *sums, float *grad_weight,
+                                          float *grad_bias, void *ws, size_t ws_bytes, ts_stream_t stream) {
+  return bn_sync_backward_reduce<float, 4>("ts_bn_sync_backward_reduce", grad_out, mask, x, mean, invstd, n, c, sums,
+                                           grad_weight, grad_bias, ws, ws_bytes, (hipStream_t)stream);
+}
+
+extern "C" int ts_bn_act_train_forward_f16(const void *x, const void *residual, const float *weight, const float *bias,
+                                           float *running_mean, float *running_var, int64_t *num_batches_tracked,
+                                           int64_t n, int32_t c, float eps, float momentum, int32_t relu, float *mean,
+                                           float *invstd, void *out, uint8_t *mask, void *ws, size_t ws_bytes,
+                                           ts_stream_t stream) {
+  return bn_train_forward<_Float16, 8>("ts_bn_act_train_forward_f16", x, residual, weight, bias, running_mean, running_var,
+                                       num_batches_tracked, n, c, eps, momentum, relu, mean, invstd, out, mask, ws, ws_bytes,
+                                       (hipStream_t)stream);
+}
+
+extern "C" int ts_bn_act_train_backward_f16(const void *grad_out, const uint8_t *mask, const void *x, const float *mean,
+                                            const float *invstd, const float *weight, int64_t n, int32_t c,
+                                            void *grad_x, void *grad_residual, float *grad_weight, float *grad_bias,
+                                            void *ws, size_t ws_bytes, ts_stream_t stream) {
+  return bn_train_backward<_Float16, 8>("ts_bn_act_train_backward_f16", grad_out, mask, x, mean, invstd, weight, n, c, grad_x,
+                                        grad_residual, grad_weight, grad_bias, ws, ws_bytes, (hipStream_t)stream);
+}
+
+// SyncBatchNorm halves for half-storage activations (the reference's actual recipe is AMP + DDP + SyncBatchNorm,
+// R/dist_train.sh:17-19): the same double sums cross the ranks, activations and gradients stay half in HBM.
+extern "C" int ts_bn_sync_stats_f16(const void *x, int64_t n, int32_t c, double *pack, void *ws, size_t ws_bytes,
+                                    ts_stream_t stream) {
+  return bn_sync_stats<_Float16, 8>("ts_bn_sync_stats_f16", x, n, c, pack, ws, ws_bytes, (hipStream_t)stream);
 }
 
 extern "C" int ts_bn_act_forward_f16(const void *x, const void *residual, const float *mean, const float *invstd,
                                      const float *weight, const float *bias, int64_t n, int32_t c, int32_t relu,
-                                     void *out, uint8_t *mask, ts_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  int rc = bn_h_check("ts_bn_act_forward_f16", n, c);
+                                     void *out, uint8_t *mask, ts_stream_t stream) {
+  const int rc = bn_check_size<8>("ts_bn_act_forward_f16", n, c);
   if (rc != TS_OK) return rc;
-  TS_REQUIRE(x && mean && invstd && weight && bias && out, TS_ERR_INVALID_ARGUMENT, "ts_bn_act_forward_f16: null pointer");
-  TS_REQUIRE(bn_aligned(x) && bn_aligned(out) && (!residual || bn_aligned(residual)), TS_ERR_INVALID_ARGUMENT,
-             "ts_bn_act_forward_f16: pointers must be 16-byte aligned");
-  const int64_t total8 = n * (c / 8);
-  const unsigned grid = (unsigned)std::min<int64_t>(ts_cdiv(total8, 256), 1 << 16);
-  bn_act_fwd_h_kernel<<<grid, 256, 0, stream>>>((const bn_h8 *)x, (const bn_h8 *)residual, mean, invstd, weight, bias,
-                                                total8, c / 8, relu, (bn_h8 *)out, mask);
-  TS_CHECK_LAUNCH("ts_bn_act_forward_f16");
-  return TS_OK;
+  return bn_apply_forward<_Float16, 8>("ts_bn_act_forward_f16", x, residual, mean, invstd, weight, bias, n, c, relu, out, mask,
+                                       (hipStream_t)stream);
 }
 
 extern "C" int ts_bn_sync_backward_reduce_f16(const void *grad_out, const uint8_t *mask, const void *x, const float *mean,
                                               const float *invstd, int64_t n, int32_t c, double *sums,
                                               float *grad_weight, float *grad_bias, void *ws, size_t ws_bytes,
-                                              ts_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  int rc = bn_h_check("ts_bn_sync_backward_reduce_f16", n, c);
-  if (rc != TS_OK) return rc;
-  TS_REQUIRE(grad_out && x && mean && invstd && sums && ws, TS_ERR_INVALID_ARGUMENT,
-             "ts_bn_sync_backward_reduce_f16: null pointer");
-  TS_REQUIRE(bn_aligned(grad_out) && bn_aligned(x) && bn_aligned(ws), TS_ERR_INVALID_ARGUMENT,
-             "ts_bn_sync_backward_reduce_f16: pointers must be 16-byte aligned");
-  TS_REQUIRE(ws_bytes >= ts_bn_train_workspace_bytes(c), TS_ERR_INVALID_ARGUMENT,
-             "ts_bn_sync_backward_reduce_f16: workspace too small");
-  float *part = (float *)ws;
-  const int rows = bn_rows_per_slice_h(n, c);
-  const int slices = (int)ts_cdiv(n, rows);
-  if (mask)
-    bn_partial_h_kernel<2><<<slices, 256, 0, stream>>>((const _Float16 *)x, (const _Float16 *)grad_out, mask, mean, n, c,
-                                                       rows, part);
-  else
-    bn_partial_h_kernel<1><<<slices, 256, 0, stream>>>((const _Float16 *)x, (const _Float16 *)grad_out, nullptr, mean, n,
-                                                       c, rows, part);
-  bn_sums_finish_kernel<<<(unsigned)ts_cdiv(c, BN_FIN_CH), 256, 0, stream>>>(part, slices, c, -1.0, invstd, sums,
-                                                                           grad_weight, grad_bias);
-  TS_CHECK_LAUNCH("ts_bn_sync_backward_reduce_f16");
-  return TS_OK;
+                                              ts_stream_t stream) {
+  return bn_sync_backward_reduce<_Float16, 8>("ts_bn_sync_backward_reduce_f16", grad_out, mask, x, mean, invstd, n, c, sums,
+                                              grad_weight, grad_bias, ws, ws_bytes, (hipStream_t)stream);
 }
 
 extern "C" int ts_bn_act_backward_f16(const void *grad_out, const uint8_t *mask, const void *x, const float *mean,
                                       const float *invstd, const float *weight, const double *sums,
                                       const double *total_dev, double total_host, int64_t n, int32_t c, void *grad_x,
-                                      void *grad_residual, void *ws, size_t ws_bytes, ts_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  int rc = bn_h_check("ts_bn_act_backward_f16", n, c);
-  if (rc != TS_OK) return rc;
-  TS_REQUIRE(grad_out && x && mean && invstd && weight && sums && grad_x && ws, TS_ERR_INVALID_ARGUMENT,
-             "ts_bn_act_backward_f16: null pointer");
-  TS_REQUIRE(total_dev || total_host > 0.0, TS_ERR_INVALID_ARGUMENT, "ts_bn_act_backward_f16: empty batch");
-  TS_REQUIRE(ws_bytes >= 2 * (size_t)c * sizeof(float), TS_ERR_INVALID_ARGUMENT, "ts_bn_act_backward_f16: workspace too small");
-  TS_REQUIRE(bn_aligned(grad_out) && bn_aligned(x) && bn_aligned(grad_x) && (!grad_residual || bn_aligned(grad_residual)) &&
-                 bn_aligned(ws), TS_ERR_INVALID_ARGUMENT, "ts_bn_act_backward_f16: pointers must be 16-byte aligned");
-  float *coef = (float *)ws;
-  bn_coef_from_sums_kernel<<<(unsigned)ts_cdiv(c, 256), 256, 0, stream>>>(sums, total_dev, total_host, invstd, c, coef);
-  const int64_t total8 = n * (c / 8);
-  const unsigned grid = (unsigned)std::min<int64_t>(ts_cdiv(total8, 256), 1 << 16);
-  bn_act_bwd_coef_h_kernel<<<grid, 256, 0, stream>>>((const bn_h8 *)grad_out, mask, (const bn_h8 *)x, mean, invstd, weight,
-                                                     coef, total8, c, (bn_h8 *)grad_x, (bn_h8 *)grad_residual);
-  TS_CHECK_LAUNCH("ts_bn_act_backward_f16");
-  return TS_OK;
+                                      void *grad_residual, void *ws, size_t ws_bytes, ts_stream_t stream) {
+  return bn_apply_backward_coef<_Float16, 8>("ts_bn_act_backward_f16", grad_out, mask, x, mean, invstd, weight, sums, total_dev,
+                                             total_host, n, c, grad_x, grad_residual, ws, ws_bytes, (hipStream_t)stream);
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -796,25 +687,21 @@ extern "C" int ts_bn_act_backward_f16(const void *grad_out, const uint8_t *mask,
 // Three launches per direction (partial sums -> finish -> elementwise), 2 reads + 1 write of N*C*s forward, 3 reads + 1 write
 // backward, where the library path of this PyTorch-ROCm takes a LeakyReLU pass, a layout copy and three MIOpen BatchNorm kernels
 // forward, and as many backward.  T = float (4 channels per thread) or _Float16 (8 per thread); statistics fp32 / double.
-template <typename T, int VE>
-struct alignas(VE * sizeof(T)) LbnVec {
-  T x[VE];
-};
-
 __device__ __forceinline__ float lbn_leaky(float v, float slope) { return v > 0.f ? v : v * slope; }
 
 // MODE 0: (a, a^2)   1: (dy, dy (a - mean))
 template <typename T, int VE, int MODE>
 __global__ __launch_bounds__(256) void lbn_partial_kernel(const T *__restrict__ X, const T *__restrict__ DY, const float *__restrict__ mean,
                                                           float slope, int64_t n, int c, int rows_per_wg, float *__restrict__ part) {
-  using V = LbnVec<T, VE>;
+  using V = BnVec<T, VE>;
   __shared__ float red[2][256 * VE];
   const int cq = c / VE, rpp = 256 / cq;
   const int tid = threadIdx.x, ty = tid / cq, tx = tid - ty * cq;
   const bool active = ty < rpp;
-  float s0[VE], s1[VE], mu[VE];
+  BnVec<float, VE> s0 = {}, s1 = {};
+  float mu[VE];
 #pragma unroll
-  for (int i = 0; i < VE; ++i) s0[i] = s1[i] = mu[i] = 0.f;
+  for (int i = 0; i < VE; ++i) mu[i] = 0.f;
   if (MODE != 0 && active) {
 #pragma unroll
     for (int i = 0; i < VE; ++i) mu[i] = mean[VE * tx + i];
@@ -826,15 +713,15 @@ __global__ __launch_bounds__(256) void lbn_partial_kernel(const T *__restrict__ 
 #pragma unroll
         for (int i = 0; i < VE; ++i) {
           const float a = lbn_leaky((float)x.x[i], slope);
-          s0[i] += a;
-          s1[i] += a * a;
+          s0.x[i] += a;
+          s1.x[i] += a * a;
         }
       } else {
 #pragma unroll
         for (int i = 0; i < VE; ++i) {
           const float dv = (float)d.x[i];
-          s0[i] += dv;
-          s1[i] += dv * (lbn_leaky((float)x.x[i], slope) - mu[i]);
+          s0.x[i] += dv;
+          s1.x[i] += dv * (lbn_leaky((float)x.x[i], slope) - mu[i]);
         }
       }
     };
@@ -860,41 +747,25 @@ __global__ __launch_bounds__(256) void lbn_partial_kernel(const T *__restrict__ 
       add(x, d);
     }
   }
-#pragma unroll
-  for (int i = 0; i < VE; ++i) {
-    red[0][tid * VE + i] = s0[i];
-    red[1][tid * VE + i] = s1[i];
-  }
-  __syncthreads();
-  float *out = part + (int64_t)blockIdx.x * 2 * c;
-  for (int ch = tid; ch < c; ch += 256) {
-    const int q = ch / VE, l = ch % VE;
-    float a = 0.f, b = 0.f;
-    for (int y = 0; y < rpp; ++y) {
-      a += red[0][(y * cq + q) * VE + l];
-      b += red[1][(y * cq + q) * VE + l];
-    }
-    out[ch] = a;
-    out[c + ch] = b;
-  }
+  bn_fold_slice<VE>(s0, s1, red, c, cq, rpp, part);
 }
 
 template <typename T, int VE>
-__global__ __launch_bounds__(256) void lbn_fwd_kernel(const LbnVec<T, VE> *__restrict__ X, const float *__restrict__ mean,
+__global__ __launch_bounds__(256) void lbn_fwd_kernel(const BnVec<T, VE> *__restrict__ X, const float *__restrict__ mean,
                                                       const float *__restrict__ invstd, const float *__restrict__ w,
                                                       const float *__restrict__ b, float slope, int64_t total, int cq,
-                                                      const LbnVec<T, VE> *__restrict__ RES, LbnVec<T, VE> *__restrict__ OUT) {
+                                                      const BnVec<T, VE> *__restrict__ RES, BnVec<T, VE> *__restrict__ OUT) {
   int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t step = (int64_t)gridDim.x * blockDim.x;
   for (; e < total; e += step) {
     const int q = (int)(e % cq) * VE;
-    const LbnVec<T, VE> x = X[e];
-    LbnVec<T, VE> y;
+    const BnVec<T, VE> x = X[e];
+    BnVec<T, VE> y;
 #pragma unroll
     for (int i = 0; i < VE; ++i)
       y.x[i] = (T)((lbn_leaky((float)x.x[i], slope) - mean[q + i]) * invstd[q + i] * w[q + i] + b[q + i]);
     if (RES) {                                             // the block's residual sum: added to the ROUNDED result, as the module pair does
-      const LbnVec<T, VE> r = RES[e];
+      const BnVec<T, VE> r = RES[e];
 #pragma unroll
       for (int i = 0; i < VE; ++i) y.x[i] = (T)((float)y.x[i] + (float)r.x[i]);
     }
@@ -903,17 +774,17 @@ __global__ __launch_bounds__(256) void lbn_fwd_kernel(const LbnVec<T, VE> *__res
 }
 
 template <typename T, int VE>
-__global__ __launch_bounds__(256) void lbn_bwd_kernel(const LbnVec<T, VE> *__restrict__ GOUT, const LbnVec<T, VE> *__restrict__ X,
+__global__ __launch_bounds__(256) void lbn_bwd_kernel(const BnVec<T, VE> *__restrict__ GOUT, const BnVec<T, VE> *__restrict__ X,
                                                       const float *__restrict__ mean, const float *__restrict__ invstd,
                                                       const float *__restrict__ w, const float *__restrict__ coef, float slope,
-                                                      int64_t total, int c, LbnVec<T, VE> *__restrict__ GX) {
+                                                      int64_t total, int c, BnVec<T, VE> *__restrict__ GX) {
   const int cq = c / VE;
   int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t step = (int64_t)gridDim.x * blockDim.x;
   for (; e < total; e += step) {
     const int q = (int)(e % cq) * VE;
-    const LbnVec<T, VE> g = GOUT[e], x = X[e];
-    LbnVec<T, VE> gx;
+    const BnVec<T, VE> g = GOUT[e], x = X[e];
+    BnVec<T, VE> gx;
 #pragma unroll
     for (int i = 0; i < VE; ++i) {
       const float xv = (float)x.x[i];
@@ -933,25 +804,17 @@ static int lbn_check(const char *what, int64_t n, int32_t c, int32_t half, size_
 }
 
 template <typename T, int VE>
-static inline int lbn_rows_per_slice(int64_t n, int c) {
-  const int rpp = 256 / (c / VE);
-  int64_t rows = std::max<int64_t>(ts_cdiv(n, BN_MAX_SLICES), 32);
-  return (int)(ts_cdiv(rows, rpp) * rpp);
-}
-
-template <typename T, int VE>
 static void lbn_forward_launch(const void *x, const float *weight, const float *bias, float *running_mean, float *running_var,
                                int64_t *nbt, int64_t n, int c, float eps, float momentum, float slope, float *mean, float *invstd,
                                const void *residual, void *out, float *part, hipStream_t stream) {
-  const int rows = lbn_rows_per_slice<T, VE>(n, c);
+  const int rows = bn_rows_per_slice<VE>(n, c);
   const int slices = (int)ts_cdiv(n, rows);
   lbn_partial_kernel<T, VE, 0><<<slices, 256, 0, stream>>>((const T *)x, nullptr, nullptr, slope, n, c, rows, part);
   bn_fwd_finish_kernel<<<(unsigned)ts_cdiv(c, BN_FIN_CH), 256, 0, stream>>>(part, slices, (double)n, c, eps, momentum, running_mean,
                                                                            running_var, mean, invstd, nbt);
   const int64_t total = n * (c / VE);
-  const unsigned grid = (unsigned)std::min<int64_t>(ts_cdiv(total, 256), 1 << 16);
-  lbn_fwd_kernel<T, VE><<<grid, 256, 0, stream>>>((const LbnVec<T, VE> *)x, mean, invstd, weight, bias, slope, total, c / VE,
-                                                  (const LbnVec<T, VE> *)residual, (LbnVec<T, VE> *)out);
+  lbn_fwd_kernel<T, VE><<<bn_grid(total), 256, 0, stream>>>((const BnVec<T, VE> *)x, mean, invstd, weight, bias, slope, total, c / VE,
+                                                  (const BnVec<T, VE> *)residual, (BnVec<T, VE> *)out);
 }
 
 template <typename T, int VE>
@@ -959,15 +822,14 @@ static void lbn_backward_launch(const void *grad_out, const void *x, const float
                                 int64_t n, int c, float slope, void *grad_x, float *grad_weight, float *grad_bias, float *part,
                                 hipStream_t stream) {
   float *coef = part + (size_t)BN_MAX_SLICES * 2 * c;
-  const int rows = lbn_rows_per_slice<T, VE>(n, c);
+  const int rows = bn_rows_per_slice<VE>(n, c);
   const int slices = (int)ts_cdiv(n, rows);
   lbn_partial_kernel<T, VE, 1><<<slices, 256, 0, stream>>>((const T *)x, (const T *)grad_out, mean, slope, n, c, rows, part);
   bn_bwd_finish_kernel<<<(unsigned)ts_cdiv(c, BN_FIN_CH), 256, 0, stream>>>(part, slices, (double)n, c, invstd, coef, grad_weight,
                                                                            grad_bias);
   const int64_t total = n * (c / VE);
-  const unsigned grid = (unsigned)std::min<int64_t>(ts_cdiv(total, 256), 1 << 16);
-  lbn_bwd_kernel<T, VE><<<grid, 256, 0, stream>>>((const LbnVec<T, VE> *)grad_out, (const LbnVec<T, VE> *)x, mean, invstd, weight,
-                                                  coef, slope, total, c, (LbnVec<T, VE> *)grad_x);
+  lbn_bwd_kernel<T, VE><<<bn_grid(total), 256, 0, stream>>>((const BnVec<T, VE> *)grad_out, (const BnVec<T, VE> *)x, mean, invstd, weight,
+                                                  coef, slope, total, c, (BnVec<T, VE> *)grad_x);
 }
 
 // out [N, C] = BatchNorm_train(LeakyReLU_slope(x [N, C])) (+ residual [N, C], may be NULL: the block's `skip + y`, added to the rounded
