@@ -558,6 +558,35 @@ int ts_sgd_decide(double *sumsq, int32_t *nonfinite, float *state, float max_nor
 int ts_sgd_apply(float *param, const float *grad, float *momentum_buf, int64_t n, const float *state, float lr,
                  float momentum, float weight_decay, int32_t first_step, ts_stream_t stream);
 
+/* ts_sgd_apply per parameter slot of a bucket, one launch (what FlatSGD.step() issues).  Device tables:
+ *   slots[n_slots]      one record per parameter of the bucket, ascending offsets; every slot starts on a 16-element
+ *                       boundary and the padding up to the next slot holds zeros in all three buckets
+ *   tile_first[n_tiles] n_tiles = ceil(n / TS_SGD_TILE): index of the slot that holds element t * TS_SGD_TILE
+ *   flags               NULL with one process: a slot with `unused` set is left untouched, bit for bit.  Else the
+ *                       reducer's all-reduced "some rank had a gradient" array: such a slot is skipped only when
+ *                       flags[flag_index] == 0
+ *   groups[n_groups]    hyper-parameters per group, or NULL (n_groups 1): then every slot takes lr / momentum /
+ *                       weight_decay / nesterov from the arguments
+ * Per element ts_sgd_apply's arithmetic (the same bits for one group without Nesterov); with nesterov
+ * p -= lr * (d + momentum * m_new).  n % 4 == 0, the three buckets 16-byte aligned. */
+#define TS_SGD_TILE 4096
+typedef struct TsSgdSlot {
+  int64_t offset;      /* first element of the slot in the bucket */
+  int64_t count;       /* elements of the parameter (the slot is padded to the next multiple of 16) */
+  int32_t group;       /* index into groups */
+  int32_t unused;      /* != 0: this rank has no gradient for the parameter this step */
+  int32_t flag_index;  /* index into flags */
+  int32_t reserved;
+} TsSgdSlot;
+typedef struct TsSgdGroup {
+  float lr, momentum, weight_decay;
+  int32_t nesterov;
+} TsSgdGroup;
+int ts_sgd_apply_segments(float *param, const float *grad, float *momentum_buf, int64_t n, const float *state,
+                          const TsSgdSlot *slots, int32_t n_slots, const int32_t *tile_first, int64_t n_tiles,
+                          const float *flags, const TsSgdGroup *groups, int32_t n_groups, float lr, float momentum,
+                          float weight_decay, int32_t nesterov, int32_t first_step, ts_stream_t stream);
+
 /* Half-storage forms of the SyncBatchNorm halves (ts_bn_sync_stats, ts_bn_act_forward, ts_bn_sync_backward_reduce,
  * ts_bn_act_backward): activations / gradients IEEE half [n, c] (c % 8 == 0), mask one byte per 8 elements, everything
  * else as in the fp32 forms.  ts_bn_act_backward_f16 needs 2 c floats of 16-byte aligned scratch. */

@@ -116,6 +116,8 @@ SIGNATURES = {
     "ts_sgd_grad_stats": (_i32, [_vp, _i64, _vp, _vp, _vp]),
     "ts_sgd_decide": (_i32, [_vp, _vp, _vp, _c.c_float, _c.c_float, _c.c_float, _i32, _i32, _vp]),
     "ts_sgd_apply": (_i32, [_vp, _vp, _vp, _i64, _vp, _c.c_float, _c.c_float, _c.c_float, _i32, _vp]),
+    "ts_sgd_apply_segments": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _i32, _vp, _i64, _vp, _vp, _i32, _c.c_float, _c.c_float,
+                                     _c.c_float, _i32, _i32, _vp]),
     "ts_bn_sync_stats_f16": (_i32, [_vp, _i64, _i32, _vp, _vp, _sz, _vp]),
     "ts_bn_act_forward_f16": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp]),
     "ts_bn_sync_backward_reduce_f16": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
@@ -206,6 +208,9 @@ SIGNATURES = {
     "ts_voxel_coords": (_i32, [_vp, _i64, _i32, _c.c_float, _vp, _i32, _vp, _vp, _vp, _vp]),
 }
 
+
+
+SGD_TILE = 4096       # include/taseg_hip.h TS_SGD_TILE (ts_sgd_apply_segments refuses a tile list of another length)
 
 
 class TsClassPlan(_c.Structure):

@@ -1,9 +1,9 @@
-"""Flat-bucket SGD for the training step (reference R/train.py:399-417, R/pcseg/optim/__init__.py:13-21).
+"""Flat-bucket SGD for the training step (reference R/train.py:399-417, R/pcseg/optim/__init__.py:13-34).
 
 `FlatSGD` keeps parameters, gradients and momentum in a few flat fp32 buckets and performs
 `GradScaler.unscale_ -> clip_grad_norm_ -> SGD.step -> GradScaler.update` with three kinds of HIP launches per
-step (ts_sgd_grad_stats per bucket, ts_sgd_decide once, ts_sgd_apply per bucket) and NO device->host read: the skip
-decision on non-finite gradients, the clip coefficient and the loss-scale schedule live on the device.  torch's
+step (ts_sgd_grad_stats per bucket, ts_sgd_decide once, ts_sgd_apply_segments per bucket) and NO device->host read: the
+skip decision on non-finite gradients, the clip coefficient and the loss-scale schedule live on the device.  torch's
 equivalent is ~10 multi-tensor launches over 380 tensors plus `found_inf.item()`, a queue-draining read per step.
 
 Gradients arrive through `parallel.GradBucketReducer` (one multi-tensor copy per bucket during backward, then the
@@ -13,7 +13,13 @@ all-reduce over ranks when there are several), whose buckets this optimizer shar
     with torch.autocast("cuda", dtype=torch.float16): loss = ...
     (loss * opt.loss_scale()).backward()        # device scalar, no sync
     opt.step()                                  # reducer.finish() + the three launches
+
+Hyper-parameters live in `opt.param_groups`, a list of dictionaries in torch.optim.SGD's shape (one group unless `groups=`
+is given); `opt.lr` / `opt.momentum` / `opt.weight_decay` read and write the single group.  `state_dict()` /
+`load_state_dict()` speak torch.optim.SGD's format, `scaler_state_dict()` / `load_scaler_state_dict()`
+torch.amp.GradScaler's.  `taseg_amd.pcseg.optim.FlatOptimizer` wraps all this as a torch.optim.Optimizer for schedulers.
 """
+import numpy as np
 import torch
 
 from . import _lib as L
@@ -22,21 +28,78 @@ from .parallel import GradBucketReducer, slot_view
 
 __all__ = ["FlatSGD"]
 
+# include/taseg_hip.h TsSgdSlot / TsSgdGroup
+_SLOT = np.dtype([("offset", "<i8"), ("count", "<i8"), ("group", "<i4"), ("unused", "<i4"), ("flag_index", "<i4"),
+                  ("reserved", "<i4")])
+_GROUP = np.dtype([("lr", "<f4"), ("momentum", "<f4"), ("weight_decay", "<f4"), ("nesterov", "<i4")])
+
+
+def _check_group(g):
+    """what torch.optim.SGD refuses, plus the two things the kernel does not do"""
+    if g["lr"] < 0.0:
+        raise ValueError(f"Invalid learning rate: {g['lr']}")
+    if g["momentum"] < 0.0:
+        raise ValueError(f"Invalid momentum value: {g['momentum']}")
+    if g["weight_decay"] < 0.0:
+        raise ValueError(f"Invalid weight_decay value: {g['weight_decay']}")
+    if g.get("dampening", 0) != 0:
+        raise ValueError(f"FlatSGD: 'dampening' = {g['dampening']} is not supported (the flat update has dampening 0)")
+    if g.get("maximize", False):
+        raise ValueError("FlatSGD: 'maximize' = True is not supported")
+    if g["nesterov"] and g["momentum"] <= 0:
+        raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+
+
+def _upload(dst, host_array):
+    """stream-ordered host -> device copy that does not drain the queue: a FRESH pinned block per upload (torch's host allocator
+    keeps it alive until the copy has run), so the host array may be rewritten at once"""
+    dst.copy_(torch.from_numpy(host_array.view(np.uint8)).pin_memory(), non_blocking=True)
+
 
 class FlatSGD:
     def __init__(self, model: torch.nn.Module, lr: float, momentum: float = 0.9, weight_decay: float = 0.0,
                  max_norm: float = 0.0, amp: bool = False, init_scale: float = 65536.0, growth_factor: float = 2.0,
-                 backoff_factor: float = 0.5, growth_interval: int = 2000, process_group=None, bucket_mb: float = 32.0):
-        self.lr, self.momentum, self.weight_decay, self.max_norm = lr, momentum, weight_decay, max_norm
+                 backoff_factor: float = 0.5, growth_interval: int = 2000, process_group=None, bucket_mb: float = 32.0,
+                 nesterov: bool = False, groups=None):
+        """`groups`: None (every trainable parameter of `model` in one group) or a list of dictionaries as torch.optim.SGD takes
+        them - {"params": tensors, and any of lr / momentum / weight_decay / nesterov} - that together hold every trainable
+        parameter of `model` exactly once (parameters with requires_grad False are dropped from them)."""
+        self.max_norm = max_norm
         self.amp, self.growth, self.backoff, self.interval = amp, growth_factor, backoff_factor, growth_interval
+        defaults = {"lr": lr, "momentum": momentum, "dampening": 0, "weight_decay": weight_decay, "nesterov": nesterov,
+                    "maximize": False}
+        if groups is None:
+            groups = [{"params": [p for p in model.parameters() if p.requires_grad]}]
+        self.param_groups, group_of = [], {}
+        for gi, g in enumerate(groups):
+            g = dict(g)
+            params = g.pop("params")
+            params = [params] if isinstance(params, torch.Tensor) else list(params)
+            params = [p for p in params if p.requires_grad]
+            for p in params:
+                if id(p) in group_of:
+                    raise ValueError("some parameters appear in more than one parameter group")
+                group_of[id(p)] = gi
+            group = {**defaults, **g, "params": params}
+            _check_group(group)
+            self.param_groups.append(group)
+        trainable = {id(p): n for n, p in model.named_parameters() if p.requires_grad}
+        missing = [n for i, n in trainable.items() if i not in group_of]
+        foreign = sum(1 for i in group_of if i not in trainable)
+        if missing or foreign:
+            raise ValueError("FlatSGD: the groups must hold every trainable parameter of the model exactly once (the flat buckets "
+                             f"are updated whole); in no group: {missing[:5]}{' ...' if len(missing) > 5 else ''}, "
+                             f"not of the model: {foreign}")
         self.reducer = GradBucketReducer(model, process_group=process_group, bucket_mb=bucket_mb)
         dev = self.reducer.buckets[0]["flat"].device
         L.require_device(self.reducer.buckets[0]["flat"])
         # parameters move into flat buckets too (p.data becomes a view): the update is one launch per bucket
         names = {id(p): n for n, p in model.named_parameters()}
         self._aliases = []              # (parameter, name, address of its slice): step() refuses a rebound parameter
+        self._momentum_of = {}          # id(parameter) -> its view of the momentum bucket (what state_dict() hands out)
         for b in self.reducer.buckets:
             flat = torch.zeros_like(b["flat"])
+            mflat = torch.zeros_like(flat)
             for p, off in zip(b["params"], b["offsets"]):      # same (64-byte aligned) layout and strides as the gradient bucket
                 if p.dtype != torch.float32:
                     raise TypeError("FlatSGD keeps fp32 master parameters")
@@ -44,12 +107,36 @@ class FlatSGD:
                 view.copy_(p.data)
                 p.data = view
                 self._aliases.append((p, names.get(id(p), "?"), view.data_ptr()))
-            b["pflat"], b["mflat"] = flat, torch.zeros_like(flat)
+                self._momentum_of[id(p)] = slot_view(mflat, off, p)
+            b["pflat"], b["mflat"] = flat, mflat
+            # what ts_sgd_apply_segments reads: one record per slot, and for every tile of the bucket the slot of its first element.
+            # The layout never changes; the `unused` column is sent again only when this rank's unused set differs from the last step's
+            rec = np.zeros(len(b["params"]), dtype=_SLOT)
+            rec["offset"], rec["count"] = b["offsets"], [p.numel() for p in b["params"]]
+            rec["group"], rec["flag_index"] = [group_of[id(p)] for p in b["params"]], np.arange(len(rec))
+            starts = np.arange(-(-flat.numel() // L.SGD_TILE), dtype=np.int64) * L.SGD_TILE
+            tile_first = (np.searchsorted(rec["offset"], starts, side="right") - 1).astype(np.int32)
+            b["slot_host"], b["unused_sent"] = rec, ()
+            b["slots"] = torch.from_numpy(rec.view(np.uint8)).to(dev)
+            b["tile_first"] = torch.from_numpy(tile_first).to(dev)
+        # several groups: their values in a small device array, sent again only when one changed (under a scheduler: once a step)
+        self._groups_dev = torch.zeros(max(len(self.param_groups), 1) * _GROUP.itemsize, dtype=torch.uint8, device=dev)
+        self._groups_sent = None
         self.state = torch.zeros(8, dtype=torch.float32, device=dev)
         self.state[0] = init_scale if amp else 1.0
         self._sumsq = torch.zeros(1, dtype=torch.float64, device=dev)
         self._bad = torch.zeros(1, dtype=torch.int32, device=dev)
-        self._first = True
+
+    def _single(self, key):
+        if len(self.param_groups) != 1:
+            raise AttributeError(f"FlatSGD.{key}: there are {len(self.param_groups)} parameter groups - use param_groups[i]['{key}']")
+        return self.param_groups[0]
+
+    lr = property(lambda self: self._single("lr")["lr"], lambda self, v: self._single("lr").__setitem__("lr", v))
+    momentum = property(lambda self: self._single("momentum")["momentum"],
+                        lambda self, v: self._single("momentum").__setitem__("momentum", v))
+    weight_decay = property(lambda self: self._single("weight_decay")["weight_decay"],
+                            lambda self, v: self._single("weight_decay").__setitem__("weight_decay", v))
 
     def loss_scale(self) -> torch.Tensor:
         """Device scalar to multiply the loss with before backward (1 without AMP)."""
@@ -81,29 +168,91 @@ class FlatSGD:
         L.check(lib.ts_sgd_decide(L.ptr(self._sumsq), L.ptr(self._bad), L.ptr(self.state), float(self.max_norm),
                                   float(self.growth), float(self.backoff), int(self.interval), 1 if self.amp else 0, st),
                 "ts_sgd_decide")
+        for g in self.param_groups:
+            _check_group(g)
+        values = [(float(g["lr"]), float(g["momentum"]), float(g["weight_decay"]), int(bool(g["nesterov"])))
+                  for g in self.param_groups]
+        groups_ptr = None
+        if len(values) > 1:                           # one group (the `sgd` recipe): its values travel as kernel arguments
+            if values != self._groups_sent:
+                _upload(self._groups_dev, np.array(values, dtype=_GROUP))
+                self._groups_sent = values
+            groups_ptr = L.ptr(self._groups_dev)
+        lr, momentum, weight_decay, nesterov = values[0]
         for b in self.reducer.buckets:
             # parameters that received no gradient on ANY rank this step (an unused head, a frozen branch): torch.optim.SGD
             # skips them entirely - no weight decay, no momentum update (R/pcseg/optim/__init__.py:15-21 builds that
-            # optimizer).  The flat update touches the whole bucket, so their slices are put back afterwards.  b["unused"]
-            # is this rank's list; with several ranks the reducer's all-reduced flag of the parameter says whether some
-            # OTHER rank had a gradient for it - then the averaged gradient is applied here too (DDP's rule) and the
-            # replicas stay identical.  The flag is read on the device (torch.where), not on the host.
-            keep = []
-            for i in b.get("unused", ()):
-                off, n = b["offsets"][i], b["params"][i].numel()
-                used_elsewhere = (b["flags"][i] > 0) if self.reducer.world > 1 else None
-                keep.append((off, n, b["pflat"][off:off + n].clone(), b["mflat"][off:off + n].clone(), used_elsewhere))
-            L.check(lib.ts_sgd_apply(L.ptr(b["pflat"]), L.ptr(b["flat"]), L.ptr(b["mflat"]), b["flat"].numel(),
-                                     L.ptr(self.state), float(self.lr), float(self.momentum), float(self.weight_decay),
-                                     1 if self._first else 0, st), "ts_sgd_apply")
-            for off, n, pv, mv, used_elsewhere in keep:
-                if used_elsewhere is None:
-                    b["pflat"][off:off + n].copy_(pv)
-                    b["mflat"][off:off + n].copy_(mv)
-                else:
-                    b["pflat"][off:off + n].copy_(torch.where(used_elsewhere, b["pflat"][off:off + n], pv))
-                    b["mflat"][off:off + n].copy_(torch.where(used_elsewhere, b["mflat"][off:off + n], mv))
-        # (a skipped very first step leaves the momentum buffers zero, which `first` = 0 then treats correctly:
-        #  momentum * 0 + d = d)
-        self._first = False
-        _planes.invalidate()       # ts_sgd_apply wrote the parameters through raw pointers: pre-split weights are stale
+            # optimizer) - and so does the kernel, slot by slot.  b["unused"] is this rank's list; with several ranks the
+            # reducer's all-reduced flag of the parameter says whether some OTHER rank had a gradient for it - then the averaged
+            # gradient is applied here too (DDP's rule) and the replicas stay identical.  The flag is read on the device.
+            # There is no "first step" flag: a slot that has never been stepped holds m = 0, and momentum * 0 + d = d is torch's
+            # "no buffer yet: buf = d" to the bit (a skipped slot keeps its zeros, so this holds for a parameter whose first
+            # gradient arrives late, after a skipped first step, and after load_state_dict() of a state without buffers).
+            unused = tuple(b.get("unused", ()))
+            if unused != b["unused_sent"]:
+                b["slot_host"]["unused"] = 0
+                b["slot_host"]["unused"][list(unused)] = 1
+                _upload(b["slots"], b["slot_host"])
+                b["unused_sent"] = unused
+            n = b["flat"].numel()
+            L.check(lib.ts_sgd_apply_segments(L.ptr(b["pflat"]), L.ptr(b["flat"]), L.ptr(b["mflat"]), n, L.ptr(self.state),
+                                              L.ptr(b["slots"]), len(b["params"]), L.ptr(b["tile_first"]),
+                                              b["tile_first"].numel(), L.ptr(b["flags"]) if self.reducer.world > 1 else None,
+                                              groups_ptr, len(values), lr, momentum, weight_decay, nesterov, 0, st),
+                    "ts_sgd_apply_segments")
+        _planes.invalidate()       # the kernel wrote the parameters through raw pointers: pre-split weights are stale
+
+    # ---- checkpoints: torch.optim.SGD's and torch.amp.GradScaler's own formats (R/train.py:339,359) ------------------------
+    def _ordered(self):
+        return [p for g in self.param_groups for p in g["params"]]
+
+    def state_dict(self):
+        """torch.optim.SGD.state_dict()'s format.  Parameters are numbered through the groups in order (one group: the order of
+        model.parameters() filtered by requires_grad); every parameter carries its momentum buffer, a VIEW of the momentum bucket -
+        zeros for a parameter never stepped, which torch.optim.SGD continues from exactly as from "no buffer"."""
+        index = {id(p): i for i, p in enumerate(self._ordered())}
+        return {"state": {index[id(p)]: {"momentum_buffer": self._momentum_of[id(p)]} for p in self._ordered()},
+                "param_groups": [{**{k: v for k, v in g.items() if k != "params"}, "params": [index[id(p)] for p in g["params"]]}
+                                 for g in self.param_groups]}
+
+    def load_state_dict(self, state_dict):
+        """adopts a torch.optim.SGD / FlatSGD state: the saved momentum buffers are copied into the bucket views (a parameter without
+        one gets zeros), the saved hyper-parameters replace the current ones as torch does"""
+        saved = state_dict["param_groups"]
+        if len(saved) != len(self.param_groups):
+            raise ValueError("loaded state dict has a different number of parameter groups")
+        if any(len(s["params"]) != len(g["params"]) for s, g in zip(saved, self.param_groups)):
+            raise ValueError("loaded state dict contains a parameter group that doesn't match the size of optimizer's group")
+        for s in saved:
+            if s.get("dampening", 0) != 0:
+                raise ValueError(f"FlatSGD.load_state_dict: saved 'dampening' = {s['dampening']} is not supported (must be 0)")
+            if s.get("maximize", False):
+                raise ValueError("FlatSGD.load_state_dict: saved 'maximize' = True is not supported")
+        param_of = dict(zip((i for s in saved for i in s["params"]), self._ordered()))
+        for b in self.reducer.buckets:
+            b["mflat"].zero_()
+        for i, st in state_dict["state"].items():
+            buf = st.get("momentum_buffer")
+            if buf is not None:
+                self._momentum_of[id(param_of[i])].copy_(buf)
+        for s, g in zip(saved, self.param_groups):           # in place: whoever shares the dictionaries sees the new values
+            g.update({k: v for k, v in s.items() if k != "params"})
+            _check_group(g)
+
+    def scaler_state_dict(self):
+        """torch.amp.GradScaler.state_dict()'s format ({} without AMP, as a disabled GradScaler).  The one host read of this class:
+        loss scale and growth tracker live on the device."""
+        if not self.amp:
+            return {}
+        scale, tracker = self.state[:2].tolist()
+        return {"scale": scale, "growth_factor": self.growth, "backoff_factor": self.backoff, "growth_interval": self.interval,
+                "_growth_tracker": int(tracker)}
+
+    def load_scaler_state_dict(self, state_dict):
+        """an empty dictionary (a disabled scaler's) leaves everything as constructed"""
+        if not self.amp or not state_dict:
+            return
+        self.state[0] = float(state_dict["scale"])
+        self.state[1] = float(state_dict["_growth_tracker"])
+        self.growth, self.backoff = state_dict["growth_factor"], state_dict["backoff_factor"]
+        self.interval = state_dict["growth_interval"]

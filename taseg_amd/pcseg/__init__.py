@@ -1,3 +1,3 @@
 """pcseg-compatible surface of the hot path: `pcseg.model.build_network`, the MinkUNet family
-segmentors and the loss they call (reference: /root/reference/pcseg/{model,loss})."""
-from . import loss, model  # noqa: F401
+segmentors, the loss they call and the optimizer / scheduler builders of the training loop (reference: pcseg/{model,loss,optim})."""
+from . import loss, model, optim  # noqa: F401
