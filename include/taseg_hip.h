@@ -709,6 +709,36 @@ int ts_scene_counts(const int32_t *b_vox, int64_t stride_vox, int64_t n_vox, con
                     ts_stream_t stream);
 int ts_unvoxelise(const void *logits, int32_t half, int32_t C, const int64_t *counts, int32_t n_scenes, const int32_t *b_pts,
                   int64_t stride_pts, const int64_t *inv, int64_t n_pts, void *mapped, int64_t *pred, int32_t *flags, ts_stream_t stream);
+/* Evaluation on the device (R/train.py:35-52, 465-540: fast_hist over the scans of a batch; the summed votes of one scan, their
+ * arg-max and the label payload) behind ts_scene_counts, for index arrays grouped by scene.  With cnt_v / cnt_p / cnt_l = its counts:
+ * the KEPT points of scene s are its points in array order (those with point_mask != 0 where ts_eval_rows ran), K_s of them,
+ * m_s = min(K_s, max(num_points[s], 0)); kept point j < m_s reads logits row start_v[s] + inv[p].
+ *   ts_eval_rows       (point_mask given) rows [n_pts] int32: per kept point, scene-major, inv[p] (-1 where it is negative or above
+ *                      2^31 - 1); kept [n_scenes] int64 = K_s.  Stable compaction in three launches, no atomics for order.
+ *   ts_eval_confusion  hist [C, C] int64 += 1 at (l, arg-max of the row) for kept point j < m_s of scene s with label l =
+ *                      labels[start_l[s] + j] in 0 .. C - 1 (labels of label_bytes 1 unsigned, 4 or 8 signed); the call ADDS.
+ *                      pred (optional, int32, pred_cap rows >= sum m_s are written at most): the arg-max, scene-major.  One launch.
+ *   ts_eval_votes      the scenes are the votes of ONE scan, n = m_s for all s: total[j, c] = ((x_0 + x_1) + x_2) + ... in float32 in
+ *                      vote order, x_v = (float)logits[row of (v, j), c]; label [cap] (label_bytes 4: uint32, 1: uint8) = first
+ *                      maximum of total[j]; sums (optional) [cap, C] float32 = total; top3 (optional, C >= 3) [cap, 3] float32 = the
+ *                      three largest sums, descending; *n_out = n.  cap >= n_pts / n_scenes holds every n.  One launch.
+ * Either inv (no mask) or rows + kept (ts_eval_rows), the other NULL.  scene_flags: the int ts_scene_counts wrote.  num_points
+ * [n_scenes] int64, num_points_ms (optional) likewise.  *flags is OR-ed into and never cleared: bits 0 and 1 ts_scene_counts', bit 2
+ * (4) an inverse map entry outside its scene (the row is skipped), bit 3 (8) min(cnt_l, num_points) != m_s for a scene (it
+ * contributes nothing), bit 4 (16) votes of unequal m_s (nothing is written), bit 5 (32) num_points_ms[s] != cnt_p[s].  The arg-max
+ * is the first maximum, a NaN wins (ts_unvoxelise).  No index addresses a load before it has been range-checked; n_pts = 0 is valid. */
+size_t ts_eval_rows_workspace_bytes(int64_t n_pts, int32_t n_scenes);
+int ts_eval_rows(const uint8_t *point_mask, const int32_t *b_pts, int64_t stride_pts, const int64_t *inv, int64_t n_pts,
+                 int32_t n_scenes, int32_t *rows, int64_t *kept, void *ws, size_t ws_bytes, ts_stream_t stream);
+int ts_eval_confusion(const void *logits, int32_t half, int32_t C, int64_t n_vox, const int64_t *counts, const int32_t *scene_flags,
+                      int32_t n_scenes, const int64_t *inv, const int32_t *rows, const int64_t *kept, int64_t n_pts,
+                      const void *labels, int32_t label_bytes, int64_t n_lab, const int64_t *num_points,
+                      const int64_t *num_points_ms, int64_t *hist, int32_t *pred, int64_t pred_cap, int32_t *flags,
+                      ts_stream_t stream);
+int ts_eval_votes(const void *logits, int32_t half, int32_t C, int64_t n_vox, const int64_t *counts, const int32_t *scene_flags,
+                  int32_t n_scenes, const int64_t *inv, const int32_t *rows, const int64_t *kept, int64_t n_pts,
+                  const int64_t *num_points, const int64_t *num_points_ms, void *label, int32_t label_bytes, float *sums,
+                  float *top3, int64_t cap, int64_t *n_out, int32_t *flags, ts_stream_t stream);
 /* Column concatenation / slicing of row-major feature matrices - torchsparse.cat (TS/torchsparse/operators.py:10-17: torch.cat of
  * the feature matrices along dim 1, the skip connections of the decoder, R/pcseg/model/segmentor/voxel/minkunet/minkunet.py:403-416)
  * and its gradient, for callers that chain block calls without tensors (the stage programs of csrc/fastpath/stage_program.h).

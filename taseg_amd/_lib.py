@@ -139,6 +139,12 @@ SIGNATURES = {
     "ts_set_device": (_i32, [_i32]),
     "ts_scene_counts": (_i32, [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _i32, _vp, _vp, _vp]),
     "ts_unvoxelise": (_i32, [_vp, _i32, _i32, _vp, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "ts_eval_rows_workspace_bytes": (_sz, [_i64, _i32]),
+    "ts_eval_rows": (_i32, [_vp, _vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "ts_eval_confusion": (_i32, [_vp, _i32, _i32, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _i64, _vp, _i32, _i64, _vp, _vp, _vp, _vp, _i64,
+                                 _vp, _vp]),
+    "ts_eval_votes": (_i32, [_vp, _i32, _i32, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i32, _vp, _vp, _i64, _vp, _vp,
+                             _vp]),
     "ts_cat_cols": (_i32, [_vp, _i64, _vp, _i64, _i64, _vp, _vp]),
     "ts_copy_cols": (_i32, [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _vp]),
     "ts_conv_block_forward": (_i32, [_vp, _i64, _i32, _vp, _i32, _vp, _vp, _i64, _i32, _vp, _i64, _i32, _vp, _vp, _vp, _vp,

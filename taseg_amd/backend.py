@@ -21,6 +21,7 @@ __all__ = [
     "convolution_forward_cuda", "convolution_backward_cuda",
     "downsample", "unique_i64", "build_kmap", "trilinear_map", "conv_nbr", "conv_wgrad", "conv_class_plan", "conv_class_gemm", "conv_class_gemm_f16", "conv_class_conv", "conv_class_conv_f16", "class_finish_pays",
     "fuse_scan", "fuse_scans", "fuse_sweeps", "project_fov", "voxel_coords", "sparse_quantize", "set_conv_impl", "image_gather_forward", "image_gather_backward", "image_gather_rows_forward", "image_gather_rows_backward", "avgpool3s2_rows_forward", "avgpool3s2_rows_backward", "conv3x3c32_pack", "conv3x3c32_rows", "conv3x3c32_wgrad", "conv3x3_rows_takes", "conv3x3_rows_pack", "conv3x3_rows", "conv3x3_wgrad", "conv1x1c32_pack", "conv1x1c32_rows", "conv1x1c32_wgrad", "shuffle_cat_rows_takes", "shuffle_cat_rows_forward", "shuffle_cat_rows_backward",
+    "eval_confusion", "eval_votes",
 ]
 
 
@@ -1813,3 +1814,124 @@ def conv_class_gemm_f16(feat, w16, plan, weight_transposed=False):
                                                 1 if weight_transposed else 0, plan["mirror"], L.ptr(plan["rows"]), L.ptr(zp),
                                                 L.stream()), "ts_conv_class_gemm_f16")
     return zp
+
+
+# --------------------------------------------------------------------------- evaluation on the device (csrc/evaltail.hip)
+_EVAL_LABEL_BYTES = {torch.uint8: 1, torch.int32: 4, torch.int64: 8}
+
+
+def _eval_batch(logits, vox_batch, pts_batch, inv, lab_batch, num_points, point_mask, num_points_ms, what):
+    """the part eval_confusion and eval_votes share: argument checks, ts_scene_counts, and ts_eval_rows where a mask has to be
+    compacted.  Returns the leading arguments of the reduce call and the tensors they point into."""
+    L.require_device(logits, vox_batch, pts_batch, inv, lab_batch, point_mask)
+    if logits.dim() != 2 or logits.dtype not in (torch.float32, torch.float16):
+        raise ValueError(f"{what}: logits must be a float32 or float16 [n, C] tensor (got {logits.dtype}, {tuple(logits.shape)})")
+    n_scenes = int(torch.as_tensor(num_points).numel())
+    if not 1 <= n_scenes <= 64:
+        raise ValueError(f"{what}: 1 .. 64 scenes per batch (got {n_scenes})")
+    for name, t in (("vox_batch", vox_batch), ("pts_batch", pts_batch), ("lab_batch", lab_batch)):
+        if t is not None and (t.dtype != torch.int32 or t.dim() != 1):
+            raise ValueError(f"{what}: {name} must be a 1-d int32 tensor (a column of a coordinate matrix may be strided)")
+    if inv.dtype not in (torch.int64, torch.int32) or inv.dim() != 1 or inv.shape[0] != pts_batch.shape[0]:
+        raise ValueError(f"{what}: inv must hold one int64 voxel index per point")
+    if vox_batch.shape[0] != logits.shape[0]:
+        raise ValueError(f"{what}: one scene index per logits row")
+    dev = logits.device
+    logits, inv = logits.contiguous(), inv.long().contiguous()
+    n_vox, n_pts, c = logits.shape[0], inv.shape[0], logits.shape[1]
+    n_lab = 0 if lab_batch is None else lab_batch.shape[0]
+
+    def scalars(t, name):
+        t = torch.as_tensor(t).reshape(-1)
+        if t.numel() != n_scenes or t.is_floating_point():
+            raise ValueError(f"{what}: {name} must hold one integer per scene")
+        return t.to(dev, non_blocking=True).long().contiguous()
+    np_d = scalars(num_points, "num_points")
+    ms_d = None if num_points_ms is None else scalars(num_points_ms, "num_points_ms")
+    lib, st = L.load(), L.stream()
+    meta = torch.empty(8 + 4 * n_scenes, dtype=torch.int64, device=dev)      # [scene flags | counts 3 x n | kept n]
+    stride = lambda t: int(t.stride(0)) if t.shape[0] > 1 else 1  # noqa: E731
+    counts, kept = meta.data_ptr() + 64, None
+    L.check(lib.ts_scene_counts(L.ptr(vox_batch), stride(vox_batch), n_vox, L.ptr(pts_batch), stride(pts_batch), n_pts, L.ptr(lab_batch),
+                                1 if lab_batch is None else stride(lab_batch), n_lab, n_scenes, counts, meta.data_ptr(), st),
+            "ts_scene_counts")
+    rows = None
+    if point_mask is not None:
+        if point_mask.dtype not in (torch.bool, torch.uint8) or point_mask.reshape(-1).shape[0] != n_pts:
+            raise ValueError(f"{what}: point_mask must hold one bool / uint8 per point")
+        mask = point_mask.reshape(-1).contiguous().view(torch.uint8)
+        rows = torch.empty(n_pts, dtype=torch.int32, device=dev)
+        kept = counts + 8 * 3 * n_scenes
+        ws_bytes = lib.ts_eval_rows_workspace_bytes(n_pts, n_scenes)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        L.check(lib.ts_eval_rows(L.ptr(mask), L.ptr(pts_batch), stride(pts_batch), L.ptr(inv), n_pts, n_scenes, L.ptr(rows), kept,
+                                 L.ptr(ws), ws_bytes, st), "ts_eval_rows")
+    head = (L.ptr(logits), 1 if logits.dtype == torch.float16 else 0, c, n_vox, counts, meta.data_ptr(), n_scenes,
+            None if rows is not None else L.ptr(inv), L.ptr(rows), kept, n_pts)
+    return head, (L.ptr(np_d), L.ptr(ms_d)), n_scenes, (logits, inv, rows, meta, np_d, ms_d)
+
+
+def _eval_flags(flags, what):
+    if flags.dtype != torch.int32 or flags.numel() != 1 or not flags.is_contiguous():
+        raise ValueError(f"{what}: flags must be one int32 on the device")
+
+
+def eval_confusion(logits, vox_batch, pts_batch, inv, labels, lab_batch, num_points, hist, flags, point_mask=None,
+                   num_points_ms=None, want_pred=False):
+    """csrc/evaltail.hip: the confusion-matrix additions of a batch whose scenes are scans (R/train.py:35-52, 535-540) without a
+    host read: ts_scene_counts + one launch (three more where point_mask has to be compacted).  logits [n_vox, C] float32 / half;
+    vox_batch / pts_batch / lab_batch: the int32 scene index of every logits row / point / label, grouped by scene; inv [n_pts] the
+    point's voxel inside its scene; labels [n_lab] uint8 / int32 / int64; num_points (num_points_ms) one integer per scene.
+    hist [C, C] int64 on the device is ADDED to; flags (one int32 on the device) is OR-ed into (include/taseg_hip.h) - the caller
+    clears both when it wants to and reads them when it wants to.  want_pred: returns the arg-max of the kept rows as int32 [n_pts]
+    (scene-major, the first sum of min(kept, num_points) rows are written)."""
+    L.require_device(labels, hist, flags)
+    if labels.dtype not in _EVAL_LABEL_BYTES or labels.dim() != 1:
+        raise ValueError(f"eval_confusion: labels must be a 1-d uint8, int32 or int64 tensor (got {labels.dtype})")
+    head, tail, _, keep = _eval_batch(logits, vox_batch, pts_batch, inv, lab_batch, num_points, point_mask, num_points_ms, "eval_confusion")
+    c = head[2]
+    if hist.dtype != torch.int64 or tuple(hist.shape) != (c, c) or not hist.is_contiguous():
+        raise ValueError(f"eval_confusion: hist must be a contiguous int64 [{c}, {c}] tensor")
+    _eval_flags(flags, "eval_confusion")
+    if lab_batch is None or lab_batch.shape[0] != labels.shape[0]:
+        raise ValueError("eval_confusion: one scene index per label")
+    labels = labels.contiguous()
+    n_pts = head[-1]
+    pred = torch.empty(n_pts, dtype=torch.int32, device=logits.device) if want_pred else None
+    L.check(L.load().ts_eval_confusion(*head, L.ptr(labels), _EVAL_LABEL_BYTES[labels.dtype], labels.shape[0], *tail, L.ptr(hist), L.ptr(pred),
+                                       n_pts if want_pred else 0, L.ptr(flags), L.stream()), "ts_eval_confusion")
+    return pred
+
+
+def eval_votes(logits, vox_batch, pts_batch, inv, num_points, flags, point_mask=None, num_points_ms=None, label_bytes=4,
+               want_sums=False, want_top3=False, out=None):
+    """csrc/evaltail.hip: the scenes of the batch are the votes of ONE scan (collate_batch_tta): their logits summed per point in
+    float32 in vote order (R/train.py:474-477), the arg-max as the label payload (label_bytes 4: uint32 bits in an int32 tensor,
+    1: uint8 - vote_payload's two types), optionally the sums [cap, C] and the three largest of them [cap, 3] - ts_scene_counts +
+    one launch (three more for a point_mask), no host read.  Returns {"label", "n", "sums", "top3"}: buffers of cap = n_pts //
+    votes rows of which the first n (a device scalar, int64 [1]) are written; flags as in eval_confusion.  out: the dictionary of an
+    earlier call on a batch of this size, to write into its buffers again."""
+    if label_bytes not in (1, 4):
+        raise ValueError("eval_votes: labels of 1 (uint8) or 4 (uint32) bytes")
+    L.require_device(flags)
+    head, tail, votes, keep = _eval_batch(logits, vox_batch, pts_batch, inv, None, num_points, point_mask, num_points_ms, "eval_votes")
+    _eval_flags(flags, "eval_votes")
+    c, n_pts, dev = head[2], head[-1], logits.device
+    if want_top3 and c < 3:
+        raise ValueError("eval_votes: the three largest sums need at least three classes")
+    cap = n_pts // votes
+    fresh = {"label": torch.empty(cap, dtype=torch.uint8 if label_bytes == 1 else torch.int32, device=dev),
+             "sums": torch.empty((cap, c), dtype=torch.float32, device=dev) if want_sums else None,
+             "top3": torch.empty((cap, 3), dtype=torch.float32, device=dev) if want_top3 else None,
+             "n": torch.zeros(1, dtype=torch.int64, device=dev)}
+    if out is not None:
+        for key, t in fresh.items():
+            o = out.get(key)
+            if (t is None) != (o is None) or (t is not None and (o.dtype, o.shape, o.device) != (t.dtype, t.shape, t.device)) or \
+                    (o is not None and not o.is_contiguous()):
+                raise ValueError(f"eval_votes: out[{key!r}] does not fit this batch")
+        fresh = out
+    label, sums, top3, n = fresh["label"], fresh["sums"], fresh["top3"], fresh["n"]
+    L.check(L.load().ts_eval_votes(*head, *tail, L.ptr(label), label_bytes, L.ptr(sums), L.ptr(top3), cap, L.ptr(n), L.ptr(flags),
+                                   L.stream()), "ts_eval_votes")
+    return fresh

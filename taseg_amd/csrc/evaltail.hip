@@ -9,7 +9,9 @@
 //                    points: rows of C <= 64 values move as whole rows - one launch
 // For arrays grouped by scene (every collated batch) the scene-major order IS the array order: no sort.  Anything else is
 // flagged, and the caller falls back to the sorted form (taseg_amd/pcseg/model/.../minkunet.py::unvoxelise_predictions).
+// Second half of the file: evaluation that stays on the device (ts_eval_rows, ts_eval_confusion, ts_eval_votes).
 #include "common.h"
+#include "compact.h"
 
 #define ET_MAX_SCENES 64
 
@@ -125,5 +127,383 @@ extern "C" int ts_unvoxelise(const void *logits, int32_t half, int32_t C, const 
     unvoxelise_kernel<float><<<grid, 256, 0, stream>>>((const float *)logits, C, (const long long *)counts, n_scenes, b_pts, stride_pts,
                                                        (const long long *)inv, n_pts, (float *)mapped, (long long *)pred, flags);
   TS_CHECK_LAUNCH("ts_unvoxelise");
+  return TS_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------- evaluation on the device
+// What the trainer does with the eval dictionary (R/train.py:35-52, 465-540) without the dictionary: the logits of a batch become
+// additions to a resident confusion matrix (validation) or the summed votes of one scan, their arg-max and the label payload (TTA).
+//   ts_eval_rows       point_mask given (Ms models): the stable compaction of the kept points through cp_compact - per kept point
+//                      its voxel index inside its scene, per scene the kept count K_s; three launches, no atomics for order
+//   ts_eval_confusion  one launch: a lane per kept point j < m_s of scene s, arg-max of its logits row, tally through LDS
+//   ts_eval_votes      one launch: a lane per point of the scan walks the votes in order (float32 sum in vote order: the bits of
+//                      numpy's `total += logits[v]`), arg-max, payload store, optional sums / three largest sums
+// Without a mask the kept points are a per-scene prefix of the point array: the reduce kernels index `inv` themselves.
+// Every index is range-checked before it addresses a load: inverse map entries against the scene's voxel count AND the logits'
+// row count, point / label / table positions against the lengths of their arrays.
+
+namespace {
+
+struct EtRule : CpRule {
+  typedef int Row;
+  const unsigned char *mask;
+  const int *b_pts;
+  int64_t stride;
+  const long long *inv;
+  int *rows;
+
+  __device__ __forceinline__ bool keeps(int64_t i, bool in, int &local, int *s) const {
+    *s = -1;
+    local = -1;
+    if (!in || mask[i] == 0) return false;
+    const int sc = b_pts[i * stride];
+    if (sc < 0 || sc >= n_samples) return false;      // (ts_scene_counts has raised flag bit 0)
+    *s = sc;
+    const long long v = inv[i];
+    local = (v < 0 || v > 0x7fffffffLL) ? -1 : (int)v;      // the reduce kernel checks it against the scene's voxel count
+    return true;
+  }
+
+  __device__ __forceinline__ void store(int64_t dst, int64_t, const int &local) const { rows[dst] = local; }
+};
+
+struct EtScenes {                      // per-scene layout of a batch in LDS
+  long long start_v[ET_MAX_SCENES], start_p[ET_MAX_SCENES], start_l[ET_MAX_SCENES], start_k[ET_MAX_SCENES];
+  long long cnt_v[ET_MAX_SCENES], cnt_l[ET_MAX_SCENES];      // cnt_l: min(labels of the scene, num_points)
+  long long m[ET_MAX_SCENES], start_m[ET_MAX_SCENES + 1];
+  int flags;
+};
+
+struct EtBatch {
+  const long long *counts;             // ts_scene_counts: [3][n_scenes]
+  const int *scene_flags;              // ... and its flags
+  int n_scenes;
+  const long long *inv;                // no mask: [n_pts]
+  const int *rows;                     // mask: ts_eval_rows' table [n_pts] ...
+  const long long *kept;               // ... and counts [n_scenes]
+  long long n_vox, n_pts, n_lab;
+  const long long *num_points, *num_points_ms;
+};
+
+// every thread of the block calls it (n_scenes <= ET_MAX_SCENES <= blockDim.x); ends with a barrier
+__device__ __forceinline__ void et_layout(const EtBatch &b, EtScenes &L) {
+  const int t = threadIdx.x;
+  if (t < b.n_scenes) {
+    const long long cv = b.counts[t], cp = b.counts[b.n_scenes + t], cl = b.counts[2 * b.n_scenes + t];
+    const long long np0 = b.num_points[t], np = np0 > 0 ? np0 : 0;
+    const long long k = b.kept ? b.kept[t] : cp;
+    L.cnt_v[t] = cv;
+    L.start_p[t] = cp;                 // (counts first, summed below)
+    L.start_l[t] = cl;
+    L.start_k[t] = k;
+    L.cnt_l[t] = cl < np ? cl : np;
+    L.m[t] = k < np ? k : np;
+  }
+  if (t == 0) L.flags = *b.scene_flags;
+  __syncthreads();
+  if (t < b.n_scenes && b.num_points_ms && b.num_points_ms[t] != L.start_p[t]) atomicOr(&L.flags, 32);
+  __syncthreads();
+  if (t == 0) {
+    long long av = 0, ap = 0, al = 0, ak = 0, am = 0;
+    for (int s = 0; s < b.n_scenes; ++s) {
+      const long long cv = L.cnt_v[s], cp = L.start_p[s], cl = L.start_l[s], ck = L.start_k[s];
+      L.start_v[s] = av;
+      L.start_p[s] = ap;
+      L.start_l[s] = al;
+      L.start_k[s] = ak;
+      L.start_m[s] = am;
+      av += cv;
+      ap += cp;
+      al += cl;
+      ak += ck;
+      am += L.m[s];
+    }
+    L.start_m[b.n_scenes] = am;
+  }
+  __syncthreads();
+}
+
+// logits row of kept point j < m_s of scene s, -1 where the inverse map (or, cannot happen, a position) is out of range
+__device__ __forceinline__ long long et_row(const EtBatch &b, const EtScenes &L, int s, long long j) {
+  long long local = -1;
+  if (b.kept) {
+    const long long at = L.start_k[s] + j;
+    if (at >= 0 && at < b.n_pts) local = b.rows[at];
+  } else {
+    const long long at = L.start_p[s] + j;
+    if (at >= 0 && at < b.n_pts) local = b.inv[at];
+  }
+  if (local < 0 || local >= L.cnt_v[s]) return -1;
+  const long long r = L.start_v[s] + local;
+  return r < b.n_vox ? r : -1;
+}
+
+__device__ __forceinline__ void et_argmax(float f, int c, float &best, int &arg) {
+  if (f > best || (f != f && best == best)) {      // first maximum; a NaN wins (unvoxelise_kernel, torch.argmax, np.argmax)
+    best = f;
+    arg = c;
+  }
+}
+
+template <typename T, bool VEC>
+__global__ __launch_bounds__(256) void eval_confusion_kernel(const T *__restrict__ logits, int C, EtBatch b, const void *__restrict__ labels,
+                                                             int label_bytes, unsigned long long *__restrict__ hist,
+                                                             int *__restrict__ pred, long long pred_cap, int *__restrict__ flags) {
+  __shared__ EtScenes L;
+  __shared__ unsigned tab[32 * 32];
+  const bool lds = C <= 32;
+  if (lds)
+    for (int i = threadIdx.x; i < C * C; i += 256) tab[i] = 0;
+  et_layout(b, L);
+  int bad = 0;
+  if (blockIdx.x == 0 && threadIdx.x == 0) bad = L.flags;
+  const long long total = L.start_m[b.n_scenes], step = (long long)gridDim.x * 256;
+  int s = 0;
+  for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < total; q += step) {
+    while (s < b.n_scenes - 1 && q >= L.start_m[s + 1]) ++s;
+    const long long j = q - L.start_m[s];
+    const long long r = et_row(b, L, s, j);
+    if (r < 0) {
+      bad |= 4;
+      if (pred && q < pred_cap) pred[q] = 0;
+      continue;
+    }
+    float best = -INFINITY;
+    int arg = 0;
+    if constexpr (VEC) {
+      const float4 *src = reinterpret_cast<const float4 *>(logits + r * C);
+      for (int c = 0; c < C; c += 4) {
+        const float4 v = src[c >> 2];
+        et_argmax(v.x, c, best, arg);
+        et_argmax(v.y, c + 1, best, arg);
+        et_argmax(v.z, c + 2, best, arg);
+        et_argmax(v.w, c + 3, best, arg);
+      }
+    } else {
+      const T *src = logits + r * C;
+      for (int c = 0; c < C; ++c) et_argmax((float)src[c], c, best, arg);
+    }
+    if (pred && q < pred_cap) pred[q] = arg;
+    if (L.cnt_l[s] != L.m[s]) continue;      // numpy would fail on the shapes: the scan contributes nothing (bit 3, below)
+    const long long at = L.start_l[s] + j;
+    if (at < 0 || at >= b.n_lab) continue;
+    long long lab;
+    if (label_bytes == 1)
+      lab = ((const unsigned char *)labels)[at];
+    else if (label_bytes == 4)
+      lab = ((const int *)labels)[at];
+    else
+      lab = ((const long long *)labels)[at];
+    if (lab < 0 || lab >= C) continue;       // fast_hist's k mask
+    if (lds)
+      atomicAdd(&tab[(int)lab * C + arg], 1u);
+    else
+      atomicAdd(&hist[lab * C + arg], 1ull);
+  }
+  if (blockIdx.x == 0 && (int)threadIdx.x < b.n_scenes && L.cnt_l[threadIdx.x] != L.m[threadIdx.x]) bad |= 8;
+  __syncthreads();
+  if (lds)
+    for (int i = threadIdx.x; i < C * C; i += 256) {
+      const unsigned c = tab[i];
+      if (c) atomicAdd(&hist[i], (unsigned long long)c);
+    }
+  if (bad) atomicOr(flags, bad);
+}
+
+#define ET_COLS 32       // the columns a lane sums in registers at once (a wider row takes ceil(C / 32) walks over the votes)
+
+template <typename T, bool VEC>
+__global__ __launch_bounds__(256) void eval_votes_kernel(const T *__restrict__ logits, int C, EtBatch b, void *__restrict__ label,
+                                                         int label_bytes, float *__restrict__ sums, float *__restrict__ top3,
+                                                         long long cap, long long *__restrict__ n_out, int *__restrict__ flags) {
+  __shared__ EtScenes L;
+  et_layout(b, L);
+  const bool first = blockIdx.x == 0 && threadIdx.x == 0;
+  int bad = first ? L.flags : 0;
+  const long long n = L.m[0];
+  bool equal = n <= cap;                 // (n <= n_pts / n_scenes <= cap follows from the counts; it bounds every store)
+  for (int s = 1; s < b.n_scenes; ++s) equal = equal && L.m[s] == n;
+  if (!equal) {                          // block-uniform: nothing is written
+    if (first) atomicOr(flags, bad | 16);
+    return;
+  }
+  if (first) *n_out = n;
+  const long long j = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (j < n) {
+    float best = -INFINITY, t0 = -INFINITY, t1 = -INFINITY, t2 = -INFINITY;
+    int arg = 0;
+    for (int c0 = 0; c0 < C; c0 += ET_COLS) {
+      float acc[ET_COLS];
+#pragma unroll
+      for (int k = 0; k < ET_COLS; ++k) acc[k] = 0.f;
+      bool any = false;
+      for (int v = 0; v < b.n_scenes; ++v) {
+        const long long r = et_row(b, L, v, j);
+        if (r < 0) {
+          bad |= 4;
+          continue;
+        }
+        const T *src = logits + r * C + c0;
+        if constexpr (VEC) {
+#pragma unroll
+          for (int k = 0; k < ET_COLS; k += 4) {
+            if (c0 + k < C) {
+              const float4 x = *reinterpret_cast<const float4 *>(src + k);
+              if (any) {
+                acc[k] += x.x;
+                acc[k + 1] += x.y;
+                acc[k + 2] += x.z;
+                acc[k + 3] += x.w;
+              } else {
+                acc[k] = x.x;
+                acc[k + 1] = x.y;
+                acc[k + 2] = x.z;
+                acc[k + 3] = x.w;
+              }
+            }
+          }
+        } else {
+#pragma unroll
+          for (int k = 0; k < ET_COLS; ++k) {
+            if (c0 + k < C) {
+              const float x = (float)src[k];
+              acc[k] = any ? acc[k] + x : x;
+            }
+          }
+        }
+        any = true;
+      }
+#pragma unroll
+      for (int k = 0; k < ET_COLS; ++k) {
+        if (c0 + k < C) {
+          const float f = acc[k];
+          et_argmax(f, c0 + k, best, arg);
+          if (f > t0) {
+            t2 = t1;
+            t1 = t0;
+            t0 = f;
+          } else if (f > t1) {
+            t2 = t1;
+            t1 = f;
+          } else if (f > t2) {
+            t2 = f;
+          }
+          if (sums && !VEC) sums[j * C + c0 + k] = f;
+        }
+      }
+      if (sums && VEC) {
+#pragma unroll
+        for (int k = 0; k < ET_COLS; k += 4)
+          if (c0 + k < C) *reinterpret_cast<float4 *>(sums + j * C + c0 + k) = make_float4(acc[k], acc[k + 1], acc[k + 2], acc[k + 3]);
+      }
+    }
+    if (label_bytes == 1)
+      ((unsigned char *)label)[j] = (unsigned char)arg;
+    else
+      ((unsigned *)label)[j] = (unsigned)arg;
+    if (top3) {
+      top3[j * 3] = t0;
+      top3[j * 3 + 1] = t1;
+      top3[j * 3 + 2] = t2;
+    }
+  }
+  if (bad) atomicOr(flags, bad);
+}
+
+int et_check_batch(const char *name, const void *logits, int32_t C, int64_t n_vox, const int64_t *counts, const int32_t *scene_flags,
+                   int32_t n_scenes, const int64_t *inv, const int32_t *rows, const int64_t *kept, int64_t n_pts,
+                   const int64_t *num_points, int32_t *flags) {
+  TS_REQUIRE(C > 0 && C <= 4096 && n_scenes > 0 && n_scenes <= ET_MAX_SCENES && n_vox >= 0 && n_pts >= 0 && n_vox < (int64_t)1 << 40 &&
+                 n_pts < (int64_t)1 << 40,
+             TS_ERR_INVALID_ARGUMENT, "%s: bad sizes (at most %d scenes)", name, ET_MAX_SCENES);
+  TS_REQUIRE(counts && scene_flags && num_points && flags, TS_ERR_INVALID_ARGUMENT, "%s: null pointer", name);
+  TS_REQUIRE(!(kept && inv) && !(rows && !kept), TS_ERR_INVALID_ARGUMENT,
+             "%s: either the inverse map or the table and counts of ts_eval_rows", name);
+  TS_REQUIRE(n_pts == 0 || ((kept ? rows != nullptr : inv != nullptr) && (n_vox == 0 || logits)), TS_ERR_INVALID_ARGUMENT,
+             "%s: null pointer", name);
+  return TS_OK;
+}
+
+}  // namespace
+
+extern "C" size_t ts_eval_rows_workspace_bytes(int64_t n_pts, int32_t n_scenes) {
+  const int64_t n = std::max<int64_t>(n_pts, 0);
+  return cp_compact_bytes(n, n_scenes) + ts_align_up((size_t)n * 8, 256) + ts_align_up((size_t)n * 4, 256);
+}
+
+extern "C" int ts_eval_rows(const uint8_t *point_mask, const int32_t *b_pts, int64_t stride_pts, const int64_t *inv, int64_t n_pts,
+                            int32_t n_scenes, int32_t *rows, int64_t *kept, void *ws, size_t ws_bytes, ts_stream_t stream) {
+  TS_REQUIRE(n_pts >= 0 && n_pts < (int64_t)1 << 30 && n_scenes >= 1 && n_scenes <= ET_MAX_SCENES && stride_pts > 0,
+             TS_ERR_INVALID_ARGUMENT, "ts_eval_rows: bad sizes (at most %d scenes)", ET_MAX_SCENES);
+  TS_REQUIRE(kept && ws && ((uintptr_t)ws & 7) == 0, TS_ERR_INVALID_ARGUMENT, "ts_eval_rows: null or unaligned pointer");
+  TS_REQUIRE(n_pts == 0 || (point_mask && b_pts && inv && rows), TS_ERR_INVALID_ARGUMENT, "ts_eval_rows: null pointer");
+  TS_REQUIRE(ws_bytes >= ts_eval_rows_workspace_bytes(n_pts, n_scenes), TS_ERR_WORKSPACE_TOO_SMALL, "ts_eval_rows: workspace too small");
+  const size_t cp_bytes = cp_compact_bytes(n_pts, n_scenes);
+  int64_t *sample64 = (int64_t *)((char *)ws + cp_bytes);      // the driver's per-survivor samples: not read here
+  int32_t *sample32 = (int32_t *)((char *)sample64 + ts_align_up((size_t)n_pts * 8, 256));
+  EtRule r;
+  r.n_rows = n_pts;
+  r.capacity = n_pts;
+  r.n_samples = n_scenes;
+  r.out_sample = sample64;
+  r.out_sample32 = sample32;
+  r.mask = point_mask;
+  r.b_pts = b_pts;
+  r.stride = stride_pts;
+  r.inv = (const long long *)inv;
+  r.rows = rows;
+  return cp_compact(r, "ts_eval_rows", kept, ws, cp_bytes, (hipStream_t)stream);
+}
+
+extern "C" int ts_eval_confusion(const void *logits, int32_t half, int32_t C, int64_t n_vox, const int64_t *counts,
+                                 const int32_t *scene_flags, int32_t n_scenes, const int64_t *inv, const int32_t *rows,
+                                 const int64_t *kept, int64_t n_pts, const void *labels, int32_t label_bytes, int64_t n_lab,
+                                 const int64_t *num_points, const int64_t *num_points_ms, int64_t *hist, int32_t *pred,
+                                 int64_t pred_cap, int32_t *flags, ts_stream_t stream) {
+  const int rc = et_check_batch("ts_eval_confusion", logits, C, n_vox, counts, scene_flags, n_scenes, inv, rows, kept, n_pts, num_points, flags);
+  if (rc != TS_OK) return rc;
+  TS_REQUIRE(hist && n_lab >= 0 && (n_lab == 0 || labels) && (label_bytes == 1 || label_bytes == 4 || label_bytes == 8) && pred_cap >= 0,
+             TS_ERR_INVALID_ARGUMENT, "ts_eval_confusion: bad arguments (labels of 1, 4 or 8 bytes)");
+  const EtBatch b = {(const long long *)counts, scene_flags, n_scenes, (const long long *)inv, rows, (const long long *)kept,
+                     n_vox, n_pts, n_lab, (const long long *)num_points, (const long long *)num_points_ms};
+  // (without points one block still runs: it carries ts_scene_counts' flags and the per-scene checks over)
+  const unsigned grid = (unsigned)std::min<int64_t>(std::max<int64_t>(ts_cdiv(n_pts, 256), 1), 1024);
+  unsigned long long *h = (unsigned long long *)hist;
+  if (half)
+    eval_confusion_kernel<_Float16, false><<<grid, 256, 0, (hipStream_t)stream>>>((const _Float16 *)logits, C, b, labels, label_bytes, h, pred,
+                                                                                  pred_cap, flags);
+  else if (C % 4 == 0 && ((uintptr_t)logits & 15) == 0)
+    eval_confusion_kernel<float, true><<<grid, 256, 0, (hipStream_t)stream>>>((const float *)logits, C, b, labels, label_bytes, h, pred,
+                                                                              pred_cap, flags);
+  else
+    eval_confusion_kernel<float, false><<<grid, 256, 0, (hipStream_t)stream>>>((const float *)logits, C, b, labels, label_bytes, h, pred,
+                                                                               pred_cap, flags);
+  TS_CHECK_LAUNCH("ts_eval_confusion");
+  return TS_OK;
+}
+
+extern "C" int ts_eval_votes(const void *logits, int32_t half, int32_t C, int64_t n_vox, const int64_t *counts, const int32_t *scene_flags,
+                             int32_t n_scenes, const int64_t *inv, const int32_t *rows, const int64_t *kept, int64_t n_pts,
+                             const int64_t *num_points, const int64_t *num_points_ms, void *label, int32_t label_bytes, float *sums,
+                             float *top3, int64_t cap, int64_t *n_out, int32_t *flags, ts_stream_t stream) {
+  const int rc = et_check_batch("ts_eval_votes", logits, C, n_vox, counts, scene_flags, n_scenes, inv, rows, kept, n_pts, num_points, flags);
+  if (rc != TS_OK) return rc;
+  TS_REQUIRE(cap >= 0 && n_out && (cap == 0 || label) && (label_bytes == 1 || label_bytes == 4) && (!top3 || C >= 3), TS_ERR_INVALID_ARGUMENT,
+             "ts_eval_votes: bad arguments (labels of 1 or 4 bytes; the three largest sums need 3 classes)");
+  TS_REQUIRE(label_bytes == 1 || ((uintptr_t)label & 3) == 0, TS_ERR_INVALID_ARGUMENT, "ts_eval_votes: unaligned label buffer");
+  const EtBatch b = {(const long long *)counts, scene_flags, n_scenes, (const long long *)inv, rows, (const long long *)kept,
+                     n_vox, n_pts, 0, (const long long *)num_points, (const long long *)num_points_ms};
+  const unsigned grid = (unsigned)std::max<int64_t>(ts_cdiv(cap, 256), 1);
+  TS_REQUIRE(ts_cdiv(cap, 256) < (int64_t)1 << 31, TS_ERR_INVALID_ARGUMENT, "ts_eval_votes: too many rows");
+  if (half)
+    eval_votes_kernel<_Float16, false><<<grid, 256, 0, (hipStream_t)stream>>>((const _Float16 *)logits, C, b, label, label_bytes, sums, top3, cap,
+                                                                              (long long *)n_out, flags);
+  else if (C % 4 == 0 && ((uintptr_t)logits & 15) == 0 && (!sums || ((uintptr_t)sums & 15) == 0))
+    eval_votes_kernel<float, true><<<grid, 256, 0, (hipStream_t)stream>>>((const float *)logits, C, b, label, label_bytes, sums, top3, cap,
+                                                                          (long long *)n_out, flags);
+  else
+    eval_votes_kernel<float, false><<<grid, 256, 0, (hipStream_t)stream>>>((const float *)logits, C, b, label, label_bytes, sums, top3, cap,
+                                                                           (long long *)n_out, flags);
+  TS_CHECK_LAUNCH("ts_eval_votes");
   return TS_OK;
 }

@@ -124,13 +124,72 @@ def _staged(model, batches: Iterable[Dict], prefetch: bool):
         pf.close()
 
 
+def _prediction_path(save_dir, name, dataset):
+    if dataset.startswith("nuscenes"):
+        return os.path.join(save_dir, name.split("/")[-1])
+    # .../sequences/<seq>/velodyne/<frame>.bin -> sequences/<seq>/predictions/<frame>.label
+    seq_id, frame_id = name.split("/")[-3], name.split("/")[-1]
+    return os.path.join(save_dir, "sequences", seq_id, "predictions", frame_id.replace("bin", "label"))
+
+
+def _evaluate_on_device(model, batches, num_class, tta_votes, dataset, save_dir, prefetch, scores):
+    """evaluate(on_device=True): see there"""
+    import inspect
+    import torch
+    from .model.segmentor.voxel.minkunet.minkunet import DeviceEvalTail
+    if "device_tail" not in inspect.signature(model.forward).parameters:
+        raise ValueError(f"{type(model).__name__}.forward takes no `device_tail`: evaluate it with on_device=False")
+    tail = DeviceEvalTail(num_class, next(model.parameters()).device, votes=tta_votes, dataset=dataset, scores=scores)
+    preds, kept_scores = [], []
+    was_training = model.training
+    model.eval()
+    try:
+        pending = None
+
+        def collect(p):
+            out = p.result()
+            preds.append(out["payload"])
+            if scores is not None:
+                kept_scores.append(out["scores"])
+            if save_dir is not None:
+                write_prediction(_prediction_path(save_dir, out["name"][0], dataset), out["payload"])
+
+        for batch in _staged(model, batches, prefetch):
+            with torch.no_grad():
+                cur = model(batch, device_tail=tail)
+            # TTA: one batch in flight - the next forward pass is issued before the host waits for this payload
+            if pending is not None:
+                collect(pending)
+            pending = cur if tta_votes else None
+        if pending is not None:
+            collect(pending)
+        if not tta_votes:
+            full = tail.read()                                   # the ONE host read of a validation run
+    finally:
+        model.train(was_training)
+    if tta_votes:
+        return {"predictions": preds, "scores": kept_scores} if scores is not None else {"predictions": preds}
+    hist = np.ascontiguousarray(full[1:, 1:])                    # fast_hist_crop: rows and columns 1 .. num_class - 1
+    iou = per_class_iu(hist)
+    return {"iou": iou, "miou": float(np.nanmean(iou) * 100), "hist": hist}
+
+
 def evaluate(model, batches: Iterable[Dict], num_class: int, tta_votes: int = 0, dataset: str = "semantickitti",
-             save_dir: str = None, prefetch: bool = True) -> Dict:
+             save_dir: str = None, prefetch: bool = True, on_device: bool = False, scores: str = None) -> Dict:
     """The loop body of Trainer.evaluate (R/train.py:465-540) over already collated, device-resident batches: validation
     (mIoU over the classes 1 .. num_class - 1) or, with tta_votes > 0, vote accumulation and optional writing of one
     prediction file per scan.  Returns {"iou", "miou", "hist"} or {"predictions": [...]}.  prefetch: stage the index plan of the
-    next batch while this one runs (same results)."""
+    next batch while this one runs (same results).
+    on_device=True (models whose forward takes `device_tail`: MinkUNet, MinkUNetMs): the tail of every batch stays on the device
+    (csrc/evaltail.hip).  Validation adds into a resident confusion matrix - no device -> host copy per batch, ONE host read at the
+    end (after parallel.reduce_confusion); TTA sums the votes, takes the arg-max and sends only the label payload to the host - with
+    scores="all" / "top3" also the summed logits / their three largest (R/train.py:487-501), returned as "scores".  Same results as
+    the host path; what the host path raises per batch surfaces at the read."""
     import torch
+    if scores is not None and not (on_device and tta_votes):
+        raise ValueError("scores are kept by the device tail of a TTA run: on_device=True and tta_votes > 0")
+    if on_device:
+        return _evaluate_on_device(model, batches, num_class, tta_votes, dataset, save_dir, prefetch, scores)
     unique_label = np.arange(num_class - 1)
     hist, preds = np.zeros((num_class - 1, num_class - 1), dtype=np.int64), []
     was_training = model.training
@@ -160,13 +219,7 @@ def evaluate(model, batches: Iterable[Dict], num_class: int, tta_votes: int = 0,
                 payload = vote_payload(accumulate_votes(ret, tta_votes), dataset)
                 preds.append(payload)
                 if save_dir is not None:
-                    name = ret["name"][0]
-                    if dataset.startswith("nuscenes"):
-                        path = os.path.join(save_dir, name.split("/")[-1])
-                    else:       # .../sequences/<seq>/velodyne/<frame>.bin -> sequences/<seq>/predictions/<frame>.label
-                        seq_id, frame_id = name.split("/")[-3], name.split("/")[-1]
-                        path = os.path.join(save_dir, "sequences", seq_id, "predictions", frame_id.replace("bin", "label"))
-                    write_prediction(path, payload)
+                    write_prediction(_prediction_path(save_dir, ret["name"][0], dataset), payload)
             else:
                 hist += scan_confusions(ret, unique_label)
     finally:

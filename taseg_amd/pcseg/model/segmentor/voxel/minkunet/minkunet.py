@@ -21,7 +21,7 @@ from taseg_amd.options import options
 from .utils import voxel_to_point, voxelize_index
 from . import stage_program as _SP
 
-__all__ = ["MinkUNet", "unvoxelise_predictions"]
+__all__ = ["MinkUNet", "unvoxelise_predictions", "DeviceEvalTail"]
 
 import contextlib
 import os as _os
@@ -654,6 +654,113 @@ def _tail_to_host(meta, result, mapped, labels_sorted, want_probs, defer, names,
     return pending if defer else pending.result()
 
 
+class PendingVotes:
+    """One TTA batch of the device tail in flight: the label payload (and the chosen scores) of the scan are on their way into
+    page-locked buffers behind one event.  `result()` waits for it, raises what the host path would have raised, and returns
+    {"payload": [n, 1] uint32 / uint8, "scores": [n, C] / [n, 3] float32 or None, "name"} as arrays of their own."""
+
+    def __init__(self, event, meta_h, label_h, scores_h, width, names, nuscenes, keep):
+        self.event, self.meta_h, self.label_h, self.scores_h, self.width = event, meta_h, label_h, scores_h, width
+        self.names, self.nuscenes, self._keep, self._out = names, nuscenes, keep, None
+
+    def result(self):
+        if self._out is None:
+            self.event.synchronize()
+            flags, n = (int(v) for v in self.meta_h.numpy())
+            DeviceEvalTail.raise_flags(flags, len(self.names))
+            import numpy as np
+            label = np.array(self.label_h.numpy()[:n]).reshape(n, 1)
+            if self.nuscenes:
+                if (label == 0).any():
+                    raise ValueError("nuScenes submission must not contain the ignored class 0 (R/train.py:523)")
+            else:
+                label = label.view(np.uint32)
+            scores = None if self.scores_h is None else np.array(self.scores_h.numpy()[:n * self.width]).reshape(n, self.width)
+            self._out, self._keep = {"payload": label, "scores": scores, "name": self.names}, None
+        return self._out
+
+
+class DeviceEvalTail:
+    """Where `model(batch, device_tail=tail)` leaves an evaluation batch instead of un-voxelising it to the host
+    (csrc/evaltail.hip: ts_scene_counts + one launch, three more where a point_mask has to be compacted):
+
+    votes == 0 (validation)  every scene is a scan: additions to `hist`, the resident [num_class, num_class] int64 confusion matrix
+                             (R/train.py:35-52 fast_hist before its crop).  Nothing leaves the device until `read()`.
+    votes == V  (TTA)        the V scenes are the votes of one scan: float32 sum in vote order, arg-max, label payload (uint32, or
+                             uint8 for nuScenes) and optionally scores ("all": the sums, "top3": the three largest) - the call
+                             returns a PendingVotes; only payload and scores cross to the host.
+    `flags` collects what the host path raises on (include/taseg_hip.h ts_eval_*); it is read with the matrix / the payload."""
+
+    def __init__(self, num_class, device, votes=0, dataset="semantickitti", scores=None):
+        if scores not in (None, "all", "top3"):
+            raise ValueError(f"scores must be None, 'all' or 'top3' (got {scores!r})")
+        self.num_class, self.votes, self.scores = int(num_class), int(votes), scores
+        self.nuscenes = dataset.startswith("nuscenes")
+        self.hist = torch.zeros((self.num_class, self.num_class), dtype=torch.int64, device=device)
+        self.n_scenes = 0
+        self.flags = torch.zeros(1, dtype=torch.int32, device=device)
+
+    @staticmethod
+    def raise_flags(flags, n_scenes):
+        """the host path's exceptions (PendingPredictions.result, accumulate_votes, numpy) for the bits of `flags`"""
+        if flags & 1:
+            raise IndexError(f"batch indices beyond the {n_scenes} scenes of the batch")
+        if flags & 2:
+            raise ValueError("a batch is not grouped by scene in ascending order (sparse_collate builds it so): the device tail "
+                             "does not sort - evaluate it with on_device=False")
+        if flags & 4:
+            raise IndexError("inverse_map names a voxel outside its scene")
+        if flags & 32:
+            raise IndexError("num_points_ms does not match the inverse map's points per scene")
+        if flags & 8:
+            raise IndexError("predictions and labels of a scan differ in length (labels per scene / num_points / kept points)")
+        if flags & 16:
+            raise ValueError("votes must cover the same points (one scan per TTA batch)")
+
+    def run(self, out, vox_batch, invs, all_labels, num_points, point_mask=None, num_points_ms=None, names=None):
+        if out.shape[1] != self.num_class:
+            raise ValueError(f"the model has {out.shape[1]} classes, the evaluation {self.num_class}")
+        pts_batch = invs.C[:, -1]
+        self.n_scenes = n_scenes = len(names) if names is not None else int(torch.as_tensor(num_points).numel())
+        mask = None if point_mask is None else point_mask.to(out.device)
+        if not self.votes:
+            B.eval_confusion(out, vox_batch, pts_batch, invs.F, all_labels.F.reshape(-1), all_labels.C[:, -1], num_points, self.hist,
+                             self.flags, point_mask=mask, num_points_ms=num_points_ms)
+            return self
+        if n_scenes != self.votes:
+            raise ValueError(f"TTA batch holds {n_scenes} votes, {self.votes} expected (one scan per batch, collate_batch_tta)")
+        got = B.eval_votes(out, vox_batch, pts_batch, invs.F, num_points, self.flags, point_mask=mask, num_points_ms=num_points_ms,
+                           label_bytes=1 if self.nuscenes else 4, want_sums=self.scores == "all", want_top3=self.scores == "top3")
+        scores = got["sums"] if self.scores == "all" else got["top3"]
+        meta = torch.cat([self.flags.long(), got["n"]])
+        _pinned.next_generation()
+        side = _copy_stream(out.device) if _COPY_STREAM else None
+        if side is not None:
+            ready = torch.cuda.Event()
+            ready.record()
+            side.wait_event(ready)
+
+        def to_host(key, t):
+            h = _pinned.take(key, t, t.numel())
+            h.copy_(t.reshape(-1), non_blocking=True)
+            return h
+        with (torch.cuda.stream(side) if side is not None else contextlib.nullcontext()):
+            meta_h, label_h = to_host("vote_meta", meta), to_host("vote_label", got["label"])
+            scores_h = None if scores is None else to_host("vote_scores", scores)
+            event = torch.cuda.Event()
+            event.record()
+        return PendingVotes(event, meta_h, label_h, scores_h, 0 if scores is None else scores.shape[1], names, self.nuscenes,
+                            (meta, got, scores))
+
+    def read(self):
+        """validation: the matrix summed over the ranks (parallel.reduce_confusion) and the flags in ONE host read"""
+        from taseg_amd.parallel import reduce_confusion
+        hist = reduce_confusion(self.hist.clone())       # (the all-reduce is in place: the resident matrix stays this rank's)
+        both = torch.cat([hist.reshape(-1), self.flags.long()]).cpu().numpy()
+        self.raise_flags(int(both[-1]), self.n_scenes)
+        return both[:-1].reshape(self.num_class, self.num_class)
+
+
 class MinkUNet(MinkUNetBackbone):
     """Single-frame model: re-voxelises `batch_dict['lidar']` on device, then the U-Net
     (minkunet.py:385-455)."""
@@ -666,7 +773,7 @@ class MinkUNet(MinkUNetBackbone):
         batch_dict["_plan"] = plan
         return plan
 
-    def forward(self, batch_dict, return_logit=False, return_tta=False, defer=False):
+    def forward(self, batch_dict, return_logit=False, return_tta=False, defer=False, device_tail=None):
         x = batch_dict["lidar"]
         x.F = x.F[:, :self.in_feature_dim]
         plan = batch_dict.get("_plan") or self.prepare(batch_dict)
@@ -677,6 +784,9 @@ class MinkUNet(MinkUNetBackbone):
             target = batch_dict["targets"].F.long().cuda(non_blocking=True)
             return self._train_outputs(out, target, batch_dict["lidar"].C[:, :3].float(), batch_dict["offset"])
 
+        if device_tail is not None:       # evaluation on the device (DeviceEvalTail): nothing is un-voxelised to the host
+            return device_tail.run(out, x.C[:, -1], batch_dict["inverse_map"], batch_dict["targets_mapped"], batch_dict["num_points"],
+                                   names=batch_dict["name"])
         return unvoxelise_predictions(out, x.C[:, -1], batch_dict["inverse_map"], batch_dict["targets_mapped"],
                                       batch_dict["num_points"], return_logit or return_tta, names=batch_dict["name"], defer=defer)
 

@@ -18,7 +18,7 @@ class MinkUNetMs(MinkUNetBackbone):
         batch_dict["_plan"] = plan
         return plan
 
-    def forward(self, batch_dict, return_logit=False, return_tta=False, defer=False):
+    def forward(self, batch_dict, return_logit=False, return_tta=False, defer=False, device_tail=None):
         x_ms = batch_dict["lidar_ms"]
         x_ms.F = x_ms.F[:, :self.in_feature_dim]
         plan = batch_dict.get("_plan") or self.prepare(batch_dict)
@@ -29,6 +29,10 @@ class MinkUNetMs(MinkUNetBackbone):
             return self._train_outputs(out_ms, target_ms, batch_dict["lidar_ms"].C[:, :3].float(),
                                        batch_dict["offset_ms"])
 
+        if device_tail is not None:       # evaluation on the device (minkunet.DeviceEvalTail): the mask is compacted there
+            return device_tail.run(out_ms, x_ms.C[:, -1], batch_dict["inverse_map_ms"], batch_dict["targets_mapped"],
+                                   batch_dict["num_points"], point_mask=batch_dict["point_mask"],
+                                   num_points_ms=batch_dict["num_points_ms"], names=batch_dict["name"])
         # evaluation: un-voxelise onto every point of the fused cloud, keep the current-frame
         # points (`point_mask`), trim to the scan's own point count (minkunet_ms.py:433-458)
         return unvoxelise_predictions(out_ms, x_ms.C[:, -1], batch_dict["inverse_map_ms"], batch_dict["targets_mapped"],
