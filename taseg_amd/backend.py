@@ -1877,18 +1877,20 @@ def _eval_flags(flags, what):
 
 
 def eval_confusion(logits, vox_batch, pts_batch, inv, labels, lab_batch, num_points, hist, flags, point_mask=None,
-                   num_points_ms=None, want_pred=False):
+                   num_points_ms=None, want_pred=False, want_counts=False):
     """csrc/evaltail.hip: the confusion-matrix additions of a batch whose scenes are scans (R/train.py:35-52, 535-540) without a
     host read: ts_scene_counts + one launch (three more where point_mask has to be compacted).  logits [n_vox, C] float32 / half;
     vox_batch / pts_batch / lab_batch: the int32 scene index of every logits row / point / label, grouped by scene; inv [n_pts] the
     point's voxel inside its scene; labels [n_lab] uint8 / int32 / int64; num_points (num_points_ms) one integer per scene.
     hist [C, C] int64 on the device is ADDED to; flags (one int32 on the device) is OR-ed into (include/taseg_hip.h) - the caller
     clears both when it wants to and reads them when it wants to.  want_pred: returns the arg-max of the kept rows as int32 [n_pts]
-    (scene-major, the first sum of min(kept, num_points) rows are written)."""
+    (scene-major, the first sum of min(kept, num_points) rows are written).  want_counts: returns (pred, m) with m int64 [scenes] on
+    the device, m_s = min(kept, num_points) - the rows of `pred` that belong to scene s."""
     L.require_device(labels, hist, flags)
     if labels.dtype not in _EVAL_LABEL_BYTES or labels.dim() != 1:
         raise ValueError(f"eval_confusion: labels must be a 1-d uint8, int32 or int64 tensor (got {labels.dtype})")
-    head, tail, _, keep = _eval_batch(logits, vox_batch, pts_batch, inv, lab_batch, num_points, point_mask, num_points_ms, "eval_confusion")
+    head, tail, n_scenes, keep = _eval_batch(logits, vox_batch, pts_batch, inv, lab_batch, num_points, point_mask, num_points_ms,
+                                             "eval_confusion")
     c = head[2]
     if hist.dtype != torch.int64 or tuple(hist.shape) != (c, c) or not hist.is_contiguous():
         raise ValueError(f"eval_confusion: hist must be a contiguous int64 [{c}, {c}] tensor")
@@ -1900,6 +1902,12 @@ def eval_confusion(logits, vox_batch, pts_batch, inv, labels, lab_batch, num_poi
     pred = torch.empty(n_pts, dtype=torch.int32, device=logits.device) if want_pred else None
     L.check(L.load().ts_eval_confusion(*head, L.ptr(labels), _EVAL_LABEL_BYTES[labels.dtype], labels.shape[0], *tail, L.ptr(hist), L.ptr(pred),
                                        n_pts if want_pred else 0, L.ptr(flags), L.stream()), "ts_eval_confusion")
+    if want_counts:
+        # m_s = min(kept points of the scene, num_points) as the kernel forms it (et_layout): meta is [flags 8 | voxels, points,
+        # labels per scene | kept per scene], the kept counts are the points' own where no mask was compacted
+        meta, np_d = keep[3], keep[4]
+        at = 8 + (3 if point_mask is not None else 1) * n_scenes
+        return pred, torch.minimum(meta[at:at + n_scenes], np_d.clamp(min=0))
     return pred
 
 

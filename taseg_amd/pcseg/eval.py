@@ -35,13 +35,39 @@ def accumulate_votes(ret_dict: Dict, votes: int) -> np.ndarray:
 def vote_payload(point_logits: np.ndarray, dataset: str = "semantickitti") -> np.ndarray:
     """What the trainer writes per scan: arg-max class as [n, 1] uint32 (.label, SemanticKITTI; R/train.py:499-503) or
     uint8 (nuScenes lidarseg .bin; :519-523, where class 0 must not occur)."""
-    pred = np.expand_dims(np.argmax(point_logits, axis=1), axis=1)
+    return _class_payload(np.argmax(point_logits, axis=1), dataset)
+
+
+def _class_payload(classes: np.ndarray, dataset: str) -> np.ndarray:
+    """vote_payload behind its arg-max: the classes of one scan as the [n, 1] array of the dataset's label file"""
+    pred = np.expand_dims(np.asarray(classes).reshape(-1), axis=1)
     if dataset.startswith("nuscenes"):
         out = pred.astype(np.uint8)
         if (out == 0).any():
             raise ValueError("nuScenes submission must not contain the ignored class 0 (R/train.py:523)")
         return out
     return pred.astype(np.uint32)
+
+
+def _remap_table(remap, num_class: int) -> np.ndarray:
+    """evaluate(remap=...): a {class: raw id} dictionary (remap_lut builds its table) or such a table, as a 1-d int32 array with an
+    entry for every class the model can predict"""
+    if isinstance(remap, dict):
+        if not remap:
+            raise ValueError("remap: an empty dictionary")
+        remap = remap_lut(remap)
+    elif not isinstance(remap, np.ndarray):
+        raise TypeError(f"remap must be a {{class: raw id}} dictionary or a lookup array as remap_lut builds (got {type(remap).__name__})")
+    if remap.ndim != 1 or remap.dtype.kind not in "iu":
+        raise TypeError(f"remap: the lookup array must be 1-d and integer (got {remap.dtype}, {remap.shape})")
+    if remap.shape[0] < num_class:
+        raise ValueError(f"remap: the table has {remap.shape[0]} entries, the model {num_class} classes")
+    return np.ascontiguousarray(remap.astype(np.int32))
+
+
+def _remapped(payload: np.ndarray, lut) -> np.ndarray:
+    """a payload through the table (remap_labels: a class has no instance bits, so all of it goes through), shape and type kept"""
+    return payload if lut is None else remap_labels(payload, lut).reshape(-1, 1).astype(payload.dtype)
 
 
 def write_prediction(path: str, payload: np.ndarray) -> str:
@@ -132,14 +158,15 @@ def _prediction_path(save_dir, name, dataset):
     return os.path.join(save_dir, "sequences", seq_id, "predictions", frame_id.replace("bin", "label"))
 
 
-def _evaluate_on_device(model, batches, num_class, tta_votes, dataset, save_dir, prefetch, scores):
+def _evaluate_on_device(model, batches, num_class, tta_votes, dataset, save_dir, prefetch, scores, predictions, remap):
     """evaluate(on_device=True): see there"""
     import inspect
     import torch
     from .model.segmentor.voxel.minkunet.minkunet import DeviceEvalTail
     if "device_tail" not in inspect.signature(model.forward).parameters:
         raise ValueError(f"{type(model).__name__}.forward takes no `device_tail`: evaluate it with on_device=False")
-    tail = DeviceEvalTail(num_class, next(model.parameters()).device, votes=tta_votes, dataset=dataset, scores=scores)
+    tail = DeviceEvalTail(num_class, next(model.parameters()).device, votes=tta_votes, dataset=dataset, scores=scores,
+                          predictions=predictions, remap=remap)
     preds, kept_scores = [], []
     was_training = model.training
     model.eval()
@@ -148,6 +175,12 @@ def _evaluate_on_device(model, batches, num_class, tta_votes, dataset, save_dir,
 
         def collect(p):
             out = p.result()
+            if not tta_votes:                                    # validation with predictions=True: one payload per scan
+                preds.extend(out["payload"])
+                if save_dir is not None:
+                    for name, payload in zip(out["name"], out["payload"]):
+                        write_prediction(_prediction_path(save_dir, name, dataset), payload)
+                return
             preds.append(out["payload"])
             if scores is not None:
                 kept_scores.append(out["scores"])
@@ -157,39 +190,56 @@ def _evaluate_on_device(model, batches, num_class, tta_votes, dataset, save_dir,
         for batch in _staged(model, batches, prefetch):
             with torch.no_grad():
                 cur = model(batch, device_tail=tail)
-            # TTA: one batch in flight - the next forward pass is issued before the host waits for this payload
+            # one batch in flight - the next forward pass is issued before the host waits for this payload
             if pending is not None:
                 collect(pending)
-            pending = cur if tta_votes else None
+            pending = cur if (tta_votes or predictions) else None
         if pending is not None:
             collect(pending)
         if not tta_votes:
-            full = tail.read()                                   # the ONE host read of a validation run
+            full = tail.read()                                   # the ONE host read of a validation run's matrix
     finally:
         model.train(was_training)
     if tta_votes:
         return {"predictions": preds, "scores": kept_scores} if scores is not None else {"predictions": preds}
     hist = np.ascontiguousarray(full[1:, 1:])                    # fast_hist_crop: rows and columns 1 .. num_class - 1
     iou = per_class_iu(hist)
-    return {"iou": iou, "miou": float(np.nanmean(iou) * 100), "hist": hist}
+    out = {"iou": iou, "miou": float(np.nanmean(iou) * 100), "hist": hist}
+    if predictions:
+        out["predictions"] = preds
+    return out
 
 
 def evaluate(model, batches: Iterable[Dict], num_class: int, tta_votes: int = 0, dataset: str = "semantickitti",
-             save_dir: str = None, prefetch: bool = True, on_device: bool = False, scores: str = None) -> Dict:
+             save_dir: str = None, prefetch: bool = True, on_device: bool = False, scores: str = None, predictions: bool = False,
+             remap=None) -> Dict:
     """The loop body of Trainer.evaluate (R/train.py:465-540) over already collated, device-resident batches: validation
     (mIoU over the classes 1 .. num_class - 1) or, with tta_votes > 0, vote accumulation and optional writing of one
     prediction file per scan.  Returns {"iou", "miou", "hist"} or {"predictions": [...]}.  prefetch: stage the index plan of the
     next batch while this one runs (same results).
-    on_device=True (models whose forward takes `device_tail`: MinkUNet, MinkUNetMs): the tail of every batch stays on the device
-    (csrc/evaltail.hip).  Validation adds into a resident confusion matrix - no device -> host copy per batch, ONE host read at the
-    end (after parallel.reduce_confusion); TTA sums the votes, takes the arg-max and sends only the label payload to the host - with
-    scores="all" / "top3" also the summed logits / their three largest (R/train.py:487-501), returned as "scores".  Same results as
-    the host path; what the host path raises per batch surfaces at the read."""
+    predictions=True (validation only): the result also holds "predictions", one [n, 1] label payload per scan in the order of the
+    scans (uint32, or uint8 for nuScenes: vote_payload of the scan's single-vote logits), and with `save_dir` every scan is written
+    to its prediction file - the recipe's "history predictions" (R/docs/TASeg_Sem.md) from validation batches of any size.
+    Without it `save_dir` is ignored in a validation run.
+    remap: a {class: raw id} dictionary (data.semantickitti.LEARNING_MAP_INV) or a table as remap_lut builds; the payloads of a
+    TTA run or of predictions=True go through it (remap_labels: R/tta_remap.py --inverse) before they are returned or written.
+    on_device=True (all five segmentors: MinkUNet, MinkUNetMs, MinkUNetMsMm, MinkUNetMsMmNus, MinkUNetMsKd - every forward that
+    takes `device_tail`): the tail of every batch stays on the device (csrc/evaltail.hip).  Validation adds into a resident
+    confusion matrix - no device -> host copy per batch, ONE host read at the end (after parallel.reduce_confusion); with
+    predictions=True the label bytes and the per-scan counts of each batch follow it to the host, one batch in flight.  TTA sums
+    the votes, takes the arg-max and sends only the label payload to the host - with scores="all" / "top3" also the summed
+    logits / their three largest (R/train.py:487-501), returned as "scores".  `remap` is a table gather on the device.  Same
+    results as the host path; what the host path raises per batch surfaces at the read."""
     import torch
     if scores is not None and not (on_device and tta_votes):
         raise ValueError("scores are kept by the device tail of a TTA run: on_device=True and tta_votes > 0")
+    if predictions and tta_votes:
+        raise ValueError("predictions=True is for validation batches (tta_votes == 0): a TTA run returns its predictions anyway")
+    if remap is not None and not (predictions or tta_votes):
+        raise ValueError("remap applies to label payloads: predictions=True or tta_votes > 0")
+    lut = None if remap is None else _remap_table(remap, num_class)
     if on_device:
-        return _evaluate_on_device(model, batches, num_class, tta_votes, dataset, save_dir, prefetch, scores)
+        return _evaluate_on_device(model, batches, num_class, tta_votes, dataset, save_dir, prefetch, scores, predictions, lut)
     unique_label = np.arange(num_class - 1)
     hist, preds = np.zeros((num_class - 1, num_class - 1), dtype=np.int64), []
     was_training = model.training
@@ -216,15 +266,24 @@ def evaluate(model, batches: Iterable[Dict], num_class: int, tta_votes: int = 0,
 
         for ret in results():
             if tta_votes:
-                payload = vote_payload(accumulate_votes(ret, tta_votes), dataset)
+                payload = _remapped(vote_payload(accumulate_votes(ret, tta_votes), dataset), lut)
                 preds.append(payload)
                 if save_dir is not None:
                     write_prediction(_prediction_path(save_dir, ret["name"][0], dataset), payload)
             else:
                 hist += scan_confusions(ret, unique_label)
+                if predictions:
+                    for name, classes in zip(ret["name"], ret["point_predict"]):
+                        payload = _remapped(_class_payload(classes, dataset), lut)
+                        preds.append(payload)
+                        if save_dir is not None:
+                            write_prediction(_prediction_path(save_dir, name, dataset), payload)
     finally:
         model.train(was_training)
     if tta_votes:
         return {"predictions": preds}
     iou = per_class_iu(hist)
-    return {"iou": iou, "miou": float(np.nanmean(iou) * 100), "hist": hist}
+    out = {"iou": iou, "miou": float(np.nanmean(iou) * 100), "hist": hist}
+    if predictions:
+        out["predictions"] = preds
+    return out

@@ -659,19 +659,20 @@ class PendingVotes:
     page-locked buffers behind one event.  `result()` waits for it, raises what the host path would have raised, and returns
     {"payload": [n, 1] uint32 / uint8, "scores": [n, C] / [n, 3] float32 or None, "name"} as arrays of their own."""
 
-    def __init__(self, event, meta_h, label_h, scores_h, width, names, nuscenes, keep):
+    def __init__(self, event, meta_h, label_h, scores_h, width, names, nuscenes, keep, remapped=False):
         self.event, self.meta_h, self.label_h, self.scores_h, self.width = event, meta_h, label_h, scores_h, width
-        self.names, self.nuscenes, self._keep, self._out = names, nuscenes, keep, None
+        self.names, self.nuscenes, self._keep, self._out, self.remapped = names, nuscenes, keep, None, remapped
 
     def result(self):
         if self._out is None:
             self.event.synchronize()
-            flags, n = (int(v) for v in self.meta_h.numpy())
+            flags, zero, n = (int(v) for v in self.meta_h.numpy())
             DeviceEvalTail.raise_flags(flags, len(self.names))
             import numpy as np
             label = np.array(self.label_h.numpy()[:n]).reshape(n, 1)
             if self.nuscenes:
-                if (label == 0).any():
+                # (a remapped payload no longer shows the class: the tail looked before the table and sent `zero` along)
+                if zero if self.remapped else (label == 0).any():
                     raise ValueError("nuScenes submission must not contain the ignored class 0 (R/train.py:523)")
             else:
                 label = label.view(np.uint32)
@@ -680,25 +681,67 @@ class PendingVotes:
         return self._out
 
 
+class PendingLabels:
+    """One validation batch of the device tail with predictions=True in flight: the arg-max class of every kept point of every scan
+    (through the remap table, narrowed to the payload type) and the per-scan counts m_s are on their way into page-locked buffers
+    behind one event.  `result()` waits for it, raises what the host path would have raised, and returns {"payload": one [m_s, 1]
+    uint32 / uint8 array of its own per scan, "name"}."""
+
+    def __init__(self, event, meta_h, label_h, names, nuscenes, keep, remapped):
+        self.event, self.meta_h, self.label_h, self.names, self.nuscenes = event, meta_h, label_h, names, nuscenes
+        self._keep, self._out, self.remapped = keep, None, remapped
+
+    def result(self):
+        if self._out is None:
+            self.event.synchronize()
+            import numpy as np
+            meta = self.meta_h.numpy()
+            flags, zero, counts = int(meta[0]), int(meta[1]), meta[2:].tolist()
+            DeviceEvalTail.raise_flags(flags, len(counts))
+            labels, payloads, at = self.label_h.numpy(), [], 0
+            for m in counts:
+                label = np.array(labels[at:at + m]).reshape(m, 1)
+                at += m
+                if self.nuscenes:
+                    if zero if self.remapped else (label == 0).any():
+                        raise ValueError("nuScenes submission must not contain the ignored class 0 (R/train.py:523)")
+                else:
+                    label = label.view(np.uint32)
+                payloads.append(label)
+            self._out, self._keep = {"payload": payloads, "name": self.names}, None
+        return self._out
+
+
 class DeviceEvalTail:
-    """Where `model(batch, device_tail=tail)` leaves an evaluation batch instead of un-voxelising it to the host
+    """Where `model(batch, device_tail=tail)` leaves an evaluation batch instead of un-voxelising it to the host - all five
+    segmentors (MinkUNet, MinkUNetMs, MinkUNetMsMm, MinkUNetMsMmNus, MinkUNetMsKd) take it
     (csrc/evaltail.hip: ts_scene_counts + one launch, three more where a point_mask has to be compacted):
 
     votes == 0 (validation)  every scene is a scan: additions to `hist`, the resident [num_class, num_class] int64 confusion matrix
-                             (R/train.py:35-52 fast_hist before its crop).  Nothing leaves the device until `read()`.
+                             (R/train.py:35-52 fast_hist before its crop).  Nothing leaves the device until `read()` - unless
+                             predictions=True: the launch also writes the arg-max of every kept point, and the call returns a
+                             PendingLabels (label payload of every scan and the per-scan counts, behind one event).
     votes == V  (TTA)        the V scenes are the votes of one scan: float32 sum in vote order, arg-max, label payload (uint32, or
                              uint8 for nuScenes) and optionally scores ("all": the sums, "top3": the three largest) - the call
                              returns a PendingVotes; only payload and scores cross to the host.
-    `flags` collects what the host path raises on (include/taseg_hip.h ts_eval_*); it is read with the matrix / the payload."""
+    remap: a {class: raw id} dictionary or a table as pcseg.eval.remap_lut builds - the payloads go through it on the device (one
+    gather) before they are narrowed to the payload type.
+    `flags` collects what the host path raises on (include/taseg_hip.h ts_eval_*); it is read with the matrix / every payload."""
 
-    def __init__(self, num_class, device, votes=0, dataset="semantickitti", scores=None):
+    def __init__(self, num_class, device, votes=0, dataset="semantickitti", scores=None, predictions=False, remap=None):
         if scores not in (None, "all", "top3"):
             raise ValueError(f"scores must be None, 'all' or 'top3' (got {scores!r})")
-        self.num_class, self.votes, self.scores = int(num_class), int(votes), scores
+        if predictions and votes:
+            raise ValueError("predictions=True is for validation batches (votes == 0): a TTA batch returns its payload anyway")
+        self.num_class, self.votes, self.scores, self.predictions = int(num_class), int(votes), scores, bool(predictions)
         self.nuscenes = dataset.startswith("nuscenes")
         self.hist = torch.zeros((self.num_class, self.num_class), dtype=torch.int64, device=device)
         self.n_scenes = 0
         self.flags = torch.zeros(1, dtype=torch.int32, device=device)
+        self.lut = None
+        if remap is not None:
+            from taseg_amd.pcseg.eval import _remap_table
+            self.lut = torch.from_numpy(_remap_table(remap, self.num_class)).to(device)
 
     @staticmethod
     def raise_flags(flags, n_scenes):
@@ -717,6 +760,40 @@ class DeviceEvalTail:
         if flags & 16:
             raise ValueError("votes must cover the same points (one scan per TTA batch)")
 
+    def _payload(self, classes, written):
+        """classes (int32 / uint8, the first `written` rows - a device scalar - are valid) as the label payload: through the remap
+        table, narrowed to the payload type.  Returns (payload, zero): zero [1] int64 counts the valid rows of class 0 where the
+        table hides them from the host's nuScenes check, else 0."""
+        zero = torch.zeros(1, dtype=torch.int64, device=classes.device)
+        if self.lut is not None:
+            if self.nuscenes:
+                valid = torch.arange(classes.shape[0], device=classes.device) < written
+                zero = ((classes == 0) & valid).sum().reshape(1)
+            # (rows behind the written ones hold whatever the allocation held: clamped, so that the gather stays inside the table)
+            classes = self.lut[classes.long().clamp_(0, self.num_class - 1)]
+        return (classes.to(torch.uint8) if self.nuscenes else classes.to(torch.int32)), zero
+
+    @staticmethod
+    def _to_host(device, tensors):
+        """asynchronous copies of `tensors` ({key: tensor}) into page-locked buffers on the copy stream, one event behind them"""
+        _pinned.next_generation()
+        side = _copy_stream(device) if _COPY_STREAM else None
+        if side is not None:
+            ready = torch.cuda.Event()
+            ready.record()
+            side.wait_event(ready)
+        out = {}
+        with (torch.cuda.stream(side) if side is not None else contextlib.nullcontext()):
+            for key, t in tensors.items():
+                if t is None:
+                    out[key] = None
+                    continue
+                h = out[key] = _pinned.take(key, t, t.numel())
+                h.copy_(t.reshape(-1), non_blocking=True)
+            event = torch.cuda.Event()
+            event.record()
+        return event, out
+
     def run(self, out, vox_batch, invs, all_labels, num_points, point_mask=None, num_points_ms=None, names=None):
         if out.shape[1] != self.num_class:
             raise ValueError(f"the model has {out.shape[1]} classes, the evaluation {self.num_class}")
@@ -724,33 +801,26 @@ class DeviceEvalTail:
         self.n_scenes = n_scenes = len(names) if names is not None else int(torch.as_tensor(num_points).numel())
         mask = None if point_mask is None else point_mask.to(out.device)
         if not self.votes:
-            B.eval_confusion(out, vox_batch, pts_batch, invs.F, all_labels.F.reshape(-1), all_labels.C[:, -1], num_points, self.hist,
-                             self.flags, point_mask=mask, num_points_ms=num_points_ms)
-            return self
+            got = B.eval_confusion(out, vox_batch, pts_batch, invs.F, all_labels.F.reshape(-1), all_labels.C[:, -1], num_points, self.hist,
+                                   self.flags, point_mask=mask, num_points_ms=num_points_ms, want_pred=self.predictions,
+                                   want_counts=self.predictions)
+            if not self.predictions:
+                return self
+            pred, m = got
+            label, zero = self._payload(pred, m.sum())
+            meta = torch.cat([self.flags.long(), zero, m])
+            event, h = self._to_host(out.device, {"pred_meta": meta, "pred_label": label})
+            return PendingLabels(event, h["pred_meta"], h["pred_label"], names, self.nuscenes, (meta, label), self.lut is not None)
         if n_scenes != self.votes:
             raise ValueError(f"TTA batch holds {n_scenes} votes, {self.votes} expected (one scan per batch, collate_batch_tta)")
         got = B.eval_votes(out, vox_batch, pts_batch, invs.F, num_points, self.flags, point_mask=mask, num_points_ms=num_points_ms,
                            label_bytes=1 if self.nuscenes else 4, want_sums=self.scores == "all", want_top3=self.scores == "top3")
         scores = got["sums"] if self.scores == "all" else got["top3"]
-        meta = torch.cat([self.flags.long(), got["n"]])
-        _pinned.next_generation()
-        side = _copy_stream(out.device) if _COPY_STREAM else None
-        if side is not None:
-            ready = torch.cuda.Event()
-            ready.record()
-            side.wait_event(ready)
-
-        def to_host(key, t):
-            h = _pinned.take(key, t, t.numel())
-            h.copy_(t.reshape(-1), non_blocking=True)
-            return h
-        with (torch.cuda.stream(side) if side is not None else contextlib.nullcontext()):
-            meta_h, label_h = to_host("vote_meta", meta), to_host("vote_label", got["label"])
-            scores_h = None if scores is None else to_host("vote_scores", scores)
-            event = torch.cuda.Event()
-            event.record()
-        return PendingVotes(event, meta_h, label_h, scores_h, 0 if scores is None else scores.shape[1], names, self.nuscenes,
-                            (meta, got, scores))
+        label, zero = self._payload(got["label"], got["n"]) if self.lut is not None else (got["label"], got["n"].new_zeros(1))
+        meta = torch.cat([self.flags.long(), zero, got["n"]])
+        event, h = self._to_host(out.device, {"vote_meta": meta, "vote_label": label, "vote_scores": scores})
+        return PendingVotes(event, h["vote_meta"], h["vote_label"], h["vote_scores"], 0 if scores is None else scores.shape[1], names,
+                            self.nuscenes, (meta, got, label, scores), self.lut is not None)
 
     def read(self):
         """validation: the matrix summed over the ranks (parallel.reduce_confusion) and the flags in ONE host read"""

@@ -87,7 +87,7 @@ class MinkUNetMsKd(MinkUNetBackbone):
         empty = torch.where(n_b == 0, torch.full((), float("nan"), device=dev), torch.zeros((), device=dev)).sum()
         return (per_row.sum() + empty) * (self.feat_kd_weight / batch_size)
 
-    def forward(self, batch_dict, return_logit=False, return_tta=False):
+    def forward(self, batch_dict, return_logit=False, return_tta=False, defer=False, device_tail=None):
         plan = batch_dict.get("_plan") or self.prepare(batch_dict)
         x_gt = batch_dict["lidar_ms_gt"]
         x_gt.F = x_gt.F[:, :self.in_feature_dim]
@@ -121,10 +121,14 @@ class MinkUNetMsKd(MinkUNetBackbone):
             disp = {"loss": LazyScalar(loss), "loss_seg": LazyScalar(loss_seg), "loss_feat_kd": LazyScalar(loss_kd)}
             return {"loss": loss}, disp, dict(disp)
 
+        if device_tail is not None:       # evaluation on the device (minkunet.DeviceEvalTail): the student's tail, as MinkUNetMs
+            return device_tail.run(out_ms, x_ms.C[:, -1], batch_dict["inverse_map_ms"], batch_dict["targets_mapped"],
+                                   batch_dict["num_points"], point_mask=batch_dict["point_mask"],
+                                   num_points_ms=batch_dict["num_points_ms"], names=batch_dict["name"])
         # the evaluation tail of MinkUNetMs for the whole batch at once (minkunet.unvoxelise_predictions)
         return unvoxelise_predictions(out_ms, x_ms.C[:, -1], batch_dict["inverse_map_ms"], batch_dict["targets_mapped"],
                                       batch_dict["num_points"], return_logit or return_tta, point_mask=batch_dict["point_mask"],
-                                      num_points_ms=batch_dict["num_points_ms"], names=batch_dict["name"])
+                                      num_points_ms=batch_dict["num_points_ms"], names=batch_dict["name"], defer=defer)
 
     def forward_ensemble(self, batch_dict):
         return self.forward(batch_dict, return_tta=True)

@@ -87,7 +87,7 @@ class MinkUNetMsMm(MinkUNetBackbone):
         batch_dict["_plan"] = plan
         return plan
 
-    def forward(self, batch_dict, return_logit=False, return_tta=False):
+    def forward(self, batch_dict, return_logit=False, return_tta=False, defer=False, device_tail=None):
         maps = []
         if "rgb" in self.input_feat:
             maps.append(batch_dict["image_ms"])
@@ -124,9 +124,9 @@ class MinkUNetMsMm(MinkUNetBackbone):
         z3_fov = voxel_to_point_fov(y4_fov, pts).F
         overlap = z1_fov.sum(-1) != 0
         fusion_features = torch.cat([z1, z2, z3, z1_fov, z2_fov, z3_fov], dim=1)
-        out_fusion = self.classifier_fusion(fusion_features[overlap])
 
         if self.training:
+            out_fusion = self.classifier_fusion(fusion_features[overlap])
             target = batch_dict["targets_ms"].F.long().cuda(non_blocking=True)
             img_logits = batch_dict["image_logits"].permute(0, 2, 3, 1).reshape(-1, self.num_class)
             img_targets = batch_dict["semantic_map_ms"].permute(0, 2, 3, 1).reshape(-1).to(target.dtype)
@@ -144,13 +144,21 @@ class MinkUNetMsMm(MinkUNetBackbone):
             disp = {"loss": LazyScalar(loss), **{k: LazyScalar(v) for k, v in parts.items()}}
             return {"loss": loss}, disp, dict(disp)
 
+        # the rows of `overlap` as an integer index, taken ONCE: the boolean gather and the boolean assignment of the replace ensemble
+        # each ran a `nonzero` with a host wait of its own.  Same rows in the same order - the bits of the boolean forms.
+        overlap_rows = overlap.nonzero().reshape(-1)
+        out_fusion = self.classifier_fusion(fusion_features.index_select(0, overlap_rows))
         if self.ensemble_type == "replace":
-            out_ms = out_ms.clone()
-            out_ms[overlap] = out_fusion
+            # (out of place: `out_ms` is the classifier's own output - a hook or a caller that holds it keeps its rows)
+            out_ms = out_ms.index_copy(0, overlap_rows, out_fusion.to(out_ms.dtype))
+        if device_tail is not None:       # evaluation on the device (minkunet.DeviceEvalTail), as MinkUNetMs
+            return device_tail.run(out_ms, x_ms.C[:, -1], batch_dict["inverse_map_ms"], batch_dict["targets_mapped"],
+                                   batch_dict["num_points"], point_mask=batch_dict["point_mask"],
+                                   num_points_ms=batch_dict["num_points_ms"], names=batch_dict["name"])
         # the evaluation tail of MinkUNetMs for the whole batch at once (minkunet.unvoxelise_predictions)
         return unvoxelise_predictions(out_ms, x_ms.C[:, -1], batch_dict["inverse_map_ms"], batch_dict["targets_mapped"],
                                       batch_dict["num_points"], return_logit or return_tta, point_mask=batch_dict["point_mask"],
-                                      num_points_ms=batch_dict["num_points_ms"], names=batch_dict["name"])
+                                      num_points_ms=batch_dict["num_points_ms"], names=batch_dict["name"], defer=defer)
 
     def forward_ensemble(self, batch_dict):
         return self.forward(batch_dict, return_tta=True)
