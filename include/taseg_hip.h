@@ -161,6 +161,29 @@ int ts_downsample(const int32_t *coords, int64_t n, int32_t sx, int32_t sy, int3
                   int32_t *out_coords, int32_t *out_count, void *ws, size_t ws_bytes,
                   ts_stream_t stream);
 
+/* spdownsample (nn/functional/downsample.py:32-51), the OVERLAPPING-WINDOW branch
+ * taken when some stride[k] is neither 1 nor kernel_size[k]: every row proposes
+ * row + offset for the offsets of get_kernel_offsets(kernel_size, tensor_stride)
+ * (nn/utils/kernel.py:19-20: arange(-k // 2 + 1, k // 2 + 1) * tensor_stride per
+ * axis); a candidate is kept if on every axis it is a multiple of
+ * stride * tensor_stride (:42) and not below the minimum of that axis over ALL
+ * n rows, whatever their batch index (:34, :43); no upper bound (the TODO of :41
+ * is reproduced).  Result: the unique kept rows in (b, x, y, z) order as
+ * (x, y, z, b), like ts_downsample.
+ * A row keeps at most cap = prod_a ceil(k_a / s_a) candidates and the result can
+ * have MORE rows than the input: out_coords has room for cap * n rows.
+ * Kernel sizes 1..5 and strides >= 1 per axis, cap * n < 2^31
+ * (TS_ERR_INVALID_ARGUMENT otherwise).  *out_count and the coordinate range are
+ * ts_downsample's (-1: a kept candidate outside the range; the far corner
+ * (2^17 - 1, 2^17 - 1, 2^17 - 1) of batch 1023, whose key pads the unused slots,
+ * counts as outside). */
+size_t ts_downsample_windows_workspace_bytes(int64_t n, int32_t kx, int32_t ky, int32_t kz,
+                                             int32_t sx, int32_t sy, int32_t sz);
+int ts_downsample_windows(const int32_t *coords, int64_t n, int32_t kx, int32_t ky, int32_t kz,
+                          int32_t sx, int32_t sy, int32_t sz, int32_t tx, int32_t ty, int32_t tz,
+                          int32_t *out_coords, int32_t *out_count, void *ws, size_t ws_bytes,
+                          ts_stream_t stream);
+
 /* torch.unique(int64) + position lookup as used by initial_voxelize
  * (pcseg/model/segmentor/voxel/minkunet/utils.py:16-18):
  * uniq = ascending unique values of keys (non-negative, < 2^62),

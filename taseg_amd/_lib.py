@@ -40,6 +40,8 @@ SIGNATURES = {
                                        _vp, _sz, _vp]),
     "ts_downsample_workspace_bytes": (_sz, [_i64]),
     "ts_downsample": (_i32, [_vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "ts_downsample_windows_workspace_bytes": (_sz, [_i64, _i32, _i32, _i32, _i32, _i32, _i32]),
+    "ts_downsample_windows": (_i32, [_vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
     "ts_unique_workspace_bytes": (_sz, [_i64]),
     "ts_unique_i64": (_i32, [_vp, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ts_build_kmap_workspace_bytes": (_sz, [_i64, _i64, _i32]),

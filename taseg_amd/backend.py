@@ -342,6 +342,30 @@ def downsample(coords, stride):
     return out[:m]
 
 
+def downsample_windows(coords, kernel_size, stride, tensor_stride):
+    """spdownsample's overlapping-window branch (downsample.py:32-51): the unique candidates row + kernel offset that are
+    multiples of stride * tensor_stride and not below the batch-wide minimum, (b,x,y,z)-sorted.  The result may have more
+    rows than `coords`: the buffers hold prod(ceil(kernel / stride)) candidates per row."""
+    L.require_device(coords)
+    coords = _i32(coords, "coords")
+    n = coords.shape[0]
+    k, s, t = ([int(v) for v in a] for a in (kernel_size, stride, tensor_stride))
+    if len(k) != 3 or len(s) != 3 or len(t) != 3 or not all(1 <= v <= 5 for v in k) or min(s) < 1 or min(t) < 1:
+        raise ValueError(f"downsample_windows: kernel sizes 1..5 and positive strides per axis, got kernel {k}, stride {s}, "
+                         f"tensor stride {t}")
+    cap = 1
+    for ka, sa in zip(k, s):
+        cap *= -(-ka // sa)
+    lib = L.load()
+    ws = L.workspace(lib.ts_downsample_windows_workspace_bytes(n, *k, *s), coords.device)
+    out = torch.empty((max(cap * n, 1), 4), dtype=torch.int32, device=coords.device)
+    cnt = torch.empty(1, dtype=torch.int32, device=coords.device)
+    L.check(lib.ts_downsample_windows(L.ptr(coords), n, *k, *s, *t, L.ptr(out), L.ptr(cnt), L.ptr(ws), ws.numel(),
+                                      L.stream()), "ts_downsample_windows")
+    m = _count_to_host(cnt, "downsample_windows")
+    return out[:m]
+
+
 def unique_i64(keys, return_inverse=True):
     """torch.unique(int64) (+ inverse positions) as initial_voxelize uses it (minkunet/utils.py:16-18)."""
     L.require_device(keys)

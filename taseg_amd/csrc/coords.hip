@@ -148,6 +148,180 @@ extern "C" int ts_downsample(const int32_t *coords, int64_t n, int32_t sx, int32
   return TS_OK;
 }
 
+// ------------------------------------------------------------------ downsample, overlapping windows
+// downsample.py:32-51, the branch taken when some stride is neither 1 nor the kernel size: every input row proposes the K =
+// kx * ky * kz coordinates row + offset (get_kernel_offsets(kernel_size, tensor_stride)); kept are those that are, on every axis,
+// a multiple of S = stride * tensor_stride and not below the minimum of that axis over ALL rows of the batch (no upper bound: the
+// reference's TODO about coords_max is reproduced); the result is the unique kept rows in (b, x, y, z) order.
+// Both tests are per axis, so the kept candidates of a row are the product of three per-axis lists, and k consecutive offsets hold
+// at most ceil(k / s) multiples of s: a row keeps at most cap = capx * capy * capz candidates (8 for kernel 3 / stride 2).  The
+// result can have MORE rows than the input.
+//
+// Unused slots are PADDED, not compacted: row i owns the slots i * cap .. i * cap + cap - 1 of the key array and every slot its row
+// does not fill gets DW_PAD, the largest key, which sorts last and is dropped after `unique` as ONE row.  Why not compaction
+// before the sort (count, scan, scatter, as compact.h does): it would sort ~0.4 x the keys of kernel 3 / stride 2 (a row keeps 3.4
+// of its 8 slots on average) but needs the per-row pass twice and a scan between them - three more launches in a chain of ~10
+// short ones - while the padded form keeps every slot's position fixed (slot = row * cap + j: coalesced stores, no offsets to
+// read).  The whole call takes 0.25 ms on 88k voxels (profiles/downsample_windows.txt); the compacted form was not built and timed.
+// DW_PAD is the key of (2^17 - 1, 2^17 - 1, 2^17 - 1, batch 1023): that single coordinate is reported as outside the range when
+// it is a kept candidate.
+#define DW_PAD 0xFFFFFFFFFFFFFFFFull
+#define DW_MAX_KERNEL 5
+
+struct DwGeom {
+  int lo[3];        // first offset index per axis: -((k - 1) / 2) == -k // 2 + 1 (nn/utils/kernel.py:20)
+  int k[3];         // kernel size per axis
+  int t[3];         // tensor stride
+  int S[3];         // stride * tensor stride
+  int cap[3];       // ceil(k / stride)
+};
+
+// pass 1: the three minima over all rows (integer minima: the same whatever the order of the atomics); mins = INT_MAX before
+__global__ __launch_bounds__(256) void dw_min_kernel(const int4 *__restrict__ coords, int64_t n, int *__restrict__ mins) {
+  __shared__ int blk[3];
+  if (threadIdx.x < 3) blk[threadIdx.x] = 0x7FFFFFFF;
+  __syncthreads();
+  int mx = 0x7FFFFFFF, my = 0x7FFFFFFF, mz = 0x7FFFFFFF;
+  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t step = (int64_t)gridDim.x * blockDim.x;
+  for (; i < n; i += step) {
+    const int4 c = coords[i];
+    mx = min(mx, c.x);
+    my = min(my, c.y);
+    mz = min(mz, c.z);
+  }
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) {
+    mx = min(mx, __shfl_xor(mx, d));
+    my = min(my, __shfl_xor(my, d));
+    mz = min(mz, __shfl_xor(mz, d));
+  }
+  if ((threadIdx.x & 63) == 0) {
+    atomicMin(&blk[0], mx);
+    atomicMin(&blk[1], my);
+    atomicMin(&blk[2], mz);
+  }
+  __syncthreads();
+  if (threadIdx.x < 3) atomicMin(&mins[threadIdx.x], blk[threadIdx.x]);
+}
+
+// the j-th kept candidate of one axis (j < cap <= DW_MAX_KERNEL), or false when the axis keeps fewer: walks the <= 5 offsets in
+// registers.  64-bit arithmetic: c + o * t of an arbitrary int32 coordinate must not wrap before the range test.
+__device__ __forceinline__ bool dw_axis(int c, int lo, int k, int t, int S, int cmin, int j, long long *v_out) {
+  int seen = 0;
+  bool found = false;
+#pragma unroll
+  for (int o = 0; o < DW_MAX_KERNEL; ++o) {
+    const long long v = (long long)c + (long long)(lo + o) * t;
+    const bool keep = o < k && v % S == 0 && v >= cmin;
+    if (keep && seen == j) {
+      *v_out = v;
+      found = true;
+    }
+    seen += keep ? 1 : 0;
+  }
+  return found;
+}
+
+// pass 2: one thread per SLOT (row i, candidate j of its cap): consecutive lanes write consecutive keys.  Every slot below
+// total = n * cap is written, with a key or with DW_PAD; a kept candidate outside ts_pack's range raises *err and is not written.
+__global__ __launch_bounds__(256) void dw_keys_kernel(const int4 *__restrict__ coords, int64_t total, DwGeom g,
+                                                      const int *__restrict__ mins, uint64_t *__restrict__ keys,
+                                                      int *__restrict__ err) {
+  const int cap_yz = g.cap[1] * g.cap[2], cap = g.cap[0] * cap_yz;
+  const int m0 = mins[0], m1 = mins[1], m2 = mins[2];
+  int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t step = (int64_t)gridDim.x * blockDim.x;
+  for (; s < total; s += step) {
+    const int64_t i = s / cap;
+    const int j = (int)(s - i * cap);
+    const int jx = j / cap_yz, jy = (j - jx * cap_yz) / g.cap[2], jz = j % g.cap[2];
+    const int4 c = coords[i];
+    long long x = 0, y = 0, z = 0;
+    uint64_t key = DW_PAD;
+    if (dw_axis(c.x, g.lo[0], g.k[0], g.t[0], g.S[0], m0, jx, &x) && dw_axis(c.y, g.lo[1], g.k[1], g.t[1], g.S[1], m1, jy, &y) &&
+        dw_axis(c.z, g.lo[2], g.k[2], g.t[2], g.S[2], m2, jz, &z)) {
+      const long long lim = TS_CBIAS;
+      const bool ok = x >= -lim && x < lim && y >= -lim && y < lim && z >= -lim && z < lim && (unsigned)c.w < 1024u;
+      const uint64_t packed = ok ? ts_pack((int)x, (int)y, (int)z, c.w) : DW_PAD;
+      if (ok && packed != DW_PAD) key = packed; else *err = 1;
+    }
+    keys[s] = key;
+  }
+}
+
+// the pad, if any slot carried it, is the LAST unique key: one row less
+__global__ void dw_drop_pad_kernel(const uint64_t *__restrict__ uniq, unsigned *__restrict__ count) {
+  const unsigned m = *count;
+  if (m > 0 && uniq[m - 1] == DW_PAD) *count = m - 1;
+}
+
+static int dw_geometry(DwGeom *g, int64_t n, const int32_t k[3], const int32_t s[3], const int32_t t[3], int64_t *cap) {
+  *cap = 1;
+  for (int a = 0; a < 3; ++a) {
+    TS_REQUIRE(k[a] >= 1 && k[a] <= DW_MAX_KERNEL, TS_ERR_INVALID_ARGUMENT,
+               "ts_downsample_windows: kernel size %d outside 1..%d", (int)k[a], DW_MAX_KERNEL);
+    TS_REQUIRE(s[a] >= 1 && t[a] >= 1 && (int64_t)s[a] * t[a] < (1LL << 30), TS_ERR_INVALID_ARGUMENT,
+               "ts_downsample_windows: stride %d / tensor stride %d must be positive (product < 2^30)", (int)s[a], (int)t[a]);
+    g->lo[a] = -((k[a] - 1) / 2);
+    g->k[a] = k[a];
+    g->t[a] = t[a];
+    g->S[a] = s[a] * t[a];
+    g->cap[a] = (k[a] + s[a] - 1) / s[a];
+    *cap *= g->cap[a];
+  }
+  TS_REQUIRE(n >= 0 && n * *cap < (1LL << 31), TS_ERR_INVALID_ARGUMENT, "ts_downsample_windows: bad n");
+  return TS_OK;
+}
+
+extern "C" size_t ts_downsample_windows_workspace_bytes(int64_t n, int32_t kx, int32_t ky, int32_t kz, int32_t sx, int32_t sy,
+                                                        int32_t sz) {
+  const int32_t k[3] = {kx, ky, kz}, s[3] = {sx, sy, sz};
+  int64_t cap = 1;
+  for (int a = 0; a < 3; ++a) cap *= (k[a] >= 1 && s[a] >= 1) ? (k[a] + s[a] - 1) / s[a] : 1;
+  return sort_unique_ws_bytes((n < 0 ? 0 : n) * cap);
+}
+
+extern "C" int ts_downsample_windows(const int32_t *coords, int64_t n, int32_t kx, int32_t ky, int32_t kz, int32_t sx, int32_t sy,
+                                     int32_t sz, int32_t tx, int32_t ty, int32_t tz, int32_t *out_coords, int32_t *out_count,
+                                     void *ws, size_t ws_bytes, ts_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  const int32_t k[3] = {kx, ky, kz}, s[3] = {sx, sy, sz}, t[3] = {tx, ty, tz};
+  DwGeom g;
+  int64_t cap = 1;
+  int rc = dw_geometry(&g, n, k, s, t, &cap);
+  if (rc != TS_OK) return rc;
+  TS_REQUIRE(out_count, TS_ERR_INVALID_ARGUMENT, "ts_downsample_windows: null out_count");
+  if (n == 0) {
+    TS_CHECK_HIP(hipMemsetAsync(out_count, 0, 4, stream), "ts_downsample_windows memset");
+    return TS_OK;
+  }
+  TS_REQUIRE(coords && out_coords, TS_ERR_INVALID_ARGUMENT, "ts_downsample_windows: null pointer");
+  TS_REQUIRE(((uintptr_t)coords & 15) == 0 && ((uintptr_t)out_coords & 15) == 0, TS_ERR_INVALID_ARGUMENT,
+             "ts_downsample_windows: coords must be 16-byte aligned");
+  const int64_t total = n * cap;
+  SortUniqueWs w;
+  rc = carve_sort_unique(&w, total, ws, ws_bytes);
+  if (rc != TS_OK) return rc;
+  // the 256-byte counter block: count (+0), err (+64), the three minima (+128)
+  int *mins = (int *)((char *)w.count + 128);
+  const TsFillSeg init[2] = {{w.count, 128, 0u}, {mins, 16, 0x7FFFFFFFu}};
+  rc = ts_fill_segments(init, 2, stream);
+  if (rc != TS_OK) return rc;
+  dw_min_kernel<<<(int)std::min<int64_t>(ts_cdiv(n, 256), 1024), 256, 0, stream>>>((const int4 *)coords, n, mins);
+  TS_CHECK_LAUNCH("ts_downsample_windows/min");
+  const int grid = (int)std::min<int64_t>(ts_cdiv(total, 256), 2048);
+  dw_keys_kernel<<<grid, 256, 0, stream>>>((const int4 *)coords, total, g, mins, w.a, w.err);
+  TS_CHECK_LAUNCH("ts_downsample_windows/keys");
+  rc = sort_unique(&w, total, 64, stream);
+  if (rc != TS_OK) return rc;
+  dw_drop_pad_kernel<<<1, 1, 0, stream>>>(w.u, w.count);
+  TS_CHECK_LAUNCH("ts_downsample_windows/drop");
+  ds_unpack_kernel<<<grid, 256, 0, stream>>>(w.u, w.count, w.err, (int4 *)out_coords, out_count);
+  TS_CHECK_LAUNCH("ts_downsample_windows/unpack");
+  return TS_OK;
+}
+
 // ------------------------------------------------------------------ unique int64 (+ inverse)
 __global__ __launch_bounds__(256) void uq_copy_kernel(const int64_t *__restrict__ keys, int64_t n,
                                                       uint64_t *__restrict__ out, int *__restrict__ err) {

@@ -9,7 +9,14 @@ what differs is how the work is scheduled on the device:
 * the convolution itself runs on the [K, N_out] neighbour table (output-stationary,
   every output row written once) instead of 3 x K gather / GEMM / scatter launches;
 * `nbmaps` / `nbsizes` with the reference's exact contents and order are still produced
-  (and are what the weight-gradient kernel walks), so rulebooks can be compared bit for bit.
+  (and are what the weight-gradient kernel walks), so rulebooks can be compared bit for bit;
+* the output coordinates of a strided convolution come from one backend call with one host read (the row count):
+  `ts_downsample` where the stride is 1 or the kernel size on every axis, `ts_downsample_windows` for every other stride
+  (kernel 3 / stride 2, anisotropic strides) - no candidate tensor of K x N rows, no `torch.unique(dim=0)`.
+
+Convolutions run over any of these maps - cubic or anisotropic kernels, isotropic or anisotropic strides, forward and
+transposed - on the pair GEMM / gather-sum / weight-gradient kernels, which take the kernel volume at run time; the class
+and direct plans are built for 3x3x3 / stride 1 and 2x2x2 / stride 2 maps only.
 """
 import os
 from typing import List, Optional, Tuple, Union
@@ -197,14 +204,16 @@ def calc_ti_weights(coords: torch.Tensor, idx_query: torch.Tensor, scale: float 
 
 # ------------------------------------------------------------------------------ downsample
 def spdownsample(coords: torch.Tensor, stride=2, kernel_size=2, tensor_stride=1) -> torch.Tensor:
-    """downsample.py:11-52: output coordinates of a strided convolution."""
+    """downsample.py:11-52: output coordinates of a strided convolution.  A stride that is 1 or the kernel size on every axis
+    (the MinkUNet family: kernel 2 / stride 2, kernel 3 / stride 1) rounds the coordinates down to the output grid; any other
+    stride (kernel 3 / stride 2, anisotropic strides) takes the overlapping-window branch (:32-48): every grid coordinate a kernel
+    offset away from an input row, not below the batch-wide minimum - the result may have more rows than `coords`.  Kernel sizes
+    1..5 per axis there (ValueError otherwise)."""
     stride = make_ntuple(stride, ndim=3)
     kernel_size = make_ntuple(kernel_size, ndim=3)
     tensor_stride = make_ntuple(tensor_stride, ndim=3)
     if not all(stride[k] in (1, kernel_size[k]) for k in range(3)):
-        # the overlapping-window branch (downsample.py:32-48) is never reached by the
-        # MinkUNet family (kernel 2 / stride 2 and kernel 3 / stride 1 only)
-        raise NotImplementedError("spdownsample: stride must be 1 or equal to kernel_size on every axis")
+        return B.downsample_windows(coords, kernel_size, stride, tensor_stride)
     step = [stride[k] * tensor_stride[k] for k in range(3)]
     return B.downsample(coords, step)
 
