@@ -466,6 +466,29 @@ int ts_leaky_bn_train_backward(const void *grad_out, const void *x, const float 
                                int64_t n, int32_t c, float slope, int32_t half, void *grad_x, float *grad_weight, float *grad_bias,
                                void *ws, size_t ws_bytes, ts_stream_t stream);
 
+/* Max-voxelisation of point rows (Cylinder_TS: tools/utils/common/seg_utils.py:385-401, `torch_scatter.scatter_max(z.F, idx_query,
+ * dim=0)[0]`).  feat [n, c], idx [n] int32 = voxel of every row (negative or >= m: the row takes no part), m voxels.
+ *   forward   out [m, c] = per channel the maximum over the voxel's rows, arg [m, c] int32 = the SMALLEST row index that attains it;
+ *             a voxel without rows gets 0 and -1.  The rows are grouped by voxel with the stable sort behind ts_devox_csr and walked
+ *             in ascending order from the voxel's first row: no atomics, no zero-initialised maximum, every element of out / arg
+ *             written once, run-to-run identical.  ws >= ts_voxelize_max_workspace_bytes(n, m)
+ *   backward  grad_feat [n, c] = grad_out[idx[i], ch] where arg[idx[i], ch] == i, else 0 - a gather, every element written once
+ * half != 0: IEEE half rows (c % 8 == 0), else float (c % 4 == 0); c <= 1024; 16-byte aligned rows. */
+size_t ts_voxelize_max_workspace_bytes(int64_t n, int64_t m);
+int ts_voxelize_max_forward(const void *feat, const int32_t *idx, int64_t n, int32_t c, int64_t m, int32_t half, void *out,
+                            int32_t *arg, void *ws, size_t ws_bytes, ts_stream_t stream);
+int ts_voxelize_max_backward(const void *grad_out, const int32_t *idx, const int32_t *arg, int64_t n, int32_t c, int64_t m,
+                             int32_t half, void *grad_feat, ts_stream_t stream);
+
+/* The gate of Cylinder_TS's ReconBlock (cylinder_ts.py:368-384) on rows [n, c]: out = x * (sigmoid(u) + sigmoid(v) + sigmoid(w)),
+ * one pass; the backward forms grad_x, grad_u, grad_v, grad_w from grad_out and the four inputs in one pass.  float arithmetic;
+ * half != 0: IEEE half storage (c % 8 == 0), else float (c % 4 == 0); 16-byte aligned pointers. */
+int ts_sigmoid3_gate_forward(const void *x, const void *u, const void *v, const void *w, int64_t n, int32_t c, int32_t half,
+                             void *out, ts_stream_t stream);
+int ts_sigmoid3_gate_backward(const void *grad_out, const void *x, const void *u, const void *v, const void *w, int64_t n,
+                              int32_t c, int32_t half, void *grad_x, void *grad_u, void *grad_v, void *grad_w,
+                              ts_stream_t stream);
+
 /* Dense 3 x 3 convolution, 32 -> 32 channels, stride 1, padding = dilation (1 or 2), on channels-last IEEE-half rows - the
  * full-resolution layers of UNet2D (unet2d.py:10-31,41-60: `nn.Conv2d(32, 32, (3, 3), padding=1)` and `dilation=2, padding=2`).
  *   ts_conv3x3c32_pack   the nn.Conv2d weight [co][ci][ky][kx] (half, any strides) -> the MFMA operand form the kernel keeps in

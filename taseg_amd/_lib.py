@@ -91,6 +91,11 @@ SIGNATURES = {
     "ts_leaky_bn_train_forward": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _c.c_float, _c.c_float, _c.c_float, _i32, _vp, _vp, _vp,
                                          _vp, _vp, _sz, _vp]),
     "ts_leaky_bn_train_backward": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _c.c_float, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "ts_voxelize_max_workspace_bytes": (_sz, [_i64, _i64]),
+    "ts_voxelize_max_forward": (_i32, [_vp, _vp, _i64, _i32, _i64, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "ts_voxelize_max_backward": (_i32, [_vp, _vp, _vp, _i64, _i32, _i64, _i32, _vp, _vp]),
+    "ts_sigmoid3_gate_forward": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp]),
+    "ts_sigmoid3_gate_backward": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "ts_conv3x3c32_packed_bytes": (_sz, []),
     "ts_conv3x3c32_pack": (_i32, [_vp, _i64, _i64, _i64, _i64, _i32, _vp, _vp]),
     "ts_conv3x3c32_rows": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),

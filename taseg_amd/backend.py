@@ -22,6 +22,7 @@ __all__ = [
     "downsample", "unique_i64", "build_kmap", "trilinear_map", "conv_nbr", "conv_wgrad", "conv_class_plan", "conv_class_gemm", "conv_class_gemm_f16", "conv_class_conv", "conv_class_conv_f16", "class_finish_pays",
     "fuse_scan", "fuse_scans", "fuse_sweeps", "project_fov", "voxel_coords", "sparse_quantize", "set_conv_impl", "image_gather_forward", "image_gather_backward", "image_gather_rows_forward", "image_gather_rows_backward", "avgpool3s2_rows_forward", "avgpool3s2_rows_backward", "conv3x3c32_pack", "conv3x3c32_rows", "conv3x3c32_wgrad", "conv3x3_rows_takes", "conv3x3_rows_pack", "conv3x3_rows", "conv3x3_wgrad", "conv1x1c32_pack", "conv1x1c32_rows", "conv1x1c32_wgrad", "shuffle_cat_rows_takes", "shuffle_cat_rows_forward", "shuffle_cat_rows_backward",
     "eval_confusion", "eval_votes",
+    "voxelize_max_forward", "voxelize_max_backward", "sigmoid3_gate_forward", "sigmoid3_gate_backward",
 ]
 
 
@@ -1967,3 +1968,74 @@ def eval_votes(logits, vox_batch, pts_batch, inv, num_points, flags, point_mask=
     L.check(L.load().ts_eval_votes(*head, *tail, L.ptr(label), label_bytes, L.ptr(sums), L.ptr(top3), cap, L.ptr(n), L.ptr(flags),
                                    L.stream()), "ts_eval_votes")
     return fresh
+
+
+# --------------------------------------------------------------------------- Cylinder_TS (csrc/cylinder.hip)
+def _rows_f32_f16(t, name):
+    """contiguous float32 / float16 rows [n, c] -> (tensor, half flag)"""
+    if t.dtype not in (torch.float32, torch.float16) or t.dim() != 2:
+        raise TypeError(f"{name} must be a float32 or float16 [n, c] matrix (got {t.dtype}, {tuple(t.shape)})")
+    return t.contiguous(), 1 if t.dtype == torch.float16 else 0
+
+
+def voxelize_max_forward(feat, idx, m):
+    """(out [m, c], arg [m, c] int32): per voxel and channel the maximum over the rows i of feat [n, c] with idx[i] == voxel and the
+    smallest such row that attains it (0 / -1 for a voxel without rows; negative idx: the row takes no part).  float32 with
+    c % 4 == 0 or float16 with c % 8 == 0 - anything else raises BackendError."""
+    L.require_device(feat, idx)
+    feat, half = _rows_f32_f16(feat, "feat")
+    idx = _i32(idx, "idx")
+    n, c = feat.shape
+    if idx.shape != (n,):
+        raise ValueError("voxelize_max_forward: idx must hold one voxel per row")
+    m = int(m)
+    lib = L.load()
+    out = torch.empty((m, c), dtype=feat.dtype, device=feat.device)
+    arg = torch.empty((m, c), dtype=torch.int32, device=feat.device)
+    ws = L.workspace(lib.ts_voxelize_max_workspace_bytes(n, m), feat.device)
+    L.check(lib.ts_voxelize_max_forward(L.ptr(feat), L.ptr(idx), n, c, m, half, L.ptr(out), L.ptr(arg), L.ptr(ws), ws.numel(),
+                                        L.stream()), "ts_voxelize_max_forward")
+    return out, arg
+
+
+def voxelize_max_backward(grad_out, idx, arg, n):
+    """grad_feat [n, c]: grad_out[idx[i], ch] where row i is the recorded arg-max of its voxel in channel ch, else 0 (a gather)."""
+    L.require_device(grad_out, idx, arg)
+    grad_out, half = _rows_f32_f16(grad_out, "grad_out")
+    idx, arg = _i32(idx, "idx"), _i32(arg, "arg")
+    m, c = grad_out.shape
+    n = int(n)
+    if idx.shape != (n,) or arg.shape != (m, c):
+        raise ValueError("voxelize_max_backward: idx [n] and arg [m, c] must match grad_out [m, c]")
+    out = torch.empty((n, c), dtype=grad_out.dtype, device=grad_out.device)
+    L.check(L.load().ts_voxelize_max_backward(L.ptr(grad_out), L.ptr(idx), L.ptr(arg), n, c, m, half, L.ptr(out), L.stream()),
+            "ts_voxelize_max_backward")
+    return out
+
+
+def sigmoid3_gate_forward(x, u, v, w):
+    """x * (sigmoid(u) + sigmoid(v) + sigmoid(w)) on rows [n, c] of one dtype (float32, c % 4 == 0; float16, c % 8 == 0)."""
+    L.require_device(x, u, v, w)
+    x, half = _rows_f32_f16(x, "x")
+    u, v, w = (_same_rows(t, x, "sigmoid3_gate_forward") for t in (u, v, w))
+    out = torch.empty_like(x)
+    L.check(L.load().ts_sigmoid3_gate_forward(L.ptr(x), L.ptr(u), L.ptr(v), L.ptr(w), x.shape[0], x.shape[1], half, L.ptr(out),
+                                              L.stream()), "ts_sigmoid3_gate_forward")
+    return out
+
+
+def sigmoid3_gate_backward(grad_out, x, u, v, w):
+    """(grad_x, grad_u, grad_v, grad_w) of sigmoid3_gate_forward in one pass over grad_out and the four inputs."""
+    L.require_device(grad_out, x, u, v, w)
+    x, half = _rows_f32_f16(x, "x")
+    grad_out, u, v, w = (_same_rows(t, x, "sigmoid3_gate_backward") for t in (grad_out, u, v, w))
+    grads = [torch.empty_like(x) for _ in range(4)]
+    L.check(L.load().ts_sigmoid3_gate_backward(L.ptr(grad_out), L.ptr(x), L.ptr(u), L.ptr(v), L.ptr(w), x.shape[0], x.shape[1], half,
+                                               *[L.ptr(g) for g in grads], L.stream()), "ts_sigmoid3_gate_backward")
+    return tuple(grads)
+
+
+def _same_rows(t, like, who):
+    if t.dtype != like.dtype or t.shape != like.shape:
+        raise ValueError(f"{who}: every operand must have the dtype and shape of x ({like.dtype}, {tuple(like.shape)})")
+    return t.contiguous()

@@ -155,6 +155,14 @@ int ts_fill_segments(const TsFillSeg *segs, int n, hipStream_t stream);
 int ts_table_init(TsTable *t, int64_t n, void *ws, size_t ws_bytes, hipStream_t stream, size_t *used,
                   const TsFillSeg *extra = nullptr, int n_extra = 0);
 
+// ---- stable grouping of slots by voxel (coords.hip) -----------------------------------------------------------------------
+// offsets [n_vox + 1] / entries [n_slots]: the slots e with idx[e] == v (and weight[e] != 0 where weight is given), ascending, are
+// entries[offsets[v] .. offsets[v + 1]) - a stable radix sort on the voxel id; ids outside [0, n_vox) belong to no voxel.
+// ws >= ts_group_slots_workspace_bytes(n_slots).  Behind ts_devox_csr and ts_voxelize_max_forward.
+size_t ts_group_slots_workspace_bytes(int64_t n_slots);
+int ts_group_slots(const int32_t *idx, const float *weight, int64_t n_slots, int64_t n_vox, int32_t *offsets, int32_t *entries,
+                   void *ws, size_t ws_bytes, hipStream_t stream, const char *who);
+
 // ---- deterministic weight gradient ------------------------------------------------------------------------------
 // A weight-gradient workgroup = (chunk c of consecutive rulebook pairs, TM x TN tile).  Instead of adding its partial
 // tile of offset k into dW_k with float atomics (order = whatever workgroup finishes first), it stores the tile into

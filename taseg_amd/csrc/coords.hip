@@ -822,7 +822,7 @@ __global__ __launch_bounds__(256) void devox_csr_key_kernel(const int *__restric
   const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= n8) return;
   const int v = idx[e];
-  keys[e] = (v >= 0 && v < n_vox && w[e] != 0.f) ? (unsigned)v : 0xFFFFFFFFu;
+  keys[e] = (v >= 0 && v < n_vox && (!w || w[e] != 0.f)) ? (unsigned)v : 0xFFFFFFFFu;
   vals[e] = (int)e;
 }
 
@@ -839,41 +839,51 @@ __global__ __launch_bounds__(256) void devox_csr_offsets_kernel(const unsigned *
   off[v] = (int)lo;
 }
 
-extern "C" size_t ts_devox_csr_workspace_bytes(int64_t n) {
-  const size_t n8 = (size_t)(n < 0 ? 0 : n) * 8;
-  return 3 * ts_align_up(n8 * 4, 256) + ts_align_up(n8 * 16 + (4u << 20), 256);
+// The stable grouping itself, shared inside the library (common.h): `n_slots` entries idx[e] -> group id, weight may be NULL
+// (every slot with a valid id counts).  ts_devox_csr groups the 8 n (point, corner) slots of a trilinear map with it,
+// ts_voxelize_max_forward (csrc/cylinder.hip) the n rows of a point -> voxel map.
+size_t ts_group_slots_workspace_bytes(int64_t n_slots) {
+  const size_t ns = (size_t)(n_slots < 0 ? 0 : n_slots);
+  return 3 * ts_align_up(ns * 4, 256) + ts_align_up(ns * 2 * 8 + (4u << 20), 256);
 }
 
-// idx / weight [n, 8] (a ts_trilinear_map result); offsets [n_vox + 1] and entries [8 n] int32 out: the slots of voxel v are
-// entries[offsets[v] .. offsets[v + 1]), slot = point * 8 + corner
-extern "C" int ts_devox_csr(const int32_t *idx, const float *weight, int64_t n, int64_t n_vox, int32_t *offsets,
-                            int32_t *entries, void *ws, size_t ws_bytes, ts_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  TS_REQUIRE(n >= 0 && n_vox >= 0 && n < (1LL << 27), TS_ERR_INVALID_ARGUMENT, "ts_devox_csr: bad sizes");
-  TS_REQUIRE(n_vox < (1LL << 31) - 1, TS_ERR_UNSUPPORTED, "ts_devox_csr: too many voxels");
-  TS_REQUIRE(offsets, TS_ERR_INVALID_ARGUMENT, "ts_devox_csr: null pointer");
-  const int64_t n8 = n * 8;
-  if (n == 0) {
-    TS_CHECK_HIP(hipMemsetAsync(offsets, 0, (size_t)(n_vox + 1) * 4, stream), "ts_devox_csr memset");
+int ts_group_slots(const int32_t *idx, const float *weight, int64_t n_slots, int64_t n_vox, int32_t *offsets, int32_t *entries,
+                   void *ws, size_t ws_bytes, hipStream_t stream, const char *who) {
+  TS_REQUIRE(n_slots >= 0 && n_vox >= 0 && n_slots < (1LL << 30), TS_ERR_INVALID_ARGUMENT, "%s: bad sizes", who);
+  TS_REQUIRE(n_vox < (1LL << 31) - 1, TS_ERR_UNSUPPORTED, "%s: too many voxels", who);
+  TS_REQUIRE(offsets, TS_ERR_INVALID_ARGUMENT, "%s: null pointer", who);
+  if (n_slots == 0) {
+    TS_CHECK_HIP(hipMemsetAsync(offsets, 0, (size_t)(n_vox + 1) * 4, stream), "ts_group_slots memset");
     return TS_OK;
   }
-  TS_REQUIRE(idx && weight && entries && ws, TS_ERR_INVALID_ARGUMENT, "ts_devox_csr: null pointer");
-  TS_REQUIRE(ws_bytes >= ts_devox_csr_workspace_bytes(n), TS_ERR_INVALID_ARGUMENT, "ts_devox_csr: workspace too small");
+  TS_REQUIRE(idx && entries && ws, TS_ERR_INVALID_ARGUMENT, "%s: null pointer", who);
+  TS_REQUIRE(ws_bytes >= ts_group_slots_workspace_bytes(n_slots), TS_ERR_INVALID_ARGUMENT, "%s: workspace too small", who);
   char *p = (char *)ws;
-  const size_t kb = ts_align_up((size_t)n8 * 4, 256);
+  const size_t kb = ts_align_up((size_t)n_slots * 4, 256);
   unsigned *keys = (unsigned *)p;
   unsigned *keys_out = (unsigned *)(p + kb);
   int *vals = (int *)(p + 2 * kb);
   void *tmp = p + 3 * kb;
   size_t tmp_bytes = ws_bytes - 3 * kb, need = 0;
-  devox_csr_key_kernel<<<(unsigned)ts_cdiv(n8, 256), 256, 0, stream>>>(idx, weight, n8, n_vox, keys, vals);
-  TS_CHECK_LAUNCH("ts_devox_csr/keys");
-  TS_CHECK_HIP(rocprim::radix_sort_pairs(nullptr, need, keys, keys_out, vals, entries, (size_t)n8, 0u, 32u, stream),
+  devox_csr_key_kernel<<<(unsigned)ts_cdiv(n_slots, 256), 256, 0, stream>>>(idx, weight, n_slots, n_vox, keys, vals);
+  TS_CHECK_LAUNCH("ts_group_slots/keys");
+  TS_CHECK_HIP(rocprim::radix_sort_pairs(nullptr, need, keys, keys_out, vals, entries, (size_t)n_slots, 0u, 32u, stream),
                "radix_sort_pairs size query");
-  TS_REQUIRE(need <= tmp_bytes, TS_ERR_INVALID_ARGUMENT, "ts_devox_csr: workspace too small for the sort");
-  TS_CHECK_HIP(rocprim::radix_sort_pairs(tmp, need, keys, keys_out, vals, entries, (size_t)n8, 0u, 32u, stream),
+  TS_REQUIRE(need <= tmp_bytes, TS_ERR_INVALID_ARGUMENT, "%s: workspace too small for the sort", who);
+  TS_CHECK_HIP(rocprim::radix_sort_pairs(tmp, need, keys, keys_out, vals, entries, (size_t)n_slots, 0u, 32u, stream),
                "radix_sort_pairs");
-  devox_csr_offsets_kernel<<<(unsigned)ts_cdiv(n_vox + 1, 256), 256, 0, stream>>>(keys_out, n8, n_vox, offsets);
-  TS_CHECK_LAUNCH("ts_devox_csr/offsets");
+  devox_csr_offsets_kernel<<<(unsigned)ts_cdiv(n_vox + 1, 256), 256, 0, stream>>>(keys_out, n_slots, n_vox, offsets);
+  TS_CHECK_LAUNCH("ts_group_slots/offsets");
   return TS_OK;
+}
+
+extern "C" size_t ts_devox_csr_workspace_bytes(int64_t n) { return ts_group_slots_workspace_bytes((n < 0 ? 0 : n) * 8); }
+
+// idx / weight [n, 8] (a ts_trilinear_map result); offsets [n_vox + 1] and entries [8 n] int32 out: the slots of voxel v are
+// entries[offsets[v] .. offsets[v + 1]), slot = point * 8 + corner
+extern "C" int ts_devox_csr(const int32_t *idx, const float *weight, int64_t n, int64_t n_vox, int32_t *offsets,
+                            int32_t *entries, void *ws, size_t ws_bytes, ts_stream_t stream_) {
+  TS_REQUIRE(n >= 0 && n < (1LL << 27), TS_ERR_INVALID_ARGUMENT, "ts_devox_csr: bad sizes");
+  TS_REQUIRE(n == 0 || weight, TS_ERR_INVALID_ARGUMENT, "ts_devox_csr: null pointer");
+  return ts_group_slots(idx, weight, n * 8, n_vox, offsets, entries, ws, ws_bytes, (hipStream_t)stream_, "ts_devox_csr");
 }

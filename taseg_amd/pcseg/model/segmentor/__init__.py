@@ -1,6 +1,8 @@
-"""Segmentor registry (reference pcseg/model/segmentor/__init__.py:29-62).  Only the TASeg
-hot-path models exist here; the other OpenPCSeg backbones are out of scope."""
+"""Segmentor registry (reference pcseg/model/segmentor/__init__.py:29-62).  The TASeg hot-path models and Cylinder_TS (the
+network the anisotropic / overlapping-window convolutions were added for) exist here; the other OpenPCSeg backbones are out of
+scope."""
 from .base_segmentors import BaseSegmentor
+from .voxel.cylinder3d.cylinder_ts import Cylinder_TS
 from .voxel.minkunet.minkunet import MinkUNet
 from .voxel.minkunet.minkunet_ms import MinkUNetMs
 from .voxel.minkunet.minkunet_ms_kd import MinkUNetMsKd
@@ -12,9 +14,10 @@ __all__ = {
     "MinkUNetMsKd": MinkUNetMsKd,
     "MinkUNetMsMm": MinkUNetMsMm,
     "MinkUNetMsMmNus": MinkUNetMsMmNus,
+    "Cylinder_TS": Cylinder_TS,
 }
 
-_OUT_OF_SCOPE = ("RangeNet++", "SalsaNext", "FIDNet", "CENet", "Cylinder_TS", "SPVCNN", "RPVNet")
+_OUT_OF_SCOPE = ("RangeNet++", "SalsaNext", "FIDNet", "CENet", "SPVCNN", "RPVNet")
 
 
 def build_segmentor(model_cfgs, num_class):

@@ -10,7 +10,7 @@ from torch.autograd import Function
 from ... import _lib as L
 from ...rccl import c10d_sum, direct_comm
 
-__all__ = ["batch_norm_train", "fast_path_ok"]
+__all__ = ["batch_norm_train", "fast_path_ok", "leaky_batch_norm_train", "leaky_path_ok"]
 
 
 def fast_path_ok(x: torch.Tensor) -> bool:
@@ -139,3 +139,58 @@ def batch_norm_train(x, weight, bias, running_mean, running_var, momentum, eps, 
     """y = BN(x) with batch statistics (over all ranks of `group` when given); updates the running buffers."""
     return batch_norm_act_train(x, weight, bias, running_mean, running_var, momentum, eps, relu=False, residual=None,
                                 group=group, num_batches_tracked=num_batches_tracked)
+
+
+_LEAKY_KERNEL = True        # private switch: False = LeakyReLU and BatchNorm as separate passes (tools/time_cylinder_step.py's baseline)
+
+
+def leaky_path_ok(x: torch.Tensor) -> bool:
+    """rows the ts_leaky_bn_train_* kernels take (the channel rule of fast_path_ok)"""
+    return _LEAKY_KERNEL and fast_path_ok(x)
+
+
+class _LeakyBatchNormTrain(Function):
+    """BN_train(LeakyReLU(x)) (+ residual) on rows [N, C] as ONE node on ts_leaky_bn_train_* (csrc/bn.hip, written for UNet2D's
+    channels-last maps, which are rows too): x - the convolution's output - is what is kept for the backward pass, the activated rows
+    never exist.  The residual's gradient is the incoming gradient."""
+
+    @staticmethod
+    def forward(ctx, x, residual, weight, bias, running_mean, running_var, nbt, momentum, eps, slope):
+        x = x.contiguous()
+        n, c = x.shape
+        half = x.dtype == torch.float16
+        if residual is not None:
+            residual = residual.contiguous().to(x.dtype)
+        lib = L.load()
+        out = torch.empty_like(x)
+        stats = torch.empty((2, c), dtype=torch.float32, device=x.device)
+        ws = L.workspace(lib.ts_bn_train_workspace_bytes(c), x.device)
+        L.check(lib.ts_leaky_bn_train_forward(L.ptr(x), L.ptr(weight), L.ptr(bias), L.ptr(running_mean), L.ptr(running_var),
+                                              L.ptr(nbt), n, c, float(eps), float(momentum), float(slope), 1 if half else 0,
+                                              L.ptr(stats[0]), L.ptr(stats[1]), L.ptr(residual), L.ptr(out), L.ptr(ws), ws.numel(),
+                                              L.stream()), "ts_leaky_bn_train_forward")
+        _bump(running_mean, running_var, nbt)
+        ctx.save_for_backward(x, weight, stats)
+        ctx.slope, ctx.has_res = float(slope), residual is not None
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        x, weight, stats = ctx.saved_tensors
+        n, c = x.shape
+        lib = L.load()
+        grad_out = grad_out.contiguous().to(x.dtype)
+        grad_x = torch.empty_like(x)
+        gwb = torch.empty((2, c), dtype=torch.float32, device=x.device)
+        ws = L.workspace(lib.ts_bn_train_workspace_bytes(c), x.device)
+        L.check(lib.ts_leaky_bn_train_backward(L.ptr(grad_out), L.ptr(x), L.ptr(stats[0]), L.ptr(stats[1]), L.ptr(weight), n, c,
+                                               ctx.slope, 1 if x.dtype == torch.float16 else 0, L.ptr(grad_x), L.ptr(gwb[0]),
+                                               L.ptr(gwb[1]), L.ptr(ws), ws.numel(), L.stream()), "ts_leaky_bn_train_backward")
+        return (grad_x, grad_out if ctx.has_res else None, gwb[0].to(weight.dtype), gwb[1].to(weight.dtype), None, None, None, None,
+                None, None)
+
+
+def leaky_batch_norm_train(x, weight, bias, running_mean, running_var, momentum, eps, slope=0.01, residual=None,
+                           num_batches_tracked=None):
+    """BN(LeakyReLU(x)) [+ residual] with batch statistics on rows [N, C]; updates the running buffers and the batch counter."""
+    return _LeakyBatchNormTrain.apply(x, residual, weight, bias, running_mean, running_var, num_batches_tracked, momentum, eps, slope)

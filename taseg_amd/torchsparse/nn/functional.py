@@ -32,7 +32,8 @@ from ..utils import make_ntuple
 from .utils import get_kernel_offsets
 
 __all__ = ["conv3d", "conv_geometry", "conv_block_ok", "conv_block_eval", "sphash", "sphashquery", "spcount", "spvoxelize", "spdevoxelize", "spdevoxelize_cat", "calc_ti_weights",
-           "spdownsample", "KernelMap", "build_kernel_map", "build_pyramid", "point_linear"]
+           "spdownsample", "KernelMap", "build_kernel_map", "build_pyramid", "point_linear", "spvoxelize_max", "sigmoid3_gate",
+           "gather_rows"]
 
 _fwd = torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
 _bwd = torch.amp.custom_bwd(device_type="cuda")
@@ -1074,3 +1075,92 @@ def conv_block_ok(feats: torch.Tensor, weight: torch.Tensor, kmap: "KernelMap", 
     if feats.shape[1] != c_in:
         return False
     return residual is None or tuple(residual.shape) == (rows, c_out)
+
+
+# ------------------------------------------------------------------------------ Cylinder_TS pieces (csrc/cylinder.hip)
+# Private switches (as kd._PAIR_KERNEL): False puts the tensor-op form in place of the kernel - the baseline tools/time_cylinder_step.py
+# measures against.  Nothing else reads them: a kernel that refuses its input raises, it does not fall back.
+_MAX_KERNEL = True
+_GATE_KERNEL = True
+
+
+class _VoxelizeMax(Function):
+    """out[v, ch] = max over the rows of voxel v (ts_voxelize_max_forward); the gradient goes to the smallest row index that attains
+    the maximum (ts_voxelize_max_backward: a gather).  float32 and float16 rows are taken as they are; other dtypes through float32
+    (a maximum rounds nothing)."""
+
+    @staticmethod
+    def forward(ctx, feats, idx, m):
+        dt = feats.dtype if feats.dtype in (torch.float32, torch.float16) else torch.float32
+        if dt == torch.float16 and feats.shape[1] % 8:
+            dt = torch.float32
+        idx = idx.int().contiguous()
+        out, arg = B.voxelize_max_forward(feats.contiguous().to(dt), idx, m)
+        ctx.saved = (idx, arg, feats.shape[0], feats.dtype, dt)
+        return out.to(feats.dtype)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        idx, arg, n, dtype, dt = ctx.saved
+        return B.voxelize_max_backward(grad_out.contiguous().to(dt), idx, arg, n).to(dtype), None, None
+
+
+def spvoxelize_max(feats: torch.Tensor, idx: torch.Tensor, num: int) -> torch.Tensor:
+    """`torch_scatter.scatter_max(feats, idx, dim=0)[0]` over `num` voxels (seg_utils.py:391): the per-channel maximum of the rows
+    of every voxel, 0 for a voxel without rows; rows with a negative index take no part."""
+    if not _MAX_KERNEL or feats.dtype == torch.float64:          # (double: the tensor ops - the kernels hold float and half)
+        keep = (idx >= 0) & (idx < int(num))
+        out = feats.new_zeros((int(num), feats.shape[1]))
+        return out.scatter_reduce(0, idx[keep].long().unsqueeze(1).expand(-1, feats.shape[1]), feats[keep], "amax", include_self=False)
+    return _VoxelizeMax.apply(feats, idx, int(num))
+
+
+class _Sigmoid3Gate(Function):
+    """x * (sigmoid(u) + sigmoid(v) + sigmoid(w)) and its four gradients, one kernel per direction (ts_sigmoid3_gate_*); operands of
+    mixed dtypes go through float32"""
+
+    @staticmethod
+    def forward(ctx, x, u, v, w):
+        dt = x.dtype if all(t.dtype == x.dtype for t in (u, v, w)) and x.dtype in (torch.float32, torch.float16) else torch.float32
+        ops = [t.contiguous().to(dt) for t in (x, u, v, w)]
+        ctx.save_for_backward(*ops)
+        ctx.dtypes = [t.dtype for t in (x, u, v, w)]
+        return B.sigmoid3_gate_forward(*ops)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        x, u, v, w = ctx.saved_tensors
+        grads = B.sigmoid3_gate_backward(grad_out.contiguous().to(x.dtype), x, u, v, w)
+        return tuple(g.to(d) for g, d in zip(grads, ctx.dtypes))
+
+
+def sigmoid3_gate_ok(x: torch.Tensor) -> bool:
+    return x.is_cuda and x.dim() == 2 and x.shape[0] > 0 and x.shape[1] % 8 == 0 and x.dtype in (torch.float32, torch.float16)
+
+
+def sigmoid3_gate(x: torch.Tensor, u: torch.Tensor, v: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
+    """x * (sigmoid(u) + sigmoid(v) + sigmoid(w)) on rows [n, c] - the gate of ReconBlock (cylinder_ts.py:371-382) in one pass per
+    direction; on the host, or for a channel count the kernel refuses, the tensor ops in the reference's order."""
+    if _GATE_KERNEL and sigmoid3_gate_ok(x) and u.shape == v.shape == w.shape == x.shape:
+        with _no_autocast():
+            return _Sigmoid3Gate.apply(x, u, v, w)
+    return (torch.sigmoid(u) + torch.sigmoid(v) + torch.sigmoid(w)) * x
+
+
+def gather_rows(feats: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
+    """feats[idx] for an index vector (negative entries count from the end, as tensor indexing does) with a deterministic adjoint: a
+    one-neighbour, weight-1 map through ts_devoxelize_forward, its gradient gathered along the inverse map (ts_devox_csr /
+    ts_devoxelize_backward_csr: fixed summation order, no float atomics) where tensor indexing's backward adds rows atomically."""
+    m, c = feats.shape
+    if not (feats.is_cuda and idx.dim() == 1 and m > 0 and c % 4 == 0 and c <= 1024
+            and feats.dtype in (torch.float32, torch.float16)):
+        return feats[idx.long()]
+    idx = idx.int()
+    idx = torch.where(idx < 0, idx + m, idx)
+    inside = (idx >= 0) & (idx < m)            # (tensor indexing raises on the device for anything else; here: a row of zeros)
+    idx8 = torch.full((idx.shape[0], 8), -1, dtype=torch.int32, device=feats.device)
+    idx8[:, 0] = torch.where(inside, idx, torch.full_like(idx, -1))
+    w8 = torch.zeros((idx.shape[0], 8), dtype=torch.float32, device=feats.device)
+    w8[:, 0] = inside.float()
+    with _no_autocast():
+        return spdevoxelize(feats, idx8, w8, B.devox_csr(idx8, w8, m))

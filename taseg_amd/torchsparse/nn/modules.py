@@ -14,7 +14,7 @@ from ... import planes as _planes
 from ...options import options
 from .utils import fapply
 
-__all__ = ["Conv3d", "BatchNorm", "SyncBatchNorm", "ReLU", "LeakyReLU", "bn_act", "conv_bn_act"]
+__all__ = ["Conv3d", "BatchNorm", "SyncBatchNorm", "ReLU", "LeakyReLU", "bn_act", "leaky_bn", "conv_bn_act"]
 
 
 _FUSED_BLOCK = options.fused_block
@@ -128,6 +128,39 @@ def bn_act(mod, input: SparseTensor, relu: bool = True, residual: SparseTensor =
         out = out + res
     if relu:
         out = torch.relu(out)
+    return input._like(out)
+
+
+def _rows_forward(mod):
+    """the torch module's own forward on a feature matrix (the classes below take sparse tensors)"""
+    if isinstance(mod, SyncBatchNorm):
+        return lambda f: nn.SyncBatchNorm.forward(mod, f)
+    if isinstance(mod, BatchNorm):
+        return lambda f: nn.BatchNorm1d.forward(mod, f)
+    return mod.forward
+
+
+def leaky_bn(mod, input: SparseTensor, residual: SparseTensor = None, negative_slope: float = 0.01) -> SparseTensor:
+    """BN(LeakyReLU(input)) [+ residual] for a BatchNorm / SyncBatchNorm module `mod` - conv -> act -> bn (-> + shortcut) of the
+    Cylinder3D blocks (cylinder_ts.py:138-153, 228-244, 315-332; `nn.LeakyReLU()`: slope 0.01).  Training mode with local statistics
+    runs as ONE node on ts_leaky_bn_train_* (the residual added in its elementwise pass; the residual's gradient is the incoming
+    gradient).  Evaluation mode, a channel count the kernel refuses, or statistics shared between ranks: the tensor ops in the
+    reference's order - LeakyReLU in front of the module (SyncBatchNorm across ranks: the existing collective path)."""
+    from .batchnorm import leaky_batch_norm_train, leaky_path_ok
+    feats = input.feats
+    res = None if residual is None else residual.feats
+    group = _sync_group(mod)
+    _require_rows(feats, group)
+    if mod.training and group is None and mod.momentum is not None and mod.affine and mod.track_running_stats \
+            and leaky_path_ok(feats) and mod.weight.dtype == torch.float32 \
+            and (res is None or (res.shape == feats.shape and res.dtype == feats.dtype)):
+        with F._no_autocast():
+            out = leaky_batch_norm_train(feats, mod.weight, mod.bias, mod.running_mean, mod.running_var, mod.momentum, mod.eps,
+                                         slope=negative_slope, residual=res, num_batches_tracked=mod.num_batches_tracked)
+        return input._like(out)
+    out = _bn_forward(mod, torch.nn.functional.leaky_relu(feats, negative_slope), _rows_forward(mod), group)
+    if res is not None:
+        out = out + res
     return input._like(out)
 
 
