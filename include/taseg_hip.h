@@ -596,7 +596,8 @@ int ts_bn_act_train_backward_f16(const void *grad_out, const uint8_t *mask, cons
  * [0] loss scale, [1] growth tracker, [2] gradient multiplier (clip coefficient / scale), [3] skip flag, [4] total norm.
  *   ts_sgd_grad_stats  *sumsq += sum g^2 (double), *nonfinite |= any non-finite        (call once per bucket)
  *   ts_sgd_decide      norm of the unscaled gradients, clip coefficient min(1, max_norm / (norm + 1e-6)), skip flag,
- *                      loss-scale update (amp != 0); clears sumsq / nonfinite for the next step
+ *                      loss-scale update (amp != 0; as GradScaler, the scale is not grown past the largest float);
+ *                      clears sumsq / nonfinite for the next step
  *   ts_sgd_apply       d = g * state[2] + wd * p; m = first_step ? d : momentum * m + d; p -= lr * m   (skipped if flagged) */
 int ts_sgd_grad_stats(const float *grad, int64_t n, double *sumsq, int32_t *nonfinite, ts_stream_t stream);
 int ts_sgd_decide(double *sumsq, int32_t *nonfinite, float *state, float max_norm, float growth, float backoff,

@@ -76,7 +76,8 @@ __global__ void sgd_decide_kernel(double *__restrict__ sumsq, int *__restrict__ 
     } else {
       const float tracker = state[1] + 1.f;
       if ((int)tracker >= growth_interval) {
-        state[0] = scale * growth;
+        const float grown = scale * growth;
+        if (isfinite(grown)) state[0] = grown;                           // torch does not grow the scale past fp32 bounds to inf
         state[1] = 0.f;
       } else {
         state[1] = tracker;
