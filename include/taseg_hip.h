@@ -1143,6 +1143,42 @@ int ts_stage_moving_apply(float *points, int64_t n_rows, int64_t n_cur, int32_t 
 size_t ts_quantize_workspace_bytes(int64_t n);
 int ts_sparse_quantize(const int32_t *coords, int64_t n, int32_t *out_index, int32_t *out_inverse,
                        int32_t *out_count, void *ws, size_t ws_bytes, ts_stream_t stream);
+/* The cylinder data stage (csrc/cylinder_stage.hip; taseg_amd/data/cylinder.py): pcseg/data/dataset/semantickitti/
+ * semantickitti_cylinder.py:104-219 for a whole batch - two passes around one stable radix sort.
+ * ts_cylinder_cells, one lane per row of points [n, point_stride >= 4] float32 (x, y, z, intensity, ...); sample_idx [n] int32 or
+ * NULL (= 0); space = 9 doubles ON THE HOST { min[3], max[3], interval[3] }, interval = (max - min) / (grid - 1) formed in float64
+ * by the caller as :149-151 forms it:
+ *   rho = sqrt(x*x + y*y) in float32 (:20) ; phi = (float)atan2((double)y, (double)x) ; deg = phi / float32(pi) * 180 in float32
+ *   (:21, :145: numpy keeps a float32 array float32 against a Python float).  phi is the ONE difference from the reference: numpy's
+ *   float32 arctan2 is not correctly rounded, this is the float64 value rounded once, as ts_stage_mix takes its yaw.
+ *   cell = (int)floor((clip(pol, min, max) - min) / interval) in float64 (:153): a value outside the space lands in the first or
+ *   last cell of its axis, nothing is dropped.
+ *   centre = (float)(((float)cell + 0.5f) * interval + min), product and sum in float64 (:156, :158)
+ * cells [n, 4] int32 (x, y, z, sample; 16-byte aligned: the sort's input), point_coord [n, 4] int64 the same (32-byte aligned),
+ * point_feature [n, 5 + point_stride] float32 = { centre[3], rho, deg, z, x, y, columns 3 .. } (:160).  A row with a non-finite
+ * x, y or z gets cell 0 and stores TS_CYL_FLAG_NONFINITE to flags[0] (the reference would hand astype(int) a NaN).
+ * ts_cylinder_voxels, :32-45 voxelize_with_label and the per-sample pieces of collate_batch (:176-219) for the batch: the 64-bit
+ * key of ts_sparse_quantize carries the sample, so ONE stable sort orders every sample's voxels as torchsparse's sparse_quantize
+ * does (ascending x, y, z) with a voxel's rows in input order; then head flags, their scan, the samples' first ranks, a scatter and
+ * the vote.  labels [n] int64.  out_index [n] int32: out_index[v] = the FIRST row of voxel v (np.unique's return_index), voxels
+ * sample-major; out_inverse [n] int64: the rank of the row's voxel INSIDE its sample (collate_batch concatenates the inverse maps
+ * without an offset); voxel_label [n] int64: the class with the most rows among the voxel's rows whose label != ignore_label,
+ * the LOWEST class on a tie (np.argmax), class 0 for a voxel of ignored rows only; the first m entries of either are written.
+ * counts [n_samples + 1] int32: the voxels of every sample, then m.  flags [TS_CYL_FLAG_WORDS] int32, zeroed by the caller before
+ * ts_cylinder_cells: flags[1] = TS_CYL_FLAG_LABEL where a label is neither ignore_label nor in [0, num_classes) (an IndexError
+ * in the reference), flags[2] = TS_CYL_FLAG_RANGE where a sample index is outside [0, 1024).  The caller reads counts and flags
+ * in one copy.  The vote gives every voxel 32 lanes, lane c counting class c in an integer register over the voxel's run of the
+ * sorted order (1 <= num_classes <= 32): no [m, C] table, no atomics, no float arithmetic - the same bits every run. */
+#define TS_CYL_FLAG_WORDS 3
+#define TS_CYL_FLAG_NONFINITE 1
+#define TS_CYL_FLAG_LABEL 2
+#define TS_CYL_FLAG_RANGE 4
+int ts_cylinder_cells(const float *points, int64_t n, int32_t point_stride, const int32_t *sample_idx, const double *space,
+                      int32_t *cells, int64_t *point_coord, float *point_feature, int32_t *flags, ts_stream_t stream);
+size_t ts_cylinder_voxels_workspace_bytes(int64_t n, int32_t n_samples);
+int ts_cylinder_voxels(const int32_t *cells, const int64_t *labels, int64_t n, int32_t n_samples, int32_t num_classes,
+                       int64_t ignore_label, int32_t *out_index, int64_t *out_inverse, int64_t *voxel_label, int32_t *counts,
+                       int32_t *flags, void *ws, size_t ws_bytes, ts_stream_t stream);
 
 /* fuse_multi_scan (pcseg/data/dataset/semantickitti/semantickitti_ms.py:403-417):
  * p' = ((p . R_t^T + t_t) - t_0) . R_0 for one history scan, in float32 with the

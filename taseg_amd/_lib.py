@@ -219,6 +219,9 @@ SIGNATURES = {
     "ts_quantize_workspace_bytes": (_sz, [_i64]),
     "ts_sparse_quantize": (_i32, [_vp, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ts_voxel_coords": (_i32, [_vp, _i64, _i32, _c.c_float, _vp, _i32, _vp, _vp, _vp, _vp]),
+    "ts_cylinder_cells": (_i32, [_vp, _i64, _i32, _vp, _c.POINTER(_c.c_double), _vp, _vp, _vp, _vp, _vp]),
+    "ts_cylinder_voxels_workspace_bytes": (_sz, [_i64, _i32]),
+    "ts_cylinder_voxels": (_i32, [_vp, _vp, _i64, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
 

@@ -1656,6 +1656,74 @@ def sparse_quantize(coords):
     return index[:m], inverse[:n]
 
 
+CYL_FLAG_WORDS = 3          # include/taseg_hip.h TS_CYL_FLAG_WORDS: non-finite row | bad label | sample index out of range
+
+
+def cylinder_cells(points, space, sample_idx=None, flags=None):
+    """csrc/cylinder_stage.hip: the per-row pass of the cylinder data stage (semantickitti_cylinder.py:144-160).  points [n, F >= 4]
+    float32, space = the 9 float64 { min, max, interval } on the host, sample_idx [n] int32 or None (= 0), flags [CYL_FLAG_WORDS]
+    int32 ZEROED by the caller (None: allocated here).  Returns (cells [n, 4] int32, point_coord [n, 4] int64, point_feature
+    [n, 5 + F] float32, flags).  No host read."""
+    L.require_device(points, sample_idx, flags)
+    points = _f32(points, "points")
+    if points.ndim != 2 or points.shape[1] < 4:
+        raise TypeError("points must be a float32 [n, F >= 4] tensor (x, y, z, intensity, ...)")
+    n, f = points.shape
+    space = [float(v) for v in space]
+    if len(space) != 9:
+        raise ValueError("space holds 9 doubles: min, max, interval of the three axes")
+    if sample_idx is not None:
+        sample_idx = _i32(sample_idx, "sample_idx")
+        if sample_idx.shape != (n,):
+            raise ValueError("sample_idx must hold one index per point")
+    dev = points.device
+    if flags is None:
+        flags = torch.zeros(CYL_FLAG_WORDS, dtype=torch.int32, device=dev)
+    elif flags.dtype != torch.int32 or flags.shape != (CYL_FLAG_WORDS,) or not flags.is_contiguous():
+        raise TypeError("flags must be a contiguous int32 [%d] tensor" % CYL_FLAG_WORDS)
+    cells = torch.empty((n, 4), dtype=torch.int32, device=dev)
+    coord = torch.empty((n, 4), dtype=torch.int64, device=dev)
+    feat = torch.empty((n, 5 + f), dtype=torch.float32, device=dev)
+    L.check(L.load().ts_cylinder_cells(L.ptr(points), n, f, L.ptr(sample_idx), (L._c.c_double * 9)(*space), L.ptr(cells),
+                                       L.ptr(coord), L.ptr(feat), L.ptr(flags), L.stream()), "ts_cylinder_cells")
+    return cells, coord, feat, flags
+
+
+def cylinder_voxels(cells, labels, n_samples, num_classes=20, ignore_label=67, counts=None, flags=None):
+    """csrc/cylinder_stage.hip: voxels, per-sample inverse map and majority-vote labels of a batch of cells (semantickitti_cylinder.py
+    :32-45) in one chain around one stable sort.  cells [n, 4] int32 (x, y, z, sample), labels [n] int64; counts [n_samples + 1]
+    int32 and flags [CYL_FLAG_WORDS] int32 (zeroed) may be views of one tensor, so ONE copy reads both.  Returns (index [n] int32,
+    inverse_local [n] int64, voxel_label [n] int64, counts, flags): the first counts[-1] entries of index and voxel_label are
+    written.  No host read here."""
+    L.require_device(cells, labels, counts, flags)
+    cells = _i32(cells, "cells")
+    if cells.ndim != 2 or cells.shape[1] != 4:
+        raise TypeError("cells must be an int32 [n, 4] tensor")
+    if labels.dtype != torch.int64:
+        raise TypeError("labels must be int64")
+    labels = labels.contiguous()
+    n, nb = cells.shape[0], int(n_samples)
+    if labels.shape != (n,):
+        raise ValueError("labels must hold one class per row")
+    dev = cells.device
+    if counts is None:
+        counts = torch.empty(nb + 1, dtype=torch.int32, device=dev)
+    if flags is None:
+        flags = torch.zeros(CYL_FLAG_WORDS, dtype=torch.int32, device=dev)
+    for t, size, name in ((counts, nb + 1, "counts"), (flags, CYL_FLAG_WORDS, "flags")):
+        if t.dtype != torch.int32 or t.shape != (size,) or not t.is_contiguous():
+            raise TypeError("%s must be a contiguous int32 [%d] tensor" % (name, size))
+    lib = L.load()
+    ws = L.workspace(lib.ts_cylinder_voxels_workspace_bytes(n, nb), dev)
+    index = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+    inverse = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
+    voxel_label = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
+    L.check(lib.ts_cylinder_voxels(L.ptr(cells), L.ptr(labels), n, nb, int(num_classes), int(ignore_label), L.ptr(index),
+                                   L.ptr(inverse), L.ptr(voxel_label), L.ptr(counts), L.ptr(flags), L.ptr(ws), ws.numel(),
+                                   L.stream()), "ts_cylinder_voxels")
+    return index, inverse[:n], voxel_label, counts, flags
+
+
 def _tile_cols(c):
     return 128 if c % 128 == 0 else 96 if c % 96 == 0 else 64 if c % 64 == 0 else 32
 

@@ -12,9 +12,7 @@
 #include <climits>
 
 #include "common.h"
-
-#define TQ_CBIAS (1 << 17)
-#define TQ_CMASK ((1u << 18) - 1)
+#include "quantize_keys.h"      // the key, sq_pack_kernel, sq_flag_kernel (shared with csrc/cylinder_stage.hip)
 
 // ------------------------------------------------------------------ float points -> integer voxel coords
 // The per-sample minima are reduced in registers (one sample) or LDS (<= 64 samples) first: one global atomicMin per
@@ -180,28 +178,6 @@ extern "C" int ts_segment_min3(const float *points, int64_t n, int32_t point_str
 }
 
 // ------------------------------------------------------------------ sparse_quantize
-__global__ __launch_bounds__(256) void sq_pack_kernel(const int4 *__restrict__ c, int64_t n, uint64_t *__restrict__ keys,
-                                                      int *__restrict__ vals, int *__restrict__ err) {
-  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  int64_t step = (int64_t)gridDim.x * blockDim.x;
-  for (; i < n; i += step) {
-    int4 v = c[i];
-    bool ok = (unsigned)(v.x + TQ_CBIAS) <= TQ_CMASK && (unsigned)(v.y + TQ_CBIAS) <= TQ_CMASK &&
-              (unsigned)(v.z + TQ_CBIAS) <= TQ_CMASK && (unsigned)v.w < 1024u;
-    if (!ok) *err = 1;
-    keys[i] = ((uint64_t)(unsigned)v.w << 54) | ((uint64_t)(unsigned)(v.x + TQ_CBIAS) << 36) |
-              ((uint64_t)(unsigned)(v.y + TQ_CBIAS) << 18) | (uint64_t)(unsigned)(v.z + TQ_CBIAS);
-    vals[i] = (int)i;
-  }
-}
-
-__global__ __launch_bounds__(256) void sq_flag_kernel(const uint64_t *__restrict__ keys, int64_t n,
-                                                      unsigned *__restrict__ flags) {
-  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  int64_t step = (int64_t)gridDim.x * blockDim.x;
-  for (; i < n; i += step) flags[i] = (i == 0 || keys[i] != keys[i - 1]) ? 1u : 0u;
-}
-
 // ranks = inclusive scan of head flags; rank-1 = voxel id of sorted position i
 __global__ __launch_bounds__(256) void sq_scatter_kernel(const uint64_t *__restrict__ keys, const int *__restrict__ vals,
                                                          const unsigned *__restrict__ ranks, int64_t n,
