@@ -786,6 +786,27 @@ int ts_eval_votes(const void *logits, int32_t half, int32_t C, int64_t n_vox, co
                   int32_t n_scenes, const int64_t *inv, const int32_t *rows, const int64_t *kept, int64_t n_pts,
                   const int64_t *num_points, const int64_t *num_points_ms, void *label, int32_t label_bytes, float *sums,
                   float *top3, int64_t cap, int64_t *n_out, int32_t *flags, ts_stream_t stream);
+/* The same two reductions for a model whose logits rows are NOT grouped by scene and whose points find their row through the hash of
+ * their cell (Cylinder_TS, R/pcseg/model/segmentor/voxel/cylinder3d/cylinder_ts.py:244-260: rows in ascending-hash order over the
+ * batch): grows [n_pts] int64 names the GLOBAL logits row of every point (-1 = the lookup found none) in place of the per-scene
+ * inverse map, and labels [n_pts] are aligned with the points (no batch column of their own).  counts / scene_flags: what
+ * ts_scene_counts wrote ([3][n_scenes]; only the POINT row is read - call it with the points' batch column, int32 with a stride,
+ * grouped by scene in ascending order, and n_vox = n_lab = 0).  The kept points of scene s are its first m_s = min(cnt_p[s],
+ * max(num_points[s], 0)) points; no mask, no num_points_ms.
+ *   ts_eval_confusion_rows  hist += 1 at (labels[p], arg-max of logits[grows[p]]) for every kept point whose label lies in 0 .. C - 1;
+ *                           pred (optional) as in ts_eval_confusion; m_out (optional) [n_scenes] int64 = m_s.  One launch.
+ *   ts_eval_votes_rows      as ts_eval_votes: the scenes are the votes of one scan, equal m_s; label / sums / top3 / n_out.  One launch.
+ * Flags: bits 0, 1 and 4 as above (bits 2, 3 and 5 cannot rise); bit 6 (64) a point's row is negative or >= n_vox: the point
+ * contributes nothing (confusion: not tallied, its pred is 0; votes: its term of the sum is left out).  Every row and position is
+ * range-checked before it addresses a load; n_pts = 0 is valid (grows, labels may be NULL). */
+int ts_eval_confusion_rows(const void *logits, int32_t half, int32_t C, int64_t n_vox, const int64_t *counts,
+                           const int32_t *scene_flags, int32_t n_scenes, const int64_t *grows, int64_t n_pts, const void *labels,
+                           int32_t label_bytes, const int64_t *num_points, int64_t *hist, int32_t *pred, int64_t pred_cap,
+                           int64_t *m_out, int32_t *flags, ts_stream_t stream);
+int ts_eval_votes_rows(const void *logits, int32_t half, int32_t C, int64_t n_vox, const int64_t *counts, const int32_t *scene_flags,
+                       int32_t n_scenes, const int64_t *grows, int64_t n_pts, const int64_t *num_points, void *label,
+                       int32_t label_bytes, float *sums, float *top3, int64_t cap, int64_t *n_out, int32_t *flags,
+                       ts_stream_t stream);
 /* Column concatenation / slicing of row-major feature matrices - torchsparse.cat (TS/torchsparse/operators.py:10-17: torch.cat of
  * the feature matrices along dim 1, the skip connections of the decoder, R/pcseg/model/segmentor/voxel/minkunet/minkunet.py:403-416)
  * and its gradient, for callers that chain block calls without tensors (the stage programs of csrc/fastpath/stage_program.h).

@@ -152,6 +152,8 @@ SIGNATURES = {
                                  _vp, _vp]),
     "ts_eval_votes": (_i32, [_vp, _i32, _i32, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i32, _vp, _vp, _i64, _vp, _vp,
                              _vp]),
+    "ts_eval_confusion_rows": (_i32, [_vp, _i32, _i32, _i64, _vp, _vp, _i32, _vp, _i64, _vp, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "ts_eval_votes_rows": (_i32, [_vp, _i32, _i32, _i64, _vp, _vp, _i32, _vp, _i64, _vp, _vp, _i32, _vp, _vp, _i64, _vp, _vp, _vp]),
     "ts_cat_cols": (_i32, [_vp, _i64, _vp, _i64, _i64, _vp, _vp]),
     "ts_copy_cols": (_i32, [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _vp]),
     "ts_conv_block_forward": (_i32, [_vp, _i64, _i32, _vp, _i32, _vp, _vp, _i64, _i32, _vp, _i64, _i32, _vp, _vp, _vp, _vp,

@@ -21,7 +21,7 @@ __all__ = [
     "convolution_forward_cuda", "convolution_backward_cuda",
     "downsample", "unique_i64", "build_kmap", "trilinear_map", "conv_nbr", "conv_wgrad", "conv_class_plan", "conv_class_gemm", "conv_class_gemm_f16", "conv_class_conv", "conv_class_conv_f16", "class_finish_pays",
     "fuse_scan", "fuse_scans", "fuse_sweeps", "project_fov", "voxel_coords", "sparse_quantize", "set_conv_impl", "image_gather_forward", "image_gather_backward", "image_gather_rows_forward", "image_gather_rows_backward", "avgpool3s2_rows_forward", "avgpool3s2_rows_backward", "conv3x3c32_pack", "conv3x3c32_rows", "conv3x3c32_wgrad", "conv3x3_rows_takes", "conv3x3_rows_pack", "conv3x3_rows", "conv3x3_wgrad", "conv1x1c32_pack", "conv1x1c32_rows", "conv1x1c32_wgrad", "shuffle_cat_rows_takes", "shuffle_cat_rows_forward", "shuffle_cat_rows_backward",
-    "eval_confusion", "eval_votes",
+    "eval_confusion", "eval_votes", "eval_confusion_rows", "eval_votes_rows",
     "voxelize_max_forward", "voxelize_max_backward", "sigmoid3_gate_forward", "sigmoid3_gate_backward",
 ]
 
@@ -2004,6 +2004,22 @@ def eval_confusion(logits, vox_batch, pts_batch, inv, labels, lab_batch, num_poi
     return pred
 
 
+def _vote_buffers(what, cap, c, label_bytes, want_sums, want_top3, dev, out):
+    """the output dictionary of a votes call: fresh buffers of `cap` rows, or `out` (an earlier call's) where it fits them"""
+    fresh = {"label": torch.empty(cap, dtype=torch.uint8 if label_bytes == 1 else torch.int32, device=dev),
+             "sums": torch.empty((cap, c), dtype=torch.float32, device=dev) if want_sums else None,
+             "top3": torch.empty((cap, 3), dtype=torch.float32, device=dev) if want_top3 else None,
+             "n": torch.zeros(1, dtype=torch.int64, device=dev)}
+    if out is None:
+        return fresh
+    for key, t in fresh.items():
+        o = out.get(key)
+        if (t is None) != (o is None) or (t is not None and (o.dtype, o.shape, o.device) != (t.dtype, t.shape, t.device)) or \
+                (o is not None and not o.is_contiguous()):
+            raise ValueError(f"{what}: out[{key!r}] does not fit this batch")
+    return out
+
+
 def eval_votes(logits, vox_batch, pts_batch, inv, num_points, flags, point_mask=None, num_points_ms=None, label_bytes=4,
                want_sums=False, want_top3=False, out=None):
     """csrc/evaltail.hip: the scenes of the batch are the votes of ONE scan (collate_batch_tta): their logits summed per point in
@@ -2021,20 +2037,84 @@ def eval_votes(logits, vox_batch, pts_batch, inv, num_points, flags, point_mask=
     if want_top3 and c < 3:
         raise ValueError("eval_votes: the three largest sums need at least three classes")
     cap = n_pts // votes
-    fresh = {"label": torch.empty(cap, dtype=torch.uint8 if label_bytes == 1 else torch.int32, device=dev),
-             "sums": torch.empty((cap, c), dtype=torch.float32, device=dev) if want_sums else None,
-             "top3": torch.empty((cap, 3), dtype=torch.float32, device=dev) if want_top3 else None,
-             "n": torch.zeros(1, dtype=torch.int64, device=dev)}
-    if out is not None:
-        for key, t in fresh.items():
-            o = out.get(key)
-            if (t is None) != (o is None) or (t is not None and (o.dtype, o.shape, o.device) != (t.dtype, t.shape, t.device)) or \
-                    (o is not None and not o.is_contiguous()):
-                raise ValueError(f"eval_votes: out[{key!r}] does not fit this batch")
-        fresh = out
+    fresh = _vote_buffers("eval_votes", cap, c, label_bytes, want_sums, want_top3, dev, out)
     label, sums, top3, n = fresh["label"], fresh["sums"], fresh["top3"], fresh["n"]
     L.check(L.load().ts_eval_votes(*head, *tail, L.ptr(label), label_bytes, L.ptr(sums), L.ptr(top3), cap, L.ptr(n), L.ptr(flags),
                                    L.stream()), "ts_eval_votes")
+    return fresh
+
+
+def _eval_batch_rows(logits, rows, pts_batch, num_points, what):
+    """_eval_batch for the _rows calls (logits rows not grouped by scene: Cylinder_TS): argument checks and ts_scene_counts over the
+    points' batch column alone.  Returns the leading arguments of the reduce call, num_points on the device, and what they point
+    into."""
+    L.require_device(logits, rows, pts_batch)
+    if logits.dim() != 2 or logits.dtype not in (torch.float32, torch.float16):
+        raise ValueError(f"{what}: logits must be a float32 or float16 [n, C] tensor (got {logits.dtype}, {tuple(logits.shape)})")
+    n_scenes = int(torch.as_tensor(num_points).numel())
+    if not 1 <= n_scenes <= 64:
+        raise ValueError(f"{what}: 1 .. 64 scenes per batch (got {n_scenes})")
+    if pts_batch.dtype != torch.int32 or pts_batch.dim() != 1:
+        raise ValueError(f"{what}: pts_batch must be a 1-d int32 tensor (a column of a coordinate matrix may be strided)")
+    if rows.dtype != torch.int64 or rows.dim() != 1 or rows.shape[0] != pts_batch.shape[0]:
+        raise ValueError(f"{what}: rows must hold one int64 logits row per point")
+    np_d = torch.as_tensor(num_points).reshape(-1)
+    if np_d.is_floating_point():
+        raise ValueError(f"{what}: num_points must hold one integer per scene")
+    dev = logits.device
+    logits, rows = logits.contiguous(), rows.contiguous()
+    np_d = np_d.to(dev, non_blocking=True).long().contiguous()
+    n_pts = rows.shape[0]
+    meta = torch.empty(8 + 4 * n_scenes, dtype=torch.int64, device=dev)      # [scene flags | counts 3 x n | m n]
+    counts = meta.data_ptr() + 64
+    L.check(L.load().ts_scene_counts(None, 1, 0, L.ptr(pts_batch), int(pts_batch.stride(0)) if n_pts > 1 else 1, n_pts, None, 1, 0,
+                                     n_scenes, counts, meta.data_ptr(), L.stream()), "ts_scene_counts")
+    head = (L.ptr(logits), 1 if logits.dtype == torch.float16 else 0, logits.shape[1], logits.shape[0], counts, meta.data_ptr(),
+            n_scenes, L.ptr(rows), n_pts)
+    return head, np_d, (logits, rows, meta)
+
+
+def eval_confusion_rows(logits, rows, pts_batch, labels, num_points, hist, flags, want_pred=False, want_counts=False):
+    """csrc/evaltail.hip ts_eval_confusion_rows: eval_confusion for a model whose logits rows are NOT grouped by scene (Cylinder_TS:
+    ascending hash over the batch).  rows [n_pts] int64: the GLOBAL logits row of every point, -1 where the lookup found none (flag
+    bit 64: the point is not tallied, its pred is 0); pts_batch: the points' int32 scene index, grouped by scene; labels [n_pts]
+    uint8 / int32 / int64, ALIGNED with the points; num_points one integer per scene.  hist and flags as in eval_confusion (added to /
+    OR-ed into); ts_scene_counts + one launch, no host read.  want_pred / want_counts as there."""
+    L.require_device(labels, hist, flags)
+    if labels.dtype not in _EVAL_LABEL_BYTES or labels.dim() != 1:
+        raise ValueError(f"eval_confusion_rows: labels must be a 1-d uint8, int32 or int64 tensor (got {labels.dtype})")
+    head, np_d, keep = _eval_batch_rows(logits, rows, pts_batch, num_points, "eval_confusion_rows")
+    c, n_scenes, n_pts = head[2], head[6], head[-1]
+    if labels.shape[0] != n_pts:
+        raise ValueError("eval_confusion_rows: one label per point")
+    if hist.dtype != torch.int64 or tuple(hist.shape) != (c, c) or not hist.is_contiguous():
+        raise ValueError(f"eval_confusion_rows: hist must be a contiguous int64 [{c}, {c}] tensor")
+    _eval_flags(flags, "eval_confusion_rows")
+    labels = labels.contiguous()
+    pred = torch.empty(n_pts, dtype=torch.int32, device=logits.device) if want_pred else None
+    m = keep[2][8 + 3 * n_scenes:] if want_counts else None
+    L.check(L.load().ts_eval_confusion_rows(*head, L.ptr(labels), _EVAL_LABEL_BYTES[labels.dtype], L.ptr(np_d), L.ptr(hist), L.ptr(pred),
+                                            n_pts if want_pred else 0, L.ptr(m), L.ptr(flags), L.stream()), "ts_eval_confusion_rows")
+    return (pred, m) if want_counts else pred
+
+
+def eval_votes_rows(logits, rows, pts_batch, num_points, flags, label_bytes=4, want_sums=False, want_top3=False, out=None):
+    """csrc/evaltail.hip ts_eval_votes_rows: eval_votes with a GLOBAL logits row per point (see eval_confusion_rows) - the scenes of the
+    batch are the votes of ONE scan.  Returns {"label", "n", "sums", "top3"} as eval_votes does; a vote whose row is missing leaves its
+    term out of the sum and raises flag bit 64."""
+    if label_bytes not in (1, 4):
+        raise ValueError("eval_votes_rows: labels of 1 (uint8) or 4 (uint32) bytes")
+    L.require_device(flags)
+    head, np_d, keep = _eval_batch_rows(logits, rows, pts_batch, num_points, "eval_votes_rows")
+    _eval_flags(flags, "eval_votes_rows")
+    c, votes, n_pts, dev = head[2], head[6], head[-1], logits.device
+    if want_top3 and c < 3:
+        raise ValueError("eval_votes_rows: the three largest sums need at least three classes")
+    cap = n_pts // votes
+    fresh = _vote_buffers("eval_votes_rows", cap, c, label_bytes, want_sums, want_top3, dev, out)
+    label, sums, top3, n = fresh["label"], fresh["sums"], fresh["top3"], fresh["n"]
+    L.check(L.load().ts_eval_votes_rows(*head, L.ptr(np_d), L.ptr(label), label_bytes, L.ptr(sums), L.ptr(top3), cap, L.ptr(n),
+                                        L.ptr(flags), L.stream()), "ts_eval_votes_rows")
     return fresh
 
 

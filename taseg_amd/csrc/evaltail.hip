@@ -9,7 +9,7 @@
 //                    points: rows of C <= 64 values move as whole rows - one launch
 // For arrays grouped by scene (every collated batch) the scene-major order IS the array order: no sort.  Anything else is
 // flagged, and the caller falls back to the sorted form (taseg_amd/pcseg/model/.../minkunet.py::unvoxelise_predictions).
-// Second half of the file: evaluation that stays on the device (ts_eval_rows, ts_eval_confusion, ts_eval_votes).
+// Second half of the file: evaluation that stays on the device (ts_eval_rows, ts_eval_confusion, ts_eval_votes and their _rows forms).
 #include "common.h"
 #include "compact.h"
 
@@ -139,8 +139,11 @@ extern "C" int ts_unvoxelise(const void *logits, int32_t half, int32_t C, const 
 //   ts_eval_votes      one launch: a lane per point of the scan walks the votes in order (float32 sum in vote order: the bits of
 //                      numpy's `total += logits[v]`), arg-max, payload store, optional sums / three largest sums
 // Without a mask the kept points are a per-scene prefix of the point array: the reduce kernels index `inv` themselves.
+//   ts_eval_confusion_rows / ts_eval_votes_rows  the same two launches for a model whose logits rows are NOT grouped by scene
+//                      (Cylinder_TS: ascending hash over the batch): a point names its logits row itself (`grows`, the batch-wide
+//                      hash lookup), labels are aligned with the points.  Same kernels, a second row rule in et_row.
 // Every index is range-checked before it addresses a load: inverse map entries against the scene's voxel count AND the logits'
-// row count, point / label / table positions against the lengths of their arrays.
+// row count, global rows against the logits' row count, point / label / table positions against the lengths of their arrays.
 
 namespace {
 
@@ -181,6 +184,7 @@ struct EtBatch {
   const long long *inv;                // no mask: [n_pts]
   const int *rows;                     // mask: ts_eval_rows' table [n_pts] ...
   const long long *kept;               // ... and counts [n_scenes]
+  const long long *grows;              // the _rows calls: [n_pts] GLOBAL logits row of every point (-1: none); labels follow the points
   long long n_vox, n_pts, n_lab;
   const long long *num_points, *num_points_ms;
 };
@@ -189,7 +193,7 @@ struct EtBatch {
 __device__ __forceinline__ void et_layout(const EtBatch &b, EtScenes &L) {
   const int t = threadIdx.x;
   if (t < b.n_scenes) {
-    const long long cv = b.counts[t], cp = b.counts[b.n_scenes + t], cl = b.counts[2 * b.n_scenes + t];
+    const long long cv = b.counts[t], cp = b.counts[b.n_scenes + t], cl = b.grows ? cp : b.counts[2 * b.n_scenes + t];
     const long long np0 = b.num_points[t], np = np0 > 0 ? np0 : 0;
     const long long k = b.kept ? b.kept[t] : cp;
     L.cnt_v[t] = cv;
@@ -223,8 +227,14 @@ __device__ __forceinline__ void et_layout(const EtBatch &b, EtScenes &L) {
   __syncthreads();
 }
 
-// logits row of kept point j < m_s of scene s, -1 where the inverse map (or, cannot happen, a position) is out of range
+// logits row of kept point j < m_s of scene s, -1 where the inverse map / the global row (or, cannot happen, a position) is out
+// of range
 __device__ __forceinline__ long long et_row(const EtBatch &b, const EtScenes &L, int s, long long j) {
+  if (b.grows) {
+    const long long at = L.start_p[s] + j;
+    const long long r = (at >= 0 && at < b.n_pts) ? b.grows[at] : -1;
+    return (r >= 0 && r < b.n_vox) ? r : -1;
+  }
   long long local = -1;
   if (b.kept) {
     const long long at = L.start_k[s] + j;
@@ -248,7 +258,8 @@ __device__ __forceinline__ void et_argmax(float f, int c, float &best, int &arg)
 template <typename T, bool VEC>
 __global__ __launch_bounds__(256) void eval_confusion_kernel(const T *__restrict__ logits, int C, EtBatch b, const void *__restrict__ labels,
                                                              int label_bytes, unsigned long long *__restrict__ hist,
-                                                             int *__restrict__ pred, long long pred_cap, int *__restrict__ flags) {
+                                                             int *__restrict__ pred, long long pred_cap, long long *__restrict__ m_out,
+                                                             int *__restrict__ flags) {
   __shared__ EtScenes L;
   __shared__ unsigned tab[32 * 32];
   const bool lds = C <= 32;
@@ -257,6 +268,8 @@ __global__ __launch_bounds__(256) void eval_confusion_kernel(const T *__restrict
   et_layout(b, L);
   int bad = 0;
   if (blockIdx.x == 0 && threadIdx.x == 0) bad = L.flags;
+  if (m_out && blockIdx.x == 0 && (int)threadIdx.x < b.n_scenes) m_out[threadIdx.x] = L.m[threadIdx.x];
+  const int no_row = b.grows ? 64 : 4;
   const long long total = L.start_m[b.n_scenes], step = (long long)gridDim.x * 256;
   int s = 0;
   for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < total; q += step) {
@@ -264,7 +277,7 @@ __global__ __launch_bounds__(256) void eval_confusion_kernel(const T *__restrict
     const long long j = q - L.start_m[s];
     const long long r = et_row(b, L, s, j);
     if (r < 0) {
-      bad |= 4;
+      bad |= no_row;
       if (pred && q < pred_cap) pred[q] = 0;
       continue;
     }
@@ -340,7 +353,7 @@ __global__ __launch_bounds__(256) void eval_votes_kernel(const T *__restrict__ l
       for (int v = 0; v < b.n_scenes; ++v) {
         const long long r = et_row(b, L, v, j);
         if (r < 0) {
-          bad |= 4;
+          bad |= b.grows ? 64 : 4;
           continue;
         }
         const T *src = logits + r * C + c0;
@@ -411,16 +424,55 @@ __global__ __launch_bounds__(256) void eval_votes_kernel(const T *__restrict__ l
 }
 
 int et_check_batch(const char *name, const void *logits, int32_t C, int64_t n_vox, const int64_t *counts, const int32_t *scene_flags,
-                   int32_t n_scenes, const int64_t *inv, const int32_t *rows, const int64_t *kept, int64_t n_pts,
+                   int32_t n_scenes, const int64_t *inv, const int32_t *rows, const int64_t *kept, const int64_t *grows, int64_t n_pts,
                    const int64_t *num_points, int32_t *flags) {
   TS_REQUIRE(C > 0 && C <= 4096 && n_scenes > 0 && n_scenes <= ET_MAX_SCENES && n_vox >= 0 && n_pts >= 0 && n_vox < (int64_t)1 << 40 &&
                  n_pts < (int64_t)1 << 40,
              TS_ERR_INVALID_ARGUMENT, "%s: bad sizes (at most %d scenes)", name, ET_MAX_SCENES);
   TS_REQUIRE(counts && scene_flags && num_points && flags, TS_ERR_INVALID_ARGUMENT, "%s: null pointer", name);
-  TS_REQUIRE(!(kept && inv) && !(rows && !kept), TS_ERR_INVALID_ARGUMENT,
-             "%s: either the inverse map or the table and counts of ts_eval_rows", name);
-  TS_REQUIRE(n_pts == 0 || ((kept ? rows != nullptr : inv != nullptr) && (n_vox == 0 || logits)), TS_ERR_INVALID_ARGUMENT,
+  TS_REQUIRE(!(kept && inv) && !(rows && !kept) && !(grows && (inv || rows || kept)), TS_ERR_INVALID_ARGUMENT,
+             "%s: either the inverse map or the table and counts of ts_eval_rows (the _rows calls: the global rows alone)", name);
+  TS_REQUIRE(n_pts == 0 || ((grows || (kept ? rows != nullptr : inv != nullptr)) && (n_vox == 0 || logits)), TS_ERR_INVALID_ARGUMENT,
              "%s: null pointer", name);
+  return TS_OK;
+}
+
+// the launches both forms of a call share: half rows element-wise, float rows as float4 where C and the pointers allow
+int et_launch_confusion(const char *name, const void *logits, int32_t half, int32_t C, const EtBatch &b, const void *labels,
+                        int32_t label_bytes, int64_t *hist, int32_t *pred, int64_t pred_cap, int64_t *m_out, int32_t *flags,
+                        hipStream_t stream) {
+  // (without points one block still runs: it carries ts_scene_counts' flags and the per-scene checks over)
+  const unsigned grid = (unsigned)std::min<int64_t>(std::max<int64_t>(ts_cdiv(b.n_pts, 256), 1), 1024);
+  unsigned long long *h = (unsigned long long *)hist;
+  long long *m = (long long *)m_out;
+  if (half)
+    eval_confusion_kernel<_Float16, false><<<grid, 256, 0, stream>>>((const _Float16 *)logits, C, b, labels, label_bytes, h, pred, pred_cap, m,
+                                                                     flags);
+  else if (C % 4 == 0 && ((uintptr_t)logits & 15) == 0)
+    eval_confusion_kernel<float, true><<<grid, 256, 0, stream>>>((const float *)logits, C, b, labels, label_bytes, h, pred, pred_cap, m, flags);
+  else
+    eval_confusion_kernel<float, false><<<grid, 256, 0, stream>>>((const float *)logits, C, b, labels, label_bytes, h, pred, pred_cap, m, flags);
+  TS_CHECK_LAUNCH(name);
+  return TS_OK;
+}
+
+int et_launch_votes(const char *name, const void *logits, int32_t half, int32_t C, const EtBatch &b, void *label, int32_t label_bytes,
+                    float *sums, float *top3, int64_t cap, int64_t *n_out, int32_t *flags, hipStream_t stream) {
+  TS_REQUIRE(cap >= 0 && n_out && (cap == 0 || label) && (label_bytes == 1 || label_bytes == 4) && (!top3 || C >= 3), TS_ERR_INVALID_ARGUMENT,
+             "%s: bad arguments (labels of 1 or 4 bytes; the three largest sums need 3 classes)", name);
+  TS_REQUIRE(label_bytes == 1 || ((uintptr_t)label & 3) == 0, TS_ERR_INVALID_ARGUMENT, "%s: unaligned label buffer", name);
+  TS_REQUIRE(ts_cdiv(cap, 256) < (int64_t)1 << 31, TS_ERR_INVALID_ARGUMENT, "%s: too many rows", name);
+  const unsigned grid = (unsigned)std::max<int64_t>(ts_cdiv(cap, 256), 1);
+  if (half)
+    eval_votes_kernel<_Float16, false><<<grid, 256, 0, stream>>>((const _Float16 *)logits, C, b, label, label_bytes, sums, top3, cap,
+                                                                 (long long *)n_out, flags);
+  else if (C % 4 == 0 && ((uintptr_t)logits & 15) == 0 && (!sums || ((uintptr_t)sums & 15) == 0))
+    eval_votes_kernel<float, true><<<grid, 256, 0, stream>>>((const float *)logits, C, b, label, label_bytes, sums, top3, cap, (long long *)n_out,
+                                                             flags);
+  else
+    eval_votes_kernel<float, false><<<grid, 256, 0, stream>>>((const float *)logits, C, b, label, label_bytes, sums, top3, cap,
+                                                              (long long *)n_out, flags);
+  TS_CHECK_LAUNCH(name);
   return TS_OK;
 }
 
@@ -460,50 +512,55 @@ extern "C" int ts_eval_confusion(const void *logits, int32_t half, int32_t C, in
                                  const int64_t *kept, int64_t n_pts, const void *labels, int32_t label_bytes, int64_t n_lab,
                                  const int64_t *num_points, const int64_t *num_points_ms, int64_t *hist, int32_t *pred,
                                  int64_t pred_cap, int32_t *flags, ts_stream_t stream) {
-  const int rc = et_check_batch("ts_eval_confusion", logits, C, n_vox, counts, scene_flags, n_scenes, inv, rows, kept, n_pts, num_points, flags);
+  const int rc = et_check_batch("ts_eval_confusion", logits, C, n_vox, counts, scene_flags, n_scenes, inv, rows, kept, nullptr, n_pts,
+                                num_points, flags);
   if (rc != TS_OK) return rc;
   TS_REQUIRE(hist && n_lab >= 0 && (n_lab == 0 || labels) && (label_bytes == 1 || label_bytes == 4 || label_bytes == 8) && pred_cap >= 0,
              TS_ERR_INVALID_ARGUMENT, "ts_eval_confusion: bad arguments (labels of 1, 4 or 8 bytes)");
-  const EtBatch b = {(const long long *)counts, scene_flags, n_scenes, (const long long *)inv, rows, (const long long *)kept,
+  const EtBatch b = {(const long long *)counts, scene_flags, n_scenes, (const long long *)inv, rows, (const long long *)kept, nullptr,
                      n_vox, n_pts, n_lab, (const long long *)num_points, (const long long *)num_points_ms};
-  // (without points one block still runs: it carries ts_scene_counts' flags and the per-scene checks over)
-  const unsigned grid = (unsigned)std::min<int64_t>(std::max<int64_t>(ts_cdiv(n_pts, 256), 1), 1024);
-  unsigned long long *h = (unsigned long long *)hist;
-  if (half)
-    eval_confusion_kernel<_Float16, false><<<grid, 256, 0, (hipStream_t)stream>>>((const _Float16 *)logits, C, b, labels, label_bytes, h, pred,
-                                                                                  pred_cap, flags);
-  else if (C % 4 == 0 && ((uintptr_t)logits & 15) == 0)
-    eval_confusion_kernel<float, true><<<grid, 256, 0, (hipStream_t)stream>>>((const float *)logits, C, b, labels, label_bytes, h, pred,
-                                                                              pred_cap, flags);
-  else
-    eval_confusion_kernel<float, false><<<grid, 256, 0, (hipStream_t)stream>>>((const float *)logits, C, b, labels, label_bytes, h, pred,
-                                                                               pred_cap, flags);
-  TS_CHECK_LAUNCH("ts_eval_confusion");
-  return TS_OK;
+  return et_launch_confusion("ts_eval_confusion", logits, half, C, b, labels, label_bytes, hist, pred, pred_cap, nullptr, flags,
+                             (hipStream_t)stream);
 }
 
 extern "C" int ts_eval_votes(const void *logits, int32_t half, int32_t C, int64_t n_vox, const int64_t *counts, const int32_t *scene_flags,
                              int32_t n_scenes, const int64_t *inv, const int32_t *rows, const int64_t *kept, int64_t n_pts,
                              const int64_t *num_points, const int64_t *num_points_ms, void *label, int32_t label_bytes, float *sums,
                              float *top3, int64_t cap, int64_t *n_out, int32_t *flags, ts_stream_t stream) {
-  const int rc = et_check_batch("ts_eval_votes", logits, C, n_vox, counts, scene_flags, n_scenes, inv, rows, kept, n_pts, num_points, flags);
+  const int rc = et_check_batch("ts_eval_votes", logits, C, n_vox, counts, scene_flags, n_scenes, inv, rows, kept, nullptr, n_pts, num_points,
+                                flags);
   if (rc != TS_OK) return rc;
-  TS_REQUIRE(cap >= 0 && n_out && (cap == 0 || label) && (label_bytes == 1 || label_bytes == 4) && (!top3 || C >= 3), TS_ERR_INVALID_ARGUMENT,
-             "ts_eval_votes: bad arguments (labels of 1 or 4 bytes; the three largest sums need 3 classes)");
-  TS_REQUIRE(label_bytes == 1 || ((uintptr_t)label & 3) == 0, TS_ERR_INVALID_ARGUMENT, "ts_eval_votes: unaligned label buffer");
-  const EtBatch b = {(const long long *)counts, scene_flags, n_scenes, (const long long *)inv, rows, (const long long *)kept,
+  const EtBatch b = {(const long long *)counts, scene_flags, n_scenes, (const long long *)inv, rows, (const long long *)kept, nullptr,
                      n_vox, n_pts, 0, (const long long *)num_points, (const long long *)num_points_ms};
-  const unsigned grid = (unsigned)std::max<int64_t>(ts_cdiv(cap, 256), 1);
-  TS_REQUIRE(ts_cdiv(cap, 256) < (int64_t)1 << 31, TS_ERR_INVALID_ARGUMENT, "ts_eval_votes: too many rows");
-  if (half)
-    eval_votes_kernel<_Float16, false><<<grid, 256, 0, (hipStream_t)stream>>>((const _Float16 *)logits, C, b, label, label_bytes, sums, top3, cap,
-                                                                              (long long *)n_out, flags);
-  else if (C % 4 == 0 && ((uintptr_t)logits & 15) == 0 && (!sums || ((uintptr_t)sums & 15) == 0))
-    eval_votes_kernel<float, true><<<grid, 256, 0, (hipStream_t)stream>>>((const float *)logits, C, b, label, label_bytes, sums, top3, cap,
-                                                                          (long long *)n_out, flags);
-  else
-    eval_votes_kernel<float, false><<<grid, 256, 0, (hipStream_t)stream>>>((const float *)logits, C, b, label, label_bytes, sums, top3, cap,
-                                                                           (long long *)n_out, flags);
-  TS_CHECK_LAUNCH("ts_eval_votes");
-  return TS_OK;
+  return et_launch_votes("ts_eval_votes", logits, half, C, b, label, label_bytes, sums, top3, cap, n_out, flags, (hipStream_t)stream);
+}
+
+// The _rows forms: the point's logits row comes with the point (grows), the labels are aligned with the points (n_lab = n_pts,
+// cnt_l = cnt_p in et_layout, so bit 3 cannot rise), no mask and no multi-scan counts.
+extern "C" int ts_eval_confusion_rows(const void *logits, int32_t half, int32_t C, int64_t n_vox, const int64_t *counts,
+                                      const int32_t *scene_flags, int32_t n_scenes, const int64_t *grows, int64_t n_pts,
+                                      const void *labels, int32_t label_bytes, const int64_t *num_points, int64_t *hist, int32_t *pred,
+                                      int64_t pred_cap, int64_t *m_out, int32_t *flags, ts_stream_t stream) {
+  const int rc = et_check_batch("ts_eval_confusion_rows", logits, C, n_vox, counts, scene_flags, n_scenes, nullptr, nullptr, nullptr, grows,
+                                n_pts, num_points, flags);
+  if (rc != TS_OK) return rc;
+  TS_REQUIRE(hist && (n_pts == 0 || (labels && grows)) && (label_bytes == 1 || label_bytes == 4 || label_bytes == 8) && pred_cap >= 0,
+             TS_ERR_INVALID_ARGUMENT, "ts_eval_confusion_rows: bad arguments (labels of 1, 4 or 8 bytes)");
+  const EtBatch b = {(const long long *)counts, scene_flags, n_scenes, nullptr, nullptr, nullptr, (const long long *)grows,
+                     n_vox, n_pts, n_pts, (const long long *)num_points, nullptr};
+  return et_launch_confusion("ts_eval_confusion_rows", logits, half, C, b, labels, label_bytes, hist, pred, pred_cap, m_out, flags,
+                             (hipStream_t)stream);
+}
+
+extern "C" int ts_eval_votes_rows(const void *logits, int32_t half, int32_t C, int64_t n_vox, const int64_t *counts,
+                                  const int32_t *scene_flags, int32_t n_scenes, const int64_t *grows, int64_t n_pts,
+                                  const int64_t *num_points, void *label, int32_t label_bytes, float *sums, float *top3, int64_t cap,
+                                  int64_t *n_out, int32_t *flags, ts_stream_t stream) {
+  const int rc = et_check_batch("ts_eval_votes_rows", logits, C, n_vox, counts, scene_flags, n_scenes, nullptr, nullptr, nullptr, grows,
+                                n_pts, num_points, flags);
+  if (rc != TS_OK) return rc;
+  TS_REQUIRE(n_pts == 0 || grows, TS_ERR_INVALID_ARGUMENT, "ts_eval_votes_rows: null pointer");
+  const EtBatch b = {(const long long *)counts, scene_flags, n_scenes, nullptr, nullptr, nullptr, (const long long *)grows,
+                     n_vox, n_pts, 0, (const long long *)num_points, nullptr};
+  return et_launch_votes("ts_eval_votes_rows", logits, half, C, b, label, label_bytes, sums, top3, cap, n_out, flags, (hipStream_t)stream);
 }

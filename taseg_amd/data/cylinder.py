@@ -21,8 +21,13 @@ One host read per batch: the per-sample voxel counts, their total and the error 
 there) raise ValueError at that read.
 
 Not built: the `augmented_*` / `flag*` keys (`get_single_sample` never produces them; the collate functions only pass them on), the
-nuScenes and Waymo dataset files (the same stage; rows of 5 columns are covered), `device_tail=` for this model.  PolarMix /
-LaserMix clouds (data/mix.py `polarmix_points` / `lasermix_points`) are device clouds that can be fed in as `points`.
+nuScenes and Waymo dataset files (the same stage; rows of 5 columns are covered).  PolarMix / LaserMix clouds (data/mix.py
+`polarmix_points` / `lasermix_points`) are device clouds that can be fed in as `points`.
+
+Both batches feed the evaluation on the device as they are: `pcseg.eval.evaluate(model, batches, num_class, on_device=True)` over
+`build_cylinder_batch`'s (validation, predictions=True) and, with tta_votes=V, over `build_cylinder_tta_batch`'s - the votes of one
+scan as the V scenes of a batch, equal point counts, which is what `DeviceEvalTail.run_points` sums.  Every point's cell is a voxel
+of the batch here, so the tail's "no voxel row" flag cannot rise on them.
 """
 from dataclasses import dataclass
 from typing import Dict, List, Sequence, Tuple

@@ -21,6 +21,10 @@ Reproduced as the reference has them (README "Cylinder_TS"):
 * `self.name` is "RPV_Cylinder";
 * `forward_ensemble` (ensemble=True) fails in the evaluation branch at the first scene (`out_batch_i_logits` is only bound on the
   other branch, :576-586).
+
+`forward(batch_dict, device_tail=tail)` (evaluation mode; pcseg.eval.evaluate(on_device=True)) hands the evaluation branch to
+minkunet.DeviceEvalTail.run_points: one batch-wide hash lookup in place of the per-scene queries, the confusion matrix / the vote
+sums on the device.  Without a tail the branch is the reference's, host dictionary and all; in training mode a tail is ignored.
 """
 import torch
 from torch import nn
@@ -204,7 +208,7 @@ class Cylinder_TS(BaseSegmentor):
     def get_training_loss(self, outputs, voxel_label, batch_dict):
         return self.criterion_losses(outputs, voxel_label, xyz=batch_dict["voxel_coord"][:, :3].float(), offset=batch_dict["offset"])
 
-    def forward(self, batch_dict, ensemble=False):
+    def forward(self, batch_dict, ensemble=False, device_tail=None):
         point_feature = self.PPmodel(batch_dict["point_feature"])
         ret = voxelize(PointTensor(point_feature, batch_dict["point_coord"].float()))
         ret.F = self.fea_compression(ret.F)
@@ -241,6 +245,9 @@ class Cylinder_TS(BaseSegmentor):
                 ret_dict, disp_dict, tb_dict = {"loss": loss}, {"loss": loss.item()}, {"loss": loss.item()}
             return ret_dict, tb_dict, disp_dict
 
+        if device_tail is not None:       # evaluation on the device (minkunet.DeviceEvalTail.run_points): no logits cross to the host
+            return device_tail.run_points(logits, up0e.C, batch_dict["point_coord"], batch_dict["point_label"], batch_dict["num_points"],
+                                          batch_dict["name"])
         all_labels = batch_dict["point_label"]
         point_predict, point_labels, point_predict_logits = [], [], []
         for idx in range(int(batch_dict["point_coord"][:, -1].max() + 1)):

@@ -713,9 +713,11 @@ class PendingLabels:
 
 
 class DeviceEvalTail:
-    """Where `model(batch, device_tail=tail)` leaves an evaluation batch instead of un-voxelising it to the host - all five
-    segmentors (MinkUNet, MinkUNetMs, MinkUNetMsMm, MinkUNetMsMmNus, MinkUNetMsKd) take it
-    (csrc/evaltail.hip: ts_scene_counts + one launch, three more where a point_mask has to be compacted):
+    """Where `model(batch, device_tail=tail)` leaves an evaluation batch instead of un-voxelising it to the host - all six
+    segmentors take it: MinkUNet, MinkUNetMs, MinkUNetMsMm, MinkUNetMsMmNus, MinkUNetMsKd through `run` (logits rows grouped by scene, a
+    per-scene inverse map; csrc/evaltail.hip: ts_scene_counts + one launch, three more where a point_mask has to be compacted) and
+    Cylinder_TS through `run_points` (rows in ascending-hash order over the batch, found by one batch-wide hash lookup of the points'
+    cells; ts_scene_counts + one launch):
 
     votes == 0 (validation)  every scene is a scan: additions to `hist`, the resident [num_class, num_class] int64 confusion matrix
                              (R/train.py:35-52 fast_hist before its crop).  Nothing leaves the device until `read()` - unless
@@ -759,6 +761,8 @@ class DeviceEvalTail:
             raise IndexError("predictions and labels of a scan differ in length (labels per scene / num_points / kept points)")
         if flags & 16:
             raise ValueError("votes must cover the same points (one scan per TTA batch)")
+        if flags & 64:
+            raise IndexError("a point's cell has no voxel row (the hash lookup of its coordinates found none)")
 
     def _payload(self, classes, written):
         """classes (int32 / uint8, the first `written` rows - a device scalar - are valid) as the label payload: through the remap
@@ -804,21 +808,55 @@ class DeviceEvalTail:
             got = B.eval_confusion(out, vox_batch, pts_batch, invs.F, all_labels.F.reshape(-1), all_labels.C[:, -1], num_points, self.hist,
                                    self.flags, point_mask=mask, num_points_ms=num_points_ms, want_pred=self.predictions,
                                    want_counts=self.predictions)
-            if not self.predictions:
-                return self
-            pred, m = got
-            label, zero = self._payload(pred, m.sum())
-            meta = torch.cat([self.flags.long(), zero, m])
-            event, h = self._to_host(out.device, {"pred_meta": meta, "pred_label": label})
-            return PendingLabels(event, h["pred_meta"], h["pred_label"], names, self.nuscenes, (meta, label), self.lut is not None)
+            return self._labels_to_host(out.device, got, names) if self.predictions else self
         if n_scenes != self.votes:
             raise ValueError(f"TTA batch holds {n_scenes} votes, {self.votes} expected (one scan per batch, collate_batch_tta)")
         got = B.eval_votes(out, vox_batch, pts_batch, invs.F, num_points, self.flags, point_mask=mask, num_points_ms=num_points_ms,
                            label_bytes=1 if self.nuscenes else 4, want_sums=self.scores == "all", want_top3=self.scores == "top3")
+        return self._votes_to_host(out.device, got, names)
+
+    def run_points(self, logits, voxel_coords, point_coord, point_label, num_points, names):
+        """`run` for a model whose logits rows are in no per-scene order and whose points find their row through the hash of their
+        cell (Cylinder_TS, cylinder_ts.py:244-260): logits [n_vox, C] with their int32 coordinates voxel_coords [n_vox, 4], point_coord
+        [n_pts, 4] (x, y, z, batch; grouped by scene), point_label [n_pts] aligned with the points, num_points per scene.  ONE
+        batch-wide lookup - a hash of the points' cells, a hash of the voxels', one query - names every point's logits row (the hash
+        covers the batch column, so it is the row the reference's per-scene query finds), then ts_scene_counts + one launch
+        (ts_eval_confusion_rows / ts_eval_votes_rows).  Returns what `run` returns.  One stated difference from the host path: a cell
+        without a voxel row (the query's -1, with which the reference silently reads the scene's LAST row) raises IndexError at the
+        read - batches of data.cylinder.build_cylinder_batch cannot produce one."""
+        B.L.require_device(logits, voxel_coords, point_coord, point_label)
+        if logits.shape[1] != self.num_class:
+            raise ValueError(f"the model has {logits.shape[1]} classes, the evaluation {self.num_class}")
+        self.n_scenes = n_scenes = len(names) if names is not None else int(torch.as_tensor(num_points).numel())
+        cells = point_coord.to(voxel_coords)
+        rows = spF.sphashquery(spF.sphash(cells), spF.sphash(voxel_coords))
+        pts_batch = cells[:, -1]
+        if not self.votes:
+            labels = point_label.reshape(-1)
+            labels = labels if labels.dtype in (torch.uint8, torch.int32, torch.int64) else labels.long()
+            got = B.eval_confusion_rows(logits, rows, pts_batch, labels, num_points, self.hist, self.flags, want_pred=self.predictions,
+                                        want_counts=self.predictions)
+            return self._labels_to_host(logits.device, got, names) if self.predictions else self
+        if n_scenes != self.votes:
+            raise ValueError(f"TTA batch holds {n_scenes} votes, {self.votes} expected (one scan per batch, collate_batch_tta)")
+        got = B.eval_votes_rows(logits, rows, pts_batch, num_points, self.flags, label_bytes=1 if self.nuscenes else 4,
+                                want_sums=self.scores == "all", want_top3=self.scores == "top3")
+        return self._votes_to_host(logits.device, got, names)
+
+    def _labels_to_host(self, device, got, names):
+        """validation with predictions=True: (pred, m) of the confusion call on their way to the host as a PendingLabels"""
+        pred, m = got
+        label, zero = self._payload(pred, m.sum())
+        meta = torch.cat([self.flags.long(), zero, m])
+        event, h = self._to_host(device, {"pred_meta": meta, "pred_label": label})
+        return PendingLabels(event, h["pred_meta"], h["pred_label"], names, self.nuscenes, (meta, label), self.lut is not None)
+
+    def _votes_to_host(self, device, got, names):
+        """TTA: the dictionary of the votes call on its way to the host as a PendingVotes"""
         scores = got["sums"] if self.scores == "all" else got["top3"]
         label, zero = self._payload(got["label"], got["n"]) if self.lut is not None else (got["label"], got["n"].new_zeros(1))
         meta = torch.cat([self.flags.long(), zero, got["n"]])
-        event, h = self._to_host(out.device, {"vote_meta": meta, "vote_label": label, "vote_scores": scores})
+        event, h = self._to_host(device, {"vote_meta": meta, "vote_label": label, "vote_scores": scores})
         return PendingVotes(event, h["vote_meta"], h["vote_label"], h["vote_scores"], 0 if scores is None else scores.shape[1], names,
                             self.nuscenes, (meta, got, label, scores), self.lut is not None)
 
