@@ -480,6 +480,42 @@ int ts_voxelize_max_forward(const void *feat, const int32_t *idx, int64_t n, int
 int ts_voxelize_max_backward(const void *grad_out, const int32_t *idx, const int32_t *arg, int64_t n, int32_t c, int64_t m,
                              int32_t half, void *grad_feat, ts_stream_t stream);
 
+/* Mean-voxelisation of point rows with a fixed summation order (SPVCNN: fusion/spvcnn/utils.py:41-65 `point_to_voxel`).
+ * feat [n, c], idx [n] int32 = voxel of every row (negative or >= m: the row takes no part), m voxels.
+ *   ts_point_groups   the grouping one map needs, whatever is voxelised through it: offsets [m + 1], entries [n] int32 - the rows of
+ *                     voxel v are entries[offsets[v] .. offsets[v + 1]) in ascending row order (the stable sort behind ts_devox_csr).
+ *                     ws >= ts_point_groups_workspace_bytes(n)
+ *   forward           out [m, c]: with cnt = the voxel's number of grouped rows, every term is feat[row] / (float)cnt in float32 (a
+ *                     half row widened first).  The voxel's run is cut into pieces of P = ts_voxelize_mean_piece_rows() consecutive
+ *                     rows counted from its first row; each piece is summed in ascending order, the piece sums are then added in
+ *                     ascending piece order; a voxel of at most P rows is one sequential sum; a voxel without rows is a zero row; a
+ *                     half result is rounded once at the store.  No atomics, no fill, every element written once, run-to-run
+ *                     identical.  ws >= ts_voxelize_mean_workspace_bytes(n, c) (the full pieces' float32 sums)
+ *   backward          grad_feat [n, c] = grad_out[idx[i]] / cnt, zeros for a row that took no part - a gather
+ * half != 0: IEEE half rows (c % 8 == 0), else float (c % 4 == 0); c <= 1024; 16-byte aligned rows.
+ * ts_voxelize_mean_set_piece_rows (16, 32 or 64) exists for the timing tool's comparison only: P is part of the rule. */
+int32_t ts_voxelize_mean_piece_rows(void);
+int ts_voxelize_mean_set_piece_rows(int32_t rows);
+size_t ts_point_groups_workspace_bytes(int64_t n);
+int ts_point_groups(const int32_t *idx, int64_t n, int64_t m, int32_t *offsets, int32_t *entries, void *ws, size_t ws_bytes,
+                    ts_stream_t stream);
+size_t ts_voxelize_mean_workspace_bytes(int64_t n, int32_t c);
+int ts_voxelize_mean_forward(const void *feat, const int32_t *idx, const int32_t *offsets, const int32_t *entries, int64_t n,
+                             int32_t c, int64_t m, int32_t half, void *out, void *ws, size_t ws_bytes, ts_stream_t stream);
+int ts_voxelize_mean_backward(const void *grad_out, const int32_t *idx, const int32_t *offsets, int64_t n, int32_t c, int64_t m,
+                              int32_t half, void *grad_feat, ts_stream_t stream);
+
+/* The tail of SPVCNN's point branch (spvcnn.py:417-444) on rows [n, c] in one pass:
+ *   out[i, :] = sum_k weight[i, k] vox[idx[i, k], :] + relu((y[i, :] - mean) invstd gamma + beta)
+ * idx / weight [n, 8] = a ts_trilinear_map result over the m rows of vox; the sum runs over k = 0 .. 7 in k order in float32, a
+ * corner with idx < 0 (or >= m) or weight 0 adds nothing (the arithmetic of ts_devoxelize_forward).  mask (optional, uint8
+ * [n * c / 4], half: [n * c / 8]) gets the sign bits of the BatchNorm term - not of out - in the layout of ts_bn_act_forward, for
+ * ts_bn_act_train_backward; mask == NULL with running statistics is the evaluation form.  half != 0: y, vox and out are IEEE half
+ * (c % 8 == 0), else float (c % 4 == 0); c <= 1024; float arithmetic, one rounding at the store; 16-byte aligned rows and maps. */
+int ts_point_tail_forward(const void *y, const void *vox, const int32_t *idx, const float *weight, const float *mean,
+                          const float *invstd, const float *gamma, const float *beta, int64_t n, int32_t c, int64_t m, int32_t half,
+                          void *out, uint8_t *mask, ts_stream_t stream);
+
 /* The gate of Cylinder_TS's ReconBlock (cylinder_ts.py:368-384) on rows [n, c]: out = x * (sigmoid(u) + sigmoid(v) + sigmoid(w)),
  * one pass; the backward forms grad_x, grad_u, grad_v, grad_w from grad_out and the four inputs in one pass.  float arithmetic;
  * half != 0: IEEE half storage (c % 8 == 0), else float (c % 4 == 0); 16-byte aligned pointers. */

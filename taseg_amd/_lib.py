@@ -94,6 +94,14 @@ SIGNATURES = {
     "ts_voxelize_max_workspace_bytes": (_sz, [_i64, _i64]),
     "ts_voxelize_max_forward": (_i32, [_vp, _vp, _i64, _i32, _i64, _i32, _vp, _vp, _vp, _sz, _vp]),
     "ts_voxelize_max_backward": (_i32, [_vp, _vp, _vp, _i64, _i32, _i64, _i32, _vp, _vp]),
+    "ts_voxelize_mean_piece_rows": (_i32, []),
+    "ts_voxelize_mean_set_piece_rows": (_i32, [_i32]),
+    "ts_point_groups_workspace_bytes": (_sz, [_i64]),
+    "ts_point_groups": (_i32, [_vp, _i64, _i64, _vp, _vp, _vp, _sz, _vp]),
+    "ts_voxelize_mean_workspace_bytes": (_sz, [_i64, _i32]),
+    "ts_voxelize_mean_forward": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i64, _i32, _vp, _vp, _sz, _vp]),
+    "ts_voxelize_mean_backward": (_i32, [_vp, _vp, _vp, _i64, _i32, _i64, _i32, _vp, _vp]),
+    "ts_point_tail_forward": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i64, _i32, _vp, _vp, _vp]),
     "ts_sigmoid3_gate_forward": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp]),
     "ts_sigmoid3_gate_backward": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "ts_conv3x3c32_packed_bytes": (_sz, []),

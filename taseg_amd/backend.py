@@ -23,6 +23,7 @@ __all__ = [
     "fuse_scan", "fuse_scans", "fuse_sweeps", "project_fov", "voxel_coords", "sparse_quantize", "set_conv_impl", "image_gather_forward", "image_gather_backward", "image_gather_rows_forward", "image_gather_rows_backward", "avgpool3s2_rows_forward", "avgpool3s2_rows_backward", "conv3x3c32_pack", "conv3x3c32_rows", "conv3x3c32_wgrad", "conv3x3_rows_takes", "conv3x3_rows_pack", "conv3x3_rows", "conv3x3_wgrad", "conv1x1c32_pack", "conv1x1c32_rows", "conv1x1c32_wgrad", "shuffle_cat_rows_takes", "shuffle_cat_rows_forward", "shuffle_cat_rows_backward",
     "eval_confusion", "eval_votes", "eval_confusion_rows", "eval_votes_rows",
     "voxelize_max_forward", "voxelize_max_backward", "sigmoid3_gate_forward", "sigmoid3_gate_backward",
+    "point_groups", "voxelize_mean_piece_rows", "voxelize_mean_forward", "voxelize_mean_backward", "point_tail_forward",
 ]
 
 
@@ -2186,4 +2187,88 @@ def sigmoid3_gate_backward(grad_out, x, u, v, w):
 def _same_rows(t, like, who):
     if t.dtype != like.dtype or t.shape != like.shape:
         raise ValueError(f"{who}: every operand must have the dtype and shape of x ({like.dtype}, {tuple(like.shape)})")
+    return t.contiguous()
+
+
+# --------------------------------------------------------------------------- SPVCNN (csrc/spvcnn.hip)
+def point_groups(idx, m):
+    """(offsets [m + 1], entries [n]) int32: the rows i of a point -> voxel map idx [n] grouped by voxel, ascending inside a voxel;
+    rows with idx < 0 or idx >= m belong to no voxel.  One grouping serves every voxelize_mean_* call through that map."""
+    L.require_device(idx)
+    idx = _i32(idx, "idx")
+    if idx.dim() != 1:
+        raise ValueError("point_groups: idx must hold one voxel per row")
+    n, m = idx.shape[0], int(m)
+    lib = L.load()
+    ws = L.workspace(lib.ts_point_groups_workspace_bytes(n), idx.device)
+    off = torch.empty(m + 1, dtype=torch.int32, device=idx.device)
+    ent = torch.empty(max(n, 1), dtype=torch.int32, device=idx.device)
+    L.check(lib.ts_point_groups(L.ptr(idx), n, m, L.ptr(off), L.ptr(ent), L.ptr(ws), ws.numel(), L.stream()), "ts_point_groups")
+    return off, ent
+
+
+def voxelize_mean_piece_rows():
+    """P of the summation rule of voxelize_mean_forward (include/taseg_hip.h)"""
+    return int(L.load().ts_voxelize_mean_piece_rows())
+
+
+def voxelize_mean_forward(feat, idx, groups):
+    """out [m, c]: the mean of the rows of every voxel of the map idx [n] with its grouping `groups` = point_groups(idx, m), summed in
+    the fixed order include/taseg_hip.h states (no atomics: the same bits every run); a voxel without rows is a zero row.  float32
+    with c % 4 == 0 or float16 with c % 8 == 0 - anything else raises BackendError."""
+    off, ent = groups
+    L.require_device(feat, idx, off, ent)
+    feat, half = _rows_f32_f16(feat, "feat")
+    idx, off, ent = _i32(idx, "idx"), _i32(off, "offsets"), _i32(ent, "entries")
+    n, c = feat.shape
+    m = off.shape[0] - 1
+    if idx.shape != (n,) or ent.shape[0] < n:
+        raise ValueError("voxelize_mean_forward: idx and the grouping must hold one entry per row")
+    lib = L.load()
+    out = torch.empty((m, c), dtype=feat.dtype, device=feat.device)
+    ws = L.workspace(lib.ts_voxelize_mean_workspace_bytes(n, c), feat.device)
+    L.check(lib.ts_voxelize_mean_forward(L.ptr(feat), L.ptr(idx), L.ptr(off), L.ptr(ent), n, c, m, half, L.ptr(out), L.ptr(ws),
+                                         ws.numel(), L.stream()), "ts_voxelize_mean_forward")
+    return out
+
+
+def voxelize_mean_backward(grad_out, idx, groups):
+    """grad_feat [n, c] = grad_out[idx[i]] / (rows of that voxel), zeros for a row that took no part (a gather)."""
+    off = groups[0]
+    L.require_device(grad_out, idx, off)
+    grad_out, half = _rows_f32_f16(grad_out, "grad_out")
+    idx, off = _i32(idx, "idx"), _i32(off, "offsets")
+    m, c = grad_out.shape
+    n = idx.shape[0]
+    if off.shape[0] != m + 1:
+        raise ValueError("voxelize_mean_backward: the grouping was built for another voxel count")
+    out = torch.empty((n, c), dtype=grad_out.dtype, device=grad_out.device)
+    L.check(L.load().ts_voxelize_mean_backward(L.ptr(grad_out), L.ptr(idx), L.ptr(off), n, c, m, half, L.ptr(out), L.stream()),
+            "ts_voxelize_mean_backward")
+    return out
+
+
+def point_tail_forward(y, vox, idx, weight, mean, invstd, gamma, beta, want_mask=False):
+    """(out [n, c], mask | None): out = sum_k weight[:, k] vox[idx[:, k]] + relu((y - mean) invstd gamma + beta) in one pass
+    (ts_point_tail_forward); mask = the sign bits of the BatchNorm term in ts_bn_act_forward's layout, for ts_bn_act_train_backward.
+    y and vox of one dtype: float32 (c % 4 == 0) or float16 (c % 8 == 0)."""
+    L.require_device(y, vox, idx, weight, mean, invstd, gamma, beta)
+    y, half = _rows_f32_f16(y, "y")
+    vox = _same_cols(vox, y, "point_tail_forward")
+    idx, weight = _i32(idx, "idx"), _f32(weight, "weight")
+    mean, invstd, gamma, beta = (_f32(t, "statistics") for t in (mean, invstd, gamma, beta))
+    n, c = y.shape
+    if idx.shape != (n, 8) or weight.shape != (n, 8) or any(t.shape != (c,) for t in (mean, invstd, gamma, beta)):
+        raise ValueError("point_tail_forward: maps [n, 8] and per-channel vectors [c] must match y [n, c]")
+    out = torch.empty_like(y)
+    mask = torch.empty(n * (c // (8 if half else 4)), dtype=torch.uint8, device=y.device) if want_mask else None
+    L.check(L.load().ts_point_tail_forward(L.ptr(y), L.ptr(vox), L.ptr(idx), L.ptr(weight), L.ptr(mean), L.ptr(invstd), L.ptr(gamma),
+                                           L.ptr(beta), n, c, vox.shape[0], half, L.ptr(out), L.ptr(mask), L.stream()),
+            "ts_point_tail_forward")
+    return out, mask
+
+
+def _same_cols(t, like, who):
+    if t.dtype != like.dtype or t.dim() != 2 or t.shape[1] != like.shape[1]:
+        raise ValueError(f"{who}: vox must have the dtype and width of y ({like.dtype}, {like.shape[1]})")
     return t.contiguous()

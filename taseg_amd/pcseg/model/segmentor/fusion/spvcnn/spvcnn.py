@@ -1,0 +1,144 @@
+"""SPVCNN segmentor (reference pcseg/model/segmentor/fusion/spvcnn/spvcnn.py:189-484): MinkUNet plus a point branch.
+
+Module tree, attribute names and therefore every state_dict key, their order and shapes are the reference's for both blocks
+(`stem.0.kernel` .. `up4.1.0.net.3.kernel`, `classifier.0.weight`, `point_transforms.0.0.weight`, `point_transforms.0.1.running_mean`
+...), so reference checkpoints load here and vice versa.  Stem, stages, blocks, index plan, losses and the evaluation tail are
+`minkunet.py`'s; what this file adds is the point branch:
+
+  point_to_voxel   three times per pass (strides 1, 16, 4): `spvoxelize_mean` on the groupings the index plan carries - the voxel of a
+                   point is column 0 of the trilinear map the plan builds anyway (utils.py), the sum has a fixed order
+                   (ts_voxelize_mean_forward) where `spvoxelize` adds with float atomics;
+  point_transforms z_k.F = devoxelize(x.F) + ReLU(BN(Linear(z_{k-1}.F))) three times per pass: the Linear (bias kept) as the pair GEMM
+                   of the 1x1x1 convolutions plus a bias add where both widths are multiples of 32, `torch.nn.functional.linear`
+                   elsewhere; then ONE node on ts_point_tail_forward (`functional.point_tail`).
+
+The stage programs of `minkunet.py` run the whole U-Net in one call and cannot take the point branch between the stages: this model
+always runs module by module.
+
+Reproduced from the reference, not repaired: `forward_ensemble` passes `ensemble=True` to `forward`, which has no such parameter
+(spvcnn.py:483-484: TypeError); with MULTI_SCALE other than 'concat' no `classifier` is built and `forward` fails on the attribute
+(:330-333, :449).
+"""
+import torch
+from torch import nn
+
+from taseg_amd import backend as B
+from taseg_amd import torchsparse
+from taseg_amd.torchsparse import PointTensor, SparseTensor
+from taseg_amd.torchsparse import nn as spnn
+from taseg_amd.torchsparse.nn import functional as spF
+from ...voxel.minkunet.minkunet import MinkUNetBackbone, unvoxelise_predictions
+from ...voxel.minkunet.utils import voxelize_index
+from .utils import point_to_voxel, voxel_to_point
+
+__all__ = ["SPVCNN"]
+
+_STRIDES = ((1, 1, 1), (16, 16, 16), (4, 4, 4))        # where the point branch meets the U-Net: x0 / x4 / y2 (spvcnn.py:408-443)
+
+
+class SPVCNN(MinkUNetBackbone):
+    def __init__(self, model_cfgs, num_class: int):
+        super().__init__(model_cfgs, num_class)        # stem .. up4, classifier, dropout, losses: spvcnn.py:212-326 == minkunet.py
+        self.name = "spvcnn"
+        cr = model_cfgs.get("cr", 1.0)
+        cs = [int(cr * x) for x in model_cfgs.get("PLANES", [32, 32, 64, 128, 256, 256, 128, 96, 96])]
+        exp = self.block.expansion
+        if_dist = model_cfgs.IF_DIST
+        self.multi_scale = model_cfgs.get("MULTI_SCALE", "concat")
+        if self.multi_scale != "concat":
+            del self.classifier                        # (:330-333: built for 'concat' only; forward then fails as the reference's does)
+
+        def transform(inc, outc):
+            return nn.Sequential(nn.Linear(inc, outc), nn.SyncBatchNorm(outc) if if_dist else nn.BatchNorm1d(outc), nn.ReLU(True))
+
+        self.point_transforms = nn.ModuleList([transform(cs[0], cs[4] * exp), transform(cs[4] * exp, cs[6] * exp),
+                                               transform(cs[6] * exp, cs[8] * exp)])
+        self.weight_initialization()
+
+    def prepare(self, batch_dict):
+        """the index plan of MinkUNet plus, per stride the point branch voxelises at, (idx_query, counts, grouping) - coordinates
+        only; left under batch_dict['_plan']"""
+        with torch.no_grad():
+            z = PointTensor(None, batch_dict["lidar"].C.float())
+            coords, vox_idx, vox_counts = voxelize_index(z, self.pres, self.vres)              # spvcnn.py:403-405
+            plan = self._index_plan(coords, z.C, backward=self.training, vox_idx=vox_idx, vox_counts=vox_counts)
+            p2v = {}
+            for key in _STRIDES:
+                idx = vox_idx.int() if key == _STRIDES[0] else plan["tri_idx"][key][:, 0].contiguous()
+                offsets, entries = B.point_groups(idx, plan["cmaps"][key].shape[0])
+                p2v[key] = (idx, offsets[1:] - offsets[:-1], (offsets, entries))
+            plan["p2v"] = p2v
+        batch_dict["_plan"] = plan
+        return plan
+
+    def _tail(self, k: int, x: SparseTensor, z: PointTensor) -> PointTensor:
+        """z_k = voxel_to_point(x, z_{k-1}); z_k.F += point_transforms[k](z_{k-1}.F)   (spvcnn.py:417-418, 430-431, 443-444)"""
+        lin, bn = self.point_transforms[k][0], self.point_transforms[k][1]
+        if z.F.is_cuda and z.F.dtype in (torch.float32, torch.float16) and spF._dense_ok(lin.in_features, lin.out_features):
+            # the GEMM of the 1x1x1 convolutions on the identity rulebook, then the bias: 2.0 - 2.6 x ahead of the library's linear,
+            # forward + backward, at the three shapes of cr 1.0 (profiles/spvcnn_step.txt)
+            y = spF._PointwiseConv.apply(z.F, lin.weight.t().contiguous(), spF._identity_rows(z.F.shape[0], z.F.device))
+            y = y + lin.bias.to(y.dtype)
+        else:
+            y = torch.nn.functional.linear(z.F, lin.weight, lin.bias)
+        order = (z.additional_features.get("devox_order") or {}).get(x.s)
+        out = PointTensor(spF.point_tail(y, bn, x.F, z.idx_query[x.s], z.weights[x.s], order), z.C, idx_query=z.idx_query,
+                          weights=z.weights)
+        out.additional_features = z.additional_features
+        return out
+
+    def forward(self, batch_dict, return_logit=False, return_tta=False, defer=False, device_tail=None):
+        x = batch_dict["lidar"]
+        x.F = x.F[:, :self.in_feature_dim]
+        plan = batch_dict.get("_plan") or self.prepare(batch_dict)
+        x0 = SparseTensor(spF.spvoxelize(x.F, plan["vox_idx"], plan["vox_counts"]), plan["coords"], 1)     # initial_voxelize
+        x0.cmaps, x0.kmaps = plan["cmaps"], plan["kmaps"]
+        z = PointTensor(x.F, plan["point_coords"], idx_query=plan["tri_idx"], weights=plan["tri_w"])
+        cache = z.additional_features
+        cache["devox_order"], cache["groups"] = plan["tri_order"], {}
+        for key, (idx, counts, groups) in plan["p2v"].items():
+            cache["idx_query"][key], cache["counts"][key], cache["groups"][key] = idx, counts, groups
+
+        x0 = spnn.conv_bn_act(self.stem[0], self.stem[1], x0, relu=True)
+        x0 = spnn.conv_bn_act(self.stem[3], self.stem[4], x0, relu=True)
+        z0 = voxel_to_point(x0, z, nearest=False)                  # WITH features: here z0.F is read
+
+        x1 = point_to_voxel(x0, z0)
+        x1 = self.stage1(x1)
+        x2 = self.stage2(x1)
+        x3 = self.stage3(x2)
+        x4 = self.stage4(x3)
+
+        z1 = self._tail(0, x4, z0)
+
+        y1 = point_to_voxel(x4, z1)
+        y1.F = torch.nn.functional.dropout(y1.F, self.dropout.p, self.training, False)
+        y1 = self.up1[1](torchsparse.cat([self.up1[0](y1), x3]))
+        y2 = self.up2[1](torchsparse.cat([self.up2[0](y1), x2]))
+
+        z2 = self._tail(1, y2, z1)
+
+        y3 = point_to_voxel(y2, z2)
+        y3.F = torch.nn.functional.dropout(y3.F, self.dropout.p, self.training, False)
+        y3 = self.up3[1](torchsparse.cat([self.up3[0](y3), x1]))
+        y4 = self.up4[1](torchsparse.cat([self.up4[0](y3), x0]))
+
+        z3 = self._tail(2, y4, z2)
+
+        if self.multi_scale == "concat":
+            out = self.classifier(torch.cat([z1.F, z2.F, z3.F], dim=1))
+        else:
+            out = self.classifier(z3.F)
+
+        if self.training:
+            target = batch_dict["targets"].F.long().cuda(non_blocking=True)
+            return self._train_outputs(out, target, batch_dict["lidar"].C[:, :3].float(), batch_dict["offset"])
+
+        if device_tail is not None:       # evaluation on the device (DeviceEvalTail): nothing is un-voxelised to the host
+            return device_tail.run(out, x.C[:, -1], batch_dict["inverse_map"], batch_dict["targets_mapped"], batch_dict["num_points"],
+                                   names=batch_dict["name"])
+        return unvoxelise_predictions(out, x.C[:, -1], batch_dict["inverse_map"], batch_dict["targets_mapped"],
+                                      batch_dict["num_points"], return_logit or return_tta, names=batch_dict["name"], defer=defer)
+
+    def forward_ensemble(self, batch_dict):
+        return self.forward(batch_dict, ensemble=True)

@@ -32,7 +32,7 @@ from ..utils import make_ntuple
 from .utils import get_kernel_offsets
 
 __all__ = ["conv3d", "conv_geometry", "conv_block_ok", "conv_block_eval", "sphash", "sphashquery", "spcount", "spvoxelize", "spdevoxelize", "spdevoxelize_cat", "calc_ti_weights",
-           "spdownsample", "KernelMap", "build_kernel_map", "build_pyramid", "point_linear", "spvoxelize_max", "sigmoid3_gate",
+           "spdownsample", "KernelMap", "build_kernel_map", "build_pyramid", "point_linear", "spvoxelize_max", "sigmoid3_gate", "spvoxelize_mean", "point_tail",
            "gather_rows"]
 
 _fwd = torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
@@ -1164,3 +1164,140 @@ def gather_rows(feats: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
     w8[:, 0] = inside.float()
     with _no_autocast():
         return spdevoxelize(feats, idx8, w8, B.devox_csr(idx8, w8, m))
+
+
+# ------------------------------------------------------------------------------ SPVCNN pieces (csrc/spvcnn.hip)
+# Private switches, as above: False selects what the kernel replaces - ts_voxelize_forward's float atomics / the module chain -
+# for tools/time_spvcnn_step.py's baseline.  Nothing else reads them.
+_MEAN_KERNEL = True
+_POINT_TAIL_KERNEL = True
+
+
+def _rows_dtype(half: bool, c: int):
+    """storage of rows handed to the csrc/spvcnn.hip kernels: half where the result is half anyway and the width takes 16-byte
+    pieces of 8 halves, else float32"""
+    return torch.float16 if (half and c % 8 == 0) else torch.float32
+
+
+class _VoxelizeMean(Function):
+    """mean of the rows of every voxel in a fixed summation order (ts_voxelize_mean_forward); the adjoint is a gather
+    (ts_voxelize_mean_backward).  Half result under autocast / for half rows, as `spvoxelize`; float32 sums either way."""
+
+    @staticmethod
+    def forward(ctx, feats, idx, groups):
+        half = _amp_half(feats)
+        dt = _rows_dtype(half, feats.shape[1])
+        out = B.voxelize_mean_forward(feats.contiguous().to(dt), idx, groups)
+        ctx.saved = (idx, groups, feats.dtype, dt)
+        return out.half() if half else out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        idx, groups, dtype, dt = ctx.saved
+        return B.voxelize_mean_backward(grad_out.contiguous().to(dt), idx, groups).to(dtype), None, None
+
+
+def spvoxelize_mean(feats: torch.Tensor, idx: torch.Tensor, num: int, groups=None) -> torch.Tensor:
+    """`spvoxelize(feats, idx, spcount(idx, num))` - the mean of the rows of each of `num` voxels, zeros for a voxel without rows,
+    rows with idx < 0 or idx >= num taking no part - with the summation order of include/taseg_hip.h (ts_voxelize_mean_forward)
+    instead of float atomics: the same bits every run.  groups = backend.point_groups(idx, num), built here when absent; one grouping
+    serves every call through that map.  On the host and for double rows: the tensor ops."""
+    num = int(num)
+    if not feats.is_cuda or feats.dtype == torch.float64:
+        keep = (idx >= 0) & (idx < num)
+        at = idx[keep].long()
+        counts = torch.bincount(at, minlength=num).to(feats.dtype)
+        return feats.new_zeros((num, feats.shape[1])).index_add(0, at, feats[keep] / counts[at].unsqueeze(1))
+    idx = idx.int().contiguous()
+    if not _MEAN_KERNEL:
+        idx = torch.where(idx < num, idx, torch.full_like(idx, -1))          # (ts_count takes every idx >= 0 as a voxel)
+        return spvoxelize(feats, idx, spcount(idx, num))
+    if groups is None:
+        groups = B.point_groups(idx, num)
+    with _no_autocast():
+        return _VoxelizeMean.apply(feats, idx, groups)
+
+
+class _PointTail(Function):
+    """devoxelize(vox) + relu(BN_train(y)) as ONE node: batch statistics from ts_bn_sync_stats + ts_bn_finalize (which also moves the
+    running buffers), one launch of ts_point_tail_forward; the gradient of the result goes unchanged to the devoxelisation adjoint the
+    plan's order selects and to ts_bn_act_train_backward with the mask the forward wrote."""
+
+    @staticmethod
+    def forward(ctx, y, vox, weight, bias, running_mean, running_var, nbt, momentum, eps, idx, w, order):
+        from .batchnorm import _bump
+        n, c = y.shape
+        half = y.dtype == torch.float16
+        sfx = "_f16" if half else ""
+        L = B.L
+        lib = L.load()
+        pack = torch.empty(2 * c + 1, dtype=torch.float64, device=y.device)
+        stats = torch.empty((2, c), dtype=torch.float32, device=y.device)        # mean, invstd
+        ws = L.workspace(lib.ts_bn_train_workspace_bytes(c), y.device)
+        L.check(getattr(lib, "ts_bn_sync_stats" + sfx)(L.ptr(y), n, c, L.ptr(pack), L.ptr(ws), ws.numel(), L.stream()),
+                "ts_bn_sync_stats" + sfx)
+        L.check(lib.ts_bn_finalize(L.ptr(pack), None, float(n), c, float(eps), float(momentum), L.ptr(running_mean),
+                                   L.ptr(running_var), L.ptr(stats[0]), L.ptr(stats[1]), L.stream()), "ts_bn_finalize")
+        if nbt is not None:
+            nbt.add_(1)
+        out, mask = B.point_tail_forward(y, vox, idx, w, stats[0], stats[1], weight, bias, want_mask=True)
+        _bump(running_mean, running_var)
+        ctx.save_for_backward(y, weight, stats, mask)
+        ctx.maps, ctx.m = (idx, w, order), vox.shape[0]
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        y, weight, stats, mask = ctx.saved_tensors
+        idx, w, order = ctx.maps
+        n, c = y.shape
+        half = y.dtype == torch.float16
+        g = grad_out.contiguous().to(y.dtype)
+        grad_vox = None
+        if ctx.needs_input_grad[1]:
+            if half and not isinstance(order, tuple):       # (the half adjoints walk an inverse map or a cell plan)
+                grad_vox = B.devoxelize_backward_from(g.float(), 0, c, idx, w, ctx.m, order).half()
+            else:
+                grad_vox = B.devoxelize_backward_from(g, 0, c, idx, w, ctx.m, order)
+        L = B.L
+        lib = L.load()
+        sfx = "_f16" if half else ""
+        grad_y = torch.empty_like(y)
+        gwb = torch.empty((2, c), dtype=torch.float32, device=y.device)
+        ws = L.workspace(lib.ts_bn_train_workspace_bytes(c), y.device)
+        L.check(getattr(lib, "ts_bn_act_train_backward" + sfx)(
+            L.ptr(g), L.ptr(mask), L.ptr(y), L.ptr(stats[0]), L.ptr(stats[1]), L.ptr(weight), n, c, L.ptr(grad_y), None,
+            L.ptr(gwb[0]), L.ptr(gwb[1]), L.ptr(ws), ws.numel(), L.stream()), "ts_bn_act_train_backward" + sfx)
+        return grad_y, grad_vox, gwb[0], gwb[1], None, None, None, None, None, None, None, None
+
+
+def point_tail(y: torch.Tensor, bn, vox_feats: torch.Tensor, idx: torch.Tensor, w: torch.Tensor, order=None) -> torch.Tensor:
+    """spdevoxelize(vox_feats, idx, w, order) + relu(bn(y)) for a BatchNorm1d / SyncBatchNorm module `bn` on point rows y [N, C] -
+    the tail of SPVCNN's point branch (spvcnn.py:417-444, behind the Linear of `point_transforms`).  One launch of
+    ts_point_tail_forward (csrc/spvcnn.hip) where the module trains on local statistics, or evaluates without a graph; the chain of
+    the module, ReLU, `spdevoxelize` and the add where statistics are shared between ranks, where an evaluation-mode pass records a
+    graph (its BatchNorm backward has no kernel here), on the host, and for widths the kernel does not take."""
+    from .batchnorm import fast_path_ok
+    from .modules import _sync_group
+    group = _sync_group(bn)
+    c = y.shape[1] if y.dim() == 2 else 0
+    half = y.is_cuda and (_amp_half(y) or vox_feats.dtype == torch.float16)
+    dt = _rows_dtype(half, c)
+    usable = _POINT_TAIL_KERNEL and group is None and y.is_cuda and y.dim() == 2 and vox_feats.shape[0] > 0 \
+        and y.dtype in (torch.float32, torch.float16) and vox_feats.dtype in (torch.float32, torch.float16) \
+        and bn.affine and bn.track_running_stats and bn.weight.dtype == torch.float32 and y.shape[0] > 0 and c <= 1024 \
+        and c % (8 if dt == torch.float16 else 4) == 0
+    graph = torch.is_grad_enabled() and (y.requires_grad or vox_feats.requires_grad or bn.weight.requires_grad)
+    if usable and bn.training and bn.momentum is not None and y.shape[0] > 1:
+        idx, w = idx.int().contiguous(), w.contiguous().float()
+        with _no_autocast():
+            out = _PointTail.apply(y.contiguous().to(dt), vox_feats.contiguous().to(dt), bn.weight, bn.bias, bn.running_mean,
+                                   bn.running_var, bn.num_batches_tracked, bn.momentum, bn.eps, idx, w, order)
+        return out.half() if half else out
+    if usable and not bn.training and not graph:
+        with _no_autocast():
+            invstd = torch.rsqrt(bn.running_var.float() + bn.eps)
+            out, _ = B.point_tail_forward(y.contiguous().to(dt), vox_feats.contiguous().to(dt), idx.int().contiguous(),
+                                          w.contiguous().float(), bn.running_mean.float(), invstd, bn.weight.detach(), bn.bias.detach())
+        return out.half() if half else out
+    return spdevoxelize(vox_feats, idx, w, order) + torch.relu(bn(y))

@@ -1,0 +1,271 @@
+"""The kernels of csrc/spvcnn.hip on the GPU.
+
+Mean-voxelisation (ts_voxelize_mean_forward / _backward behind backend.voxelize_mean_* and functional.spvoxelize_mean): the float32
+result equals the numpy restatement of the rule (tests/spvcnn_ref.py: pieces of P, ascending order, np.float32 at every step) BIT FOR
+BIT, the half result is that float32 value rounded once, both sit within the bound derived there of the float64 mean (+ 2^-11 |result|
+for half), two calls give the same bits, and the adjoint is exactly grad_out[idx] / cnt.
+
+Point tail (ts_point_tail_forward behind backend.point_tail_forward and functional.point_tail) against float64.  Bar of the value =
+the devoxelisation term of oracle/points64.py (t u S over the t live corners) + the BatchNorm-apply term of
+tests/test_gpu_bn_float64.py (8 u S_bn: elementwise operations only, given statistics; LAMBDA(n, c) u S_y with batch statistics) + one
+rounding of the sum (u (|devox| + |bn|)); a half result adds one rounding to half.  The mask must equal the sign of the float64
+BatchNorm term wherever that term exceeds its own bar in magnitude; with standard-normal y at most 1 % of the elements may sit inside
+it (checked on the reference values).  The gradients of the autograd Function meet the bars the BatchNorm and points tests set for the
+kernels they come from: LAMBDA(n, c) u S for grad_y, grad_gamma, grad_beta (bn_ref64), t u S for the voxel gradient (adjoint64)."""
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+import spvcnn_ref as R  # noqa: E402
+from oracle import points64 as P64  # noqa: E402
+from test_gpu_bn_float64 import EPS, U32, _check, _lam, bn_ref64, running_ref64  # noqa: E402
+
+MEAN_CASES = [(torch.float32, c) for c in (4, 48, 256, 1024)] + [(torch.float16, c) for c in (8, 48, 256)]
+TAIL_CASES = [(torch.float32, c) for c in (4, 32, 48, 256)] + [(torch.float16, c) for c in (8, 32, 256)]
+_ids = lambda case: f"{'half' if case[0] == torch.float16 else 'fp32'}-{case[1]}"  # noqa: E731
+
+
+def _bits(a):
+    a = np.ascontiguousarray(a)
+    return a.view(np.uint16 if a.dtype == np.float16 else np.uint32)
+
+
+# ------------------------------------------------------------------------------------------------------------ mean-voxelisation
+@pytest.mark.parametrize("case", MEAN_CASES, ids=_ids)
+def test_mean_kernels_equal_the_restated_rule(case):
+    from taseg_amd import backend as B
+    dtype, c = case
+    half = dtype == torch.float16
+    piece = B.voxelize_mean_piece_rows()
+    feat, idx, m = R.piece_map(piece, c)
+    if half:
+        feat = feat.astype(np.float16)
+    f, i = torch.from_numpy(feat).cuda(), torch.from_numpy(idx).cuda()
+    groups = B.point_groups(i, m)
+    off, ent = R.groups(idx, m)
+    assert np.array_equal(groups[0].cpu().numpy(), off) and np.array_equal(groups[1].cpu().numpy()[:off[-1]], ent)
+    del_me = torch.full((m, c), float("nan"), dtype=dtype, device="cuda")        # the allocator hands this block to `out` next
+    del del_me
+    out = B.voxelize_mean_forward(f, i, groups)
+    again = B.voxelize_mean_forward(f, i, groups)
+    assert torch.equal(out, again)
+    got = out.cpu().numpy()
+    want32 = R.mean32(feat, idx, m, piece)
+    want = want32.astype(np.float16) if half else want32
+    assert got.dtype == want.dtype and np.array_equal(_bits(got), _bits(want))
+    ref, bound, cnt = R.mean64(feat, idx, m)
+    err = np.abs(got.astype(np.float64) - ref)
+    bar = bound + (R.UH * np.abs(got.astype(np.float64)) if half else 0.0)
+    print(f"mean {_ids(case)} P={piece}: worst err / bar {float((err / np.maximum(bar, 1e-300)).max()):.3g}")
+    assert (err <= bar).all() and (got[cnt == 0] == 0).all()
+    # the adjoint: a gather, exact
+    gout = np.random.RandomState(7).randn(m, c).astype(np.float16 if half else np.float32)
+    back = B.voxelize_mean_backward(torch.from_numpy(gout).cuda(), i, groups)
+    assert torch.equal(back, B.voxelize_mean_backward(torch.from_numpy(gout).cuda(), i, groups))
+    want_back = R.mean_backward(gout, idx, m)
+    want_back = want_back.astype(np.float16) if half else want_back
+    assert np.array_equal(_bits(back.cpu().numpy()), _bits(want_back))
+    assert (back.cpu().numpy()[(idx < 0) | (idx >= m)] == 0).all()
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float16], ids=["fp32", "half"])
+def test_mean_kernels_without_rows_or_without_voxels(dtype):
+    from taseg_amd import backend as B
+    c = 16
+    none = torch.empty((0, c), dtype=dtype, device="cuda")
+    no_idx = torch.empty(0, dtype=torch.int32, device="cuda")
+    groups = B.point_groups(no_idx, 3)
+    assert groups[0].tolist() == [0, 0, 0, 0]
+    out = B.voxelize_mean_forward(none, no_idx, groups)                           # n = 0: three zero rows
+    assert out.shape == (3, c) and bool((out == 0).all())
+    assert B.voxelize_mean_backward(torch.ones((3, c), dtype=dtype, device="cuda"), no_idx, groups).shape == (0, c)
+    idx = torch.tensor([0, -1, 0, 2, 1], dtype=torch.int32, device="cuda")        # m = 0: every row is outside the map
+    groups = B.point_groups(idx, 0)
+    assert groups[0].tolist() == [0]
+    feat = torch.ones((5, c), dtype=dtype, device="cuda")
+    assert B.voxelize_mean_forward(feat, idx, groups).shape == (0, c)
+    back = B.voxelize_mean_backward(none, idx, groups)
+    assert back.shape == (5, c) and bool((back == 0).all())
+
+
+def test_mean_kernels_refuse_widths_off_the_16_byte_rule():
+    from taseg_amd import backend as B
+    idx = torch.zeros(10, dtype=torch.int32, device="cuda")
+    groups = B.point_groups(idx, 1)
+    for dtype, c in ((torch.float32, 6), (torch.float16, 12), (torch.float32, 1028)):
+        with pytest.raises(B.BackendError):
+            B.voxelize_mean_forward(torch.zeros((10, c), dtype=dtype, device="cuda"), idx, groups)
+        with pytest.raises(B.BackendError):
+            B.voxelize_mean_backward(torch.zeros((1, c), dtype=dtype, device="cuda"), idx, groups)
+
+
+def test_spvoxelize_mean_under_autograd_against_the_float64_composition():
+    from taseg_amd import backend as B
+    from taseg_amd.torchsparse.nn import functional as F
+    piece = B.voxelize_mean_piece_rows()
+    feat, idx, m = R.piece_map(piece, 8, seed=1)
+    i = torch.from_numpy(idx).cuda()
+    g = torch.from_numpy(np.random.RandomState(8).randn(m, 8).astype(np.float32)).cuda()
+    x32 = torch.from_numpy(feat).cuda().requires_grad_()
+    x64 = torch.from_numpy(feat).cuda().double().requires_grad_()
+    y32 = F.spvoxelize_mean(x32, i, m)                                            # the kernels (grouping built inside)
+    y64 = F.spvoxelize_mean(x64, i, m)                                            # double rows: index_add of feat / cnt
+    y32.backward(g)
+    y64.backward(g.double())
+    _, bound, cnt = R.mean64(feat, idx, m)
+    assert (np.abs(y32.detach().double().cpu().numpy() - y64.detach().cpu().numpy()) <= bound).all()
+    # one division per element: within one rounding of the float64 quotient
+    assert bool(((x32.grad.double() - x64.grad).abs() <= R.U * x64.grad.abs()).all())
+    assert torch.equal(F.spvoxelize_mean(x32, i, m, B.point_groups(i, m)), y32)   # a grouping handed in: the same bits
+
+
+def test_the_private_switch_selects_the_atomic_kernel(monkeypatch):
+    """_MEAN_KERNEL = False is `spvoxelize` on `spcount`: the baseline of tools/time_spvcnn_step.py computes the same means"""
+    from taseg_amd.torchsparse.nn import functional as F
+    feat, idx, m = R.piece_map(16, 8, seed=2)
+    x, i = torch.from_numpy(feat).cuda(), torch.from_numpy(idx).cuda()
+    ours = F.spvoxelize_mean(x, i, m)
+    monkeypatch.setattr(F, "_MEAN_KERNEL", False)
+    theirs = F.spvoxelize_mean(x, i, m)
+    _, bound, _ = R.mean64(feat, idx, m)
+    assert (np.abs(ours.double().cpu().numpy() - theirs.double().cpu().numpy()) <= 2 * bound).all()
+
+
+# ------------------------------------------------------------------------------------------------------------------ point tail
+def _tail_inputs(n, c, dtype, seed):
+    rs = np.random.RandomState(seed)
+    m = 37
+    idx, w = P64.random_map(n, m, seed)
+    idx[1::5] = -1                                              # rows with all eight corners missing (weights left non-zero)
+    store = np.float16 if dtype == torch.float16 else np.float32
+    y = rs.randn(n, c).astype(store)                            # standard normal: the mask's left-out share is capped on these
+    vox = rs.randn(m, c).astype(store)
+    mean, invstd = (rs.randn(c) * 0.3).astype(np.float32), (rs.rand(c) + 0.5).astype(np.float32)
+    gamma = ((rs.rand(c) + 0.5) * np.where(np.arange(c) % 3 == 0, -1.0, 1.0)).astype(np.float32)
+    beta = (rs.randn(c) * 0.5).astype(np.float32)
+    return idx, w, m, y, vox, mean, invstd, gamma, beta
+
+
+def _unpack(mask, n, c, half):
+    per = 8 if half else 4
+    bits = (mask.cpu().numpy().reshape(n, c // per, 1) >> np.arange(per).reshape(1, 1, per)) & 1
+    return bits.reshape(n, c).astype(bool)
+
+
+@pytest.mark.parametrize("n", [1, 255, 257])
+@pytest.mark.parametrize("case", TAIL_CASES, ids=_ids)
+def test_point_tail_forward_vs_float64(case, n):
+    from taseg_amd import backend as B
+    dtype, c = case
+    half = dtype == torch.float16
+    idx, w, m, y, vox, mean, invstd, gamma, beta = _tail_inputs(n, c, dtype, 300 + n + c)
+    dev = lambda a: torch.from_numpy(a).cuda()  # noqa: E731
+    args = [dev(a) for a in (y, vox, idx, w, mean, invstd, gamma, beta)]
+    out, mask = B.point_tail_forward(*args, want_mask=True)                       # the training form (statistics given)
+    out2, mask2 = B.point_tail_forward(*args, want_mask=True)
+    plain, none = B.point_tail_forward(*args)                                     # the evaluation form: no mask
+    assert torch.equal(out, out2) and torch.equal(mask, mask2) and torch.equal(out, plain) and none is None
+    d64, t, s_d = P64.devoxelize_forward64(vox, idx, w)
+    y64 = y.astype(np.float64)
+    bn = (y64 - mean) * invstd.astype(np.float64) * gamma + beta
+    s_bn = (np.abs(y64) + np.abs(mean)) * invstd.astype(np.float64) * np.abs(gamma) + np.abs(beta)
+    bn_bar = 8 * U32 * s_bn
+    ref = d64 + np.maximum(bn, 0.0)
+    bar = P64.bar_sum(t, s_d) + bn_bar + P64.SLACK * P64.U * (np.abs(d64) + np.maximum(bn, 0.0))
+    if half:
+        bar = P64.bar_half(bar, ref)
+    err = np.abs(out.double().cpu().numpy() - ref)
+    print(f"tail {_ids(case)} n={n}: worst err / bar {float((err / bar).max()):.3g}")
+    assert (err <= bar).all()
+    assert (t[1::5] == 0).all() and (n == 1 or (t > 0).any())                     # some rows without a corner, some with
+    sure = np.abs(bn) > bn_bar
+    assert (~sure).mean() <= 0.01                                                 # a cap, on the reference values
+    assert np.array_equal(_unpack(mask, n, c, half)[sure], (bn > 0)[sure])
+
+
+def test_point_tail_refuses_widths_off_the_16_byte_rule():
+    from taseg_amd import backend as B
+    for dtype, c in ((torch.float32, 6), (torch.float16, 12)):
+        idx, w, m, y, vox, mean, invstd, gamma, beta = _tail_inputs(3, c, dtype, 5)
+        with pytest.raises(B.BackendError):
+            B.point_tail_forward(*[torch.from_numpy(a).cuda() for a in (y, vox, idx, w, mean, invstd, gamma, beta)])
+
+
+@pytest.mark.parametrize("case", [(torch.float32, 32), (torch.float32, 48), (torch.float16, 32)], ids=_ids)
+def test_point_tail_function_vs_float64_autograd(case):
+    """functional.point_tail on a training-mode BatchNorm1d: value, running statistics, grad_y, grad_gamma, grad_beta and the voxel
+    gradient against float64 (bn_ref64 for the BatchNorm half, points64 for the trilinear half; the ReLU's derivative taken where the
+    float64 BatchNorm term is positive - the test asserts that no element sits inside the bar of that term, so the kernel's mask
+    cannot differ)."""
+    from taseg_amd import backend as B
+    from taseg_amd.torchsparse.nn import functional as F
+    dtype, c = case
+    half = dtype == torch.float16
+    n = 257
+    idx, w, m, y, vox, _, _, gamma, beta = _tail_inputs(n, c, dtype, 900 + c)
+    bn = torch.nn.BatchNorm1d(c).cuda().train()
+    with torch.no_grad():
+        bn.weight.copy_(torch.from_numpy(gamma))
+        bn.bias.copy_(torch.from_numpy(beta))
+    rm0, rv0 = bn.running_mean.clone(), bn.running_var.clone()
+    yt, vt = torch.from_numpy(y).cuda().requires_grad_(), torch.from_numpy(vox).cuda().requires_grad_()
+    it, wt = torch.from_numpy(idx).cuda(), torch.from_numpy(w).cuda()
+    g = torch.from_numpy(np.random.RandomState(11).randn(n, c).astype(y.dtype)).cuda()
+    out = F.point_tail(yt, bn, vt, it, wt, B.devox_csr(it, wt, m))
+    assert out.dtype == dtype and int(bn.num_batches_tracked) == 1
+    out.backward(g)
+    lam = _lam(n, c, half)
+    (bn64, gx, _, gw, gb, mean, var), (sy, sgx, _, sgw, sgb, smean, svar) = bn_ref64(
+        yt.detach(), None, bn.weight.detach(), bn.bias.detach(), False, EPS, g, None)
+    assert bool((bn64.abs() > lam * U32 * sy).all())            # every sign is certain: the ReLU's derivative is (bn64 > 0)
+    (_, gx, _, gw, gb, _, _), (_, sgx, _, sgw, sgb, _, _) = bn_ref64(yt.detach(), None, bn.weight.detach(), bn.bias.detach(), True,
+                                                                   EPS, g, relu_from=bn64)
+    d64, t, s_d = P64.devoxelize_forward64(vox, idx, w)
+    d64, s_d, tt = (torch.from_numpy(a).cuda() for a in (d64, s_d, t.astype(np.float64)))
+    ref = d64 + bn64.clamp_min(0.0)
+    extra = P64.SLACK * tt[:, None] * P64.U * s_d + P64.SLACK * P64.U * (d64.abs() + bn64.clamp_min(0.0)) + P64.TINY * 8
+    _check("tail value", out.detach(), ref, sy, lam, extra=extra)
+    _check("grad y", yt.grad, gx, sgx, lam)
+    _check("grad gamma", bn.weight.grad, gw, sgw, lam)
+    _check("grad beta", bn.bias.grad, gb, sgb, lam)
+    a64, ta, s_a = P64.adjoint64(g.cpu().numpy(), idx, w, m)
+    abar = P64.bar_sum(ta, s_a)
+    if half:
+        abar = P64.bar_half(abar, a64)
+    assert (np.abs(vt.grad.double().cpu().numpy() - a64) <= abar).all()
+    rm, rv, srm, srv = running_ref64(rm0, rv0, mean, var, smean, svar, n, bn.momentum)
+    _check("running mean", bn.running_mean, rm, srm, lam)
+    _check("running var", bn.running_var, rv, srv, lam)
+
+
+def test_point_tail_falls_back_to_the_chain_where_it_must(monkeypatch):
+    """evaluation mode without a graph is the kernel's evaluation form; with a graph, or with the private switch off, the chain of
+    module, ReLU, spdevoxelize and add - the same values within the value's bar"""
+    from taseg_amd.torchsparse.nn import functional as F
+    n, c = 255, 32
+    idx, w, m, y, vox, mean, invstd, gamma, beta = _tail_inputs(n, c, torch.float32, 77)
+    bn = torch.nn.BatchNorm1d(c).cuda().eval()
+    with torch.no_grad():
+        bn.weight.copy_(torch.from_numpy(gamma))
+        bn.bias.copy_(torch.from_numpy(beta))
+        bn.running_mean.copy_(torch.from_numpy(mean))
+    yt, vt, it, wt = (torch.from_numpy(a).cuda() for a in (y, vox, idx, w))
+    with torch.no_grad():
+        kernel = F.point_tail(yt, bn, vt, it, wt)
+    chain = F.point_tail(yt.clone().requires_grad_(), bn, vt, it, wt)             # records a graph: the chain
+    assert chain.requires_grad and not kernel.requires_grad
+    monkeypatch.setattr(F, "_POINT_TAIL_KERNEL", False)
+    with torch.no_grad():
+        off = F.point_tail(yt, bn, vt, it, wt)
+    assert torch.equal(off, chain.detach())
+    # kernel and chain are two float32 evaluations of one expression: each within the bar of test_point_tail_forward_vs_float64
+    d64, t, s_d = P64.devoxelize_forward64(vox, idx, w)
+    is64 = 1.0 / np.sqrt(1.0 + float(bn.eps))
+    bn64 = (y.astype(np.float64) - mean) * is64 * gamma + beta
+    s_bn = (np.abs(y.astype(np.float64)) + np.abs(mean)) * is64 * np.abs(gamma) + np.abs(beta)
+    bar = P64.bar_sum(t, s_d) + 8 * U32 * s_bn + P64.SLACK * P64.U * (np.abs(d64) + np.maximum(bn64, 0.0))
+    ref = d64 + np.maximum(bn64, 0.0)
+    for got in (kernel, off):
+        assert (np.abs(got.double().cpu().numpy() - ref) <= bar).all()
