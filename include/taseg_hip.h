@@ -894,7 +894,10 @@ int ts_prof_empty_bracket_us(int32_t reps, ts_stream_t stream, double *out_us);
  * 3 / 4 = full-tile pair GEMM with one workgroup per tile everywhere / persistent workgroups everywhere
  *         (default: persistent for the forward weight layout only),
  * 11 / 13 = with pre-split weight planes at hand (ts_conv_planes_hint) take the direct-rows pair GEMM on 96-column tiles
- *         as well / never (default: on 128-column tiles). */
+ *         as well / never (default: on 128-column tiles),
+ * 14 = the default choice everywhere, but the fp32 class GEMM's plain launch runs one workgroup per tile instead of the
+ *         persistent walk (same bits: the A/B parent and the bit oracle of the walk),
+ * 15 = as 14, but with the walk's kernel (two gathered slices in flight), launched with a workgroup per tile. */
 void ts_set_conv_impl(int32_t impl);
 
 /* Lovasz-softmax with classes = 'present' around ONE sort (R/tools/utils/common/lovasz_losses.py:158-227: lovasz_softmax_flat,
@@ -1002,6 +1005,20 @@ int32_t ts_conv_class_supported(int32_t c_red, int32_t c_out);
 int ts_conv_class_gemm(const float *feat, int32_t c_red, const float *kernel, int32_t K, int32_t groups, int32_t c_out,
                        const int32_t *src, int64_t m_pad, const int32_t *tile_info, const int32_t *n_tiles, int32_t wt,
                        int32_t mirror, const int32_t *rows, float *zp, ts_stream_t stream);
+/* With the weight's pre-split planes at hand (ts_conv_planes_hint(kernel, planes, K, C_in, C_out) right before the call, or
+ * TsConvBlockOpts.planes of a block call) ts_conv_class_gemm runs persistent workgroups that walk the tile list (workgroup `slot`
+ * of G takes tile round * G + slot, the slot order reversed every other round) and read the weight slices from the planes;
+ * G = min(m_pad / 128, ts_conv_class_walk_slots(c_out, wt)) per column tile: what the chip holds of the instantiation that serves
+ * c_out columns.  A call with a bare weight, and ts_set_conv_impl(14), run one workgroup per tile, which splits the fp32 weight
+ * slice itself: the same bits. */
+int32_t ts_conv_class_walk_slots(int32_t c_out, int32_t wt);
+/* ... with the job the block calls let ride on the launch: dw [side_k][cacb] = per offset k the ascending sum of the weight-gradient
+ * partial tiles part[c + k][cacb] over the chunks c = nboffs[k] / chunk .. (nboffs[k + 1] - 1) / chunk of its pairs (zeros where an
+ * offset has none); cacb a multiple of 4, part and dw 16-byte aligned */
+int ts_conv_class_gemm_wsum(const float *feat, int32_t c_red, const float *kernel, int32_t K, int32_t groups, int32_t c_out,
+                            const int32_t *src, int64_t m_pad, const int32_t *tile_info, const int32_t *n_tiles, int32_t wt,
+                            int32_t mirror, const int32_t *rows, float *zp, const float *part, const int32_t *side_nboffs, float *dw,
+                            int32_t side_k, int32_t chunk, int64_t cacb, ts_stream_t stream);
 /* does finishing inside the product beat pass 2 on a map of n rows (measured thresholds; what the block calls use) */
 int32_t ts_conv_class_finish_pays(int64_t n, int32_t half);
 int ts_conv_class_conv(const float *feat, int32_t c_red, const float *kernel, int32_t K, int32_t groups, int32_t c_out,

@@ -193,6 +193,9 @@ SIGNATURES = {
     "ts_conv_class_plan_pairs": (_i32, [_vp, _vp, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ts_conv_nbr_transposed": (_i32, [_vp, _vp, _i32, _i64, _vp, _vp]),
     "ts_conv_class_supported": (_i32, [_i32, _i32]),
+    "ts_conv_class_walk_slots": (_i32, [_i32, _i32]),
+    "ts_conv_class_gemm_wsum": (_i32, [_vp, _i32, _vp, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32,
+                                       _i32, _i64, _vp]),
     "ts_conv_class_gemm": (_i32, [_vp, _i32, _vp, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _i32, _i32, _vp, _vp, _vp]),
     "ts_conv_class_gemm_f16": (_i32, [_vp, _i32, _vp, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _i32, _i32, _vp, _vp, _vp]),
     "ts_conv_class_finish_pays": (_i32, [_i64, _i32]),

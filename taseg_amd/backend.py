@@ -1112,9 +1112,11 @@ def conv3x3c32_wgrad(x, grad_y, like_weight, dilation, want_bias=False):
 
 def set_conv_impl(impl):
     """0 = MFMA kernels (default: full-tile fp32 GEMMs as split-bf16 MFMAs), 1 = scalar cross-check kernels, 2 = guarded
-    generic f32 MFMA staging only, 3 / 4 = f32 MFMA one workgroup per tile / persistent, 5 = f32 MFMA default choice."""
+    generic f32 MFMA staging only, 3 / 4 = f32 MFMA one workgroup per tile / persistent, 5 = f32 MFMA default choice,
+    14 = the default choice with the fp32 class GEMM on one workgroup per tile instead of the persistent walk (same bits),
+    15 = as 14 with the walk's kernel."""
     global _conv_impl
-    _conv_impl = int(impl)
+    _conv_impl = 0 if int(impl) in (14, 15) else int(impl)
     L.load().ts_set_conv_impl(int(impl))
 
 
@@ -1802,8 +1804,9 @@ def class_plan_struct(plan):
     return st
 
 
-def conv_class_gemm(feat, kernel, plan, weight_transposed=False):
-    """The product on a class plan.  Pass-2 plans: z' [m_pad, C] with one row per (destination row, group of offsets); the
+def conv_class_gemm(feat, kernel, plan, weight_transposed=False, planes=None):
+    """The product on a class plan.  planes: the weight's pre-split planes (taseg_amd.planes.planes_for) - with them the launch
+    runs the persistent walk, without them the one-tile kernel that splits the weight itself; the same bits.  Pass-2 plans: z' [m_pad, C] with one row per (destination row, group of offsets); the
     convolution is conv_gather_sum(z', plan["pos"], n).  Direct plans: the result [n, C] itself.  weight_transposed: the
     transposed product (feat = output gradients, kernel as stored)."""
     L.require_device(feat, kernel)
@@ -1817,6 +1820,8 @@ def conv_class_gemm(feat, kernel, plan, weight_transposed=False):
     with _Timed("class_gemm", name=f"class_gemm_kernel<{_tile_cols(cols)}>", pairs=int(plan.get("pairs", 0)), c_red=c_red,
                 c_out=cols, k=k, esize=4, n_rows=feat.shape[0], z_rows=0 if direct else int(plan.get("z_rows") or plan["m_pad"]),
                 out_rows=plan["n"] if direct else 0):
+        if planes is not None:
+            L.load().ts_conv_planes_hint(L.ptr(kernel), L.ptr(planes), k, c_in, c_out)      # one-shot, read by the call below
         L.check(L.load().ts_conv_class_gemm(L.ptr(feat), c_red, L.ptr(kernel), k, plan["groups"], cols, L.ptr(plan["src"]),
                                             plan["m_pad"], L.ptr(plan["tile_info"]), L.ptr(plan["n_tiles"]),
                                             1 if weight_transposed else 0, plan["mirror"], L.ptr(plan["rows"]), L.ptr(zp),

@@ -12,6 +12,7 @@
 
 void ts_set_error(const char *fmt, ...);
 extern int g_ts_conv_impl;  // 0 = MFMA kernels, 1 = scalar cross-check kernels (ts_set_conv_impl)
+extern int g_ts_class_one_tile;  // ts_set_conv_impl(14): the fp32 class GEMM's plain launch keeps one workgroup per tile (conv_class.hip)
 
 #define TS_REQUIRE(cond, code, ...)  \
   do {                               \
@@ -255,7 +256,7 @@ struct TsClassFinish {
 int ts_conv_class_gemm_ex(const float *feat, int32_t c_red, const float *kernel, int32_t K, int32_t groups, int32_t c_out,
                           const int32_t *src, int64_t m_pad, const int32_t *tile_info, const int32_t *n_tiles, int32_t wt,
                           int32_t mirror, const int32_t *rows, float *zp, const TsWgradReduce *side, const TsClassFinish *fin,
-                          ts_stream_t stream);
+                          const void *planes, ts_stream_t stream);      // planes: the weight's pre-split planes or NULL
 int ts_conv_class_gemm_f16_ex(const void *feat, int32_t c_red, const void *w, int32_t K, int32_t groups, int32_t c_out,
                               const int32_t *src, int64_t m_pad, const int32_t *tile_info, const int32_t *n_tiles, int32_t wt,
                               int32_t mirror, const int32_t *rows, void *zp, const TsWgradReduce *side, const TsClassFinish *fin,

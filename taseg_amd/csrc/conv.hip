@@ -25,8 +25,14 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define CV_AP (CV_CK + 4)  // LDS row pitch (floats) of K-major tiles: 16-B aligned, bank-skewed
 
 int g_ts_conv_impl = 0;
+int g_ts_class_one_tile = 0;
 
-extern "C" void ts_set_conv_impl(int32_t impl) { g_ts_conv_impl = impl; }
+// 14 / 15 are the default choice everywhere except the fp32 class GEMM's plain launch, which then runs one workgroup per tile:
+// 14 = class_gemm_kernel, 15 = the walk's kernel with as many workgroups as tiles
+extern "C" void ts_set_conv_impl(int32_t impl) {
+  g_ts_class_one_tile = impl == 14 ? 1 : impl == 15 ? 2 : 0;
+  g_ts_conv_impl = (impl == 14 || impl == 15) ? 0 : impl;
+}
 
 // ======================================================================================
 // conv_nbr_kernel

@@ -558,6 +558,333 @@ __global__ __launch_bounds__(256, 2) void class_gemm_kernel(const float *__restr
         zt[(int64_t)((wr * MI + mi) * 16 + 4 * g + q) * O_total + (wc * NI + ni) * 16 + r16] = tot[mi][ni][q];
 }
 
+// The plain launch (phase 0) with persistent workgroups: the slices, the split, the six MFMAs, acc / tot and the stores of
+// class_gemm_kernel - the same bits - but a workgroup walks the tile list (tile = round * G + its slot, the slot order reversed
+// every other round: the list is sorted longest first; no communication between workgroups, every tile owns its rows) instead of
+// living for one tile.  One-tile workgroups pay the dependent chain tile entry -> row indices -> rows -> LDS before their first
+// MFMA and the flush after the last, 2 761 times on the stride-1 layer, with only the CU's other workgroup at work meanwhile.
+// Here the stream of slices does not stop at a tile's end: the entry of the next tile is read a tile ahead (scalar loads), the
+// row indices of its first offset an offset ahead (the nsrc registers), its first gathered slice and weight slice are in flight
+// behind the current tile's last MFMA block, and the finished tile's sums leave while those loads are outstanding.  A tile with
+// mask 0 (direct plans) is zero-filled inside the walk.  grid (G [+ 64 side-job workgroups], O_total / BN).
+// NS = 2: TWO gathered slices in flight (a second register set): while slice s multiplies, the rows of s + 1 and s + 2 are
+// outstanding - one slice (16 KB per workgroup, 32 KB per CU) covers too little of the fabric's latency.  The waits are the
+// compiler's own counted s_waitcnt vmcnt(N); three things keep it from falling back to vmcnt(0) (each seen in the assembly):
+// every slice issues the same number of loads (no branch around a dead row's loads, no skipped weight load), the slice loop
+// has one exit, and every lambda is inlined (a closure left as a call put acc / tot behind references, in scratch).
+// Registers (hipcc -Rpass-analysis=kernel-resource-usage, profiles/class_f32_persistent.txt): no spills at two workgroups per
+// CU with NS = 2 up to 96 columns; 128 columns keep one set.
+struct CgWalkStep {
+  int row0, grp, kl, last;  // first list slot of the tile, its group, the offset inside the group, last offset of the tile
+};
+
+struct CgWalkSlice {        // a slice of the stream that is in flight or being multiplied
+  int valid, off_done, tile_done, row0;      // last slice of its offset / of its tile; first list slot of the tile
+  const unsigned short *wb;                  // its weight slice (h plane; m and l are plane_n elements on)
+};
+
+template <int BN, int WR, bool WT, int NS>
+__global__ __launch_bounds__(256, 2) void class_gemm_p_kernel(const float *__restrict__ X, int R, const float *__restrict__ W,
+                                                             int O_total, const int *__restrict__ src, int64_t m_pad,
+                                                             const int2 *__restrict__ tile_info,
+                                                             const int *__restrict__ n_tiles_p, int tile_bound, int K, int gk,
+                                                             int mirror, const int *__restrict__ rows, float *__restrict__ Zp,
+                                                             TsWgradReduce side, int G,
+                                                             const unsigned short *__restrict__ P, int64_t plane_n) {
+  constexpr int BM = CG_BM;
+  constexpr int WC = 4 / WR;
+  constexpr int MI = (BM / 16) / WR;
+  constexpr int NI = (BN / 16) / WC;
+  constexpr int BP = BN + 8;
+  constexpr int A_PLANE = BM * CG_AP;
+  constexpr int B_PLANE = WT ? BN * CG_AP : CG_BK * BP;
+  constexpr int A_IT = BM * (CG_BK / 8) / 256;
+  constexpr int B_CHUNKS = BN * (CG_BK / 8);
+  constexpr int B_IT = (B_CHUNKS + 255) / 256;
+  constexpr int A_PLANES = 3;
+  extern __shared__ __attribute__((aligned(16))) unsigned short smem_cg[];
+  unsigned short *Ap = smem_cg;
+  unsigned short *Bp = Ap + A_PLANES * A_PLANE;
+
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int r16 = lane & 15, g = lane >> 4;
+  const int tq = r16 >> 2, tp = lane & 3;
+  const int wr = wave / WC, wc = wave % WC;
+  const int o0 = blockIdx.y * BN;
+  if ((int)blockIdx.x >= G) {                   // side job: ordered sum of the weight-gradient partials
+    if (blockIdx.y == 0) {
+      const int64_t step = (int64_t)(gridDim.x - G) * 256;
+      for (int64_t i = (int64_t)((int)blockIdx.x - G) * 256 + tid; i < (int64_t)side.K * side.cacb4; i += step)
+        ts_wgrad_reduce_one(side, i);
+    }
+    return;
+  }
+
+  // ---- the walk: everything wave-uniform (SGPRs)
+  const int n_tiles = min(__builtin_amdgcn_readfirstlane(*n_tiles_p), tile_bound);
+  const int slot = (int)blockIdx.x;
+  int round = 0, rest = 0, cur_row0 = 0, cur_grp = 0;
+  auto tile_of = [&](int r) __attribute__((always_inline)) { return r * G + ((r & 1) ? G - 1 - slot : slot); };
+  auto load_entry = [&](int t) __attribute__((always_inline)) -> int2 {
+    int2 e = make_int2(0, 0);
+    if (t < n_tiles) e = tile_info[t];
+    return make_int2(__builtin_amdgcn_readfirstlane(e.x), __builtin_amdgcn_readfirstlane(e.y));
+  };
+  auto zero_tile = [&](int row0) __attribute__((always_inline)) {               // direct plans: a tile of rows without any neighbour - their result is zero
+    int t0 = tid;
+    asm volatile("" : "+v"(t0));                 // (addresses formed here, not kept in registers across the walk)
+    for (int e = t0; e < BM * (BN / 4); e += 256) {
+      const int r = e / (BN / 4), c4 = e - r * (BN / 4);
+      const int dst = rows ? rows[row0 + r] : row0 + r;
+      if (dst >= 0) *(f32x4 *)(Zp + (int64_t)dst * O_total + o0 + 4 * c4) = (f32x4){0.f, 0.f, 0.f, 0.f};
+    }
+  };
+  int2 ahead = load_entry(tile_of(0));           // entry of the tile this workgroup opens next
+  auto next_step = [&](CgWalkStep &st) __attribute__((always_inline)) -> bool {  // false: this workgroup's list is finished
+    while (rest == 0) {
+      if (tile_of(round) >= n_tiles) return false;
+      const int2 e = ahead;
+      round += 1;
+      ahead = load_entry(tile_of(round));
+      cur_grp = e.x & 3;
+      cur_row0 = (e.x >> 2) * BM;
+      rest = e.y & 511;
+      if (rest == 0) zero_tile(cur_row0);
+    }
+    st.kl = __builtin_ctz(rest);
+    rest &= rest - 1;
+    st.row0 = cur_row0;
+    st.grp = cur_grp;
+    st.last = rest == 0;
+    return true;
+  };
+
+  const int arow0 = tid >> 2, acol = (tid & 3) << 3;
+  int boff[B_IT], bdst[B_IT];
+#pragma unroll
+  for (int it = 0; it < B_IT; ++it) {
+    const int e = min(tid + it * 256, B_CHUNKS - 1);
+    if (WT) {
+      const int col = e >> 2, c8 = (e & 3) << 3;
+      boff[it] = col * R + c8;
+      bdst[it] = col * CG_AP + c8;
+    } else {
+      constexpr int q8 = BN >> 3;
+      const int kk = e / q8, c8 = (e - kk * q8) << 3;
+      boff[it] = kk * O_total + c8;
+      bdst[it] = kk * BP + c8;
+    }
+  }
+
+  // acc / tot as in class_gemm_kernel: a fresh acc per offset, tot += acc with offsets ascending, tot = 0 at a tile's start
+  f32x4 acc[MI][NI], tot[MI][NI];
+#pragma unroll
+  for (int mi = 0; mi < MI; ++mi)
+#pragma unroll
+    for (int ni = 0; ni < NI; ++ni) acc[mi][ni] = tot[mi][ni] = (f32x4){0.f, 0.f, 0.f, 0.f};
+
+  const float *aptr[A_IT];
+  bool alive[A_IT];
+  const unsigned short *wk = P;
+  int nsrc[A_IT];                       // input rows of the step after the one being loaded, fetched an offset ahead
+  auto fetch = [&](const CgWalkStep &st) __attribute__((always_inline)) {
+#pragma unroll
+    for (int it = 0; it < A_IT; ++it) nsrc[it] = src[(int64_t)st.kl * m_pad + st.row0 + arow0 + 64 * it];
+  };
+  auto bind = [&](const CgWalkStep &st) __attribute__((always_inline)) {
+    const int k = gk * st.grp + st.kl;
+    const int kw = (WT && mirror) ? (K - 1 - k) : k;
+#pragma unroll
+    for (int it = 0; it < A_IT; ++it) {
+      alive[it] = nsrc[it] >= 0;
+      aptr[it] = alive[it] ? X + (int64_t)nsrc[it] * R + acol : W + acol;
+    }
+    wk = WT ? P + ((int64_t)kw * O_total + o0) * R : P + (int64_t)kw * R * O_total + o0;
+  };
+  f32x4 ra[NS][A_IT][2];
+  u32x4 rb[B_IT][3];                    // the weight slice as it stands in the planes: nothing to split
+  bool rlive[NS][A_IT];
+  // the walk two stages ahead of the MFMAs: sf = the step whose row indices are in nsrc, sld = the step whose rows are being
+  // loaded (aptr / alive / wk bound to it), c0_ld its next slice
+  CgWalkStep sld, sf;
+  bool has_f = false, ld_valid = false, advance = false;
+  int c0_ld = 0;
+  auto issue_a = [&](auto set_c) __attribute__((always_inline)) -> CgWalkSlice {      // the gathered rows of the next slice of the stream into register set `set`
+    constexpr int set = decltype(set_c)::value;
+    CgWalkSlice e = {0, 0, 0, 0, P};
+    if (advance) {                       // (deferred to here: the indices fetched an offset ago have arrived behind older loads)
+      advance = false;
+      if (has_f) {
+        bind(sf);
+        sld = sf;
+        c0_ld = 0;
+        has_f = next_step(sf);
+        if (has_f) fetch(sf);
+      } else {                           // the stream has ended: the loads go on (from the weight), nothing is staged from them
+        ld_valid = false;
+        c0_ld = 0;
+#pragma unroll
+        for (int it = 0; it < A_IT; ++it) {
+          alive[it] = false;
+          aptr[it] = W + acol;
+        }
+      }
+    }
+    // Every slice issues the same loads whatever its rows hold: a row without this neighbour reads the head of the weight (one
+    // cached line for all of them, never row 0 of X) and stages zeros.  With a branch around the loads of dead rows the compiler
+    // can no longer count the loads behind the one it waits for and drains them all (s_waitcnt vmcnt(0)) at every wait.
+#pragma unroll
+    for (int it = 0; it < A_IT; ++it) {
+      ra[set][it][0] = *(const f32x4 *)(aptr[it] + c0_ld);
+      ra[set][it][1] = *(const f32x4 *)(aptr[it] + c0_ld + 4);
+      rlive[set][it] = alive[it];
+    }
+    if (!ld_valid) return e;
+    e.valid = 1;
+    e.off_done = c0_ld + CG_BK >= R;
+    e.tile_done = e.off_done && sld.last;
+    e.row0 = sld.row0;
+    e.wb = WT ? wk + c0_ld : wk + (int64_t)c0_ld * O_total;
+    c0_ld += CG_BK;
+    advance = e.off_done;
+    return e;
+  };
+  auto load_b = [&](const CgWalkSlice &e) __attribute__((always_inline)) {
+#pragma unroll
+    for (int it = 0; it < B_IT; ++it) {
+#pragma unroll
+      for (int p = 0; p < 3; ++p) rb[it][p] = *(const u32x4 *)(e.wb + p * plane_n + boff[it]);
+    }
+  };
+  auto store_lds = [&](auto set_c) __attribute__((always_inline)) {
+    constexpr int set = decltype(set_c)::value;
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int it = 0; it < A_IT; ++it) {
+      const int rr = arow0 + 64 * it;
+      const f32x4 v0 = rlive[set][it] ? ra[set][it][0] : zero, v1 = rlive[set][it] ? ra[set][it][1] : zero;
+      unsigned short *dst = Ap + rr * CG_AP + acol;
+      u32x4 h, m, l;
+      cg_split8(v0, v1, h, m, l);
+      *(u32x4 *)dst = h;
+      *(u32x4 *)(dst + A_PLANE) = m;
+      *(u32x4 *)(dst + 2 * A_PLANE) = l;
+    }
+#pragma unroll
+    for (int it = 0; it < B_IT; ++it) {
+      if (B_IT * 256 == B_CHUNKS || tid + it * 256 < B_CHUNKS) {
+        unsigned short *dst = Bp + bdst[it];
+#pragma unroll
+        for (int p = 0; p < 3; ++p) *(u32x4 *)(dst + p * B_PLANE) = rb[it][p];
+      }
+    }
+  };
+  auto mma = [&]() __attribute__((always_inline)) {
+    bf8 a[MI][A_PLANES];
+#pragma unroll
+    for (int mi = 0; mi < MI; ++mi)
+#pragma unroll
+      for (int p = 0; p < A_PLANES; ++p)
+        a[mi][p] = *(const bf8 *)&Ap[p * A_PLANE + ((wr * MI + mi) * 16 + r16) * CG_AP + 8 * g];
+#pragma unroll
+    for (int ni = 0; ni < NI; ++ni) {
+      bf8 b[3];
+#pragma unroll
+      for (int p = 0; p < 3; ++p) {
+        if (WT)
+          b[p] = *(const bf8 *)&Bp[p * B_PLANE + ((wc * NI + ni) * 16 + r16) * CG_AP + 8 * g];
+        else
+          b[p] = cg_frag_tr(Bp + p * B_PLANE, BP, 8 * g, (wc * NI + ni) * 16, tq, tp);
+      }
+#pragma unroll
+      for (int mi = 0; mi < MI; ++mi) CG_MMA(acc[mi][ni], a[mi], b);
+    }
+  };
+  // the finished tile's sums: Z' rows of the tile, or - direct plans - the destination rows of its slots (-1 = padding)
+  auto store_tile = [&](int row0) __attribute__((always_inline)) {
+    int g = lane >> 4, r16 = lane & 15;
+    asm volatile("" : "+v"(g), "+v"(r16));       // (addresses formed here, not kept in registers across the walk)
+    if (rows) {
+      int dst[MI][4];                      // (all of them first: one wait, not one per row)
+#pragma unroll
+      for (int mi = 0; mi < MI; ++mi)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) dst[mi][q] = rows[row0 + (wr * MI + mi) * 16 + 4 * g + q];
+#pragma unroll
+      for (int mi = 0; mi < MI; ++mi)
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+          if (dst[mi][q] >= 0) {
+            float *zr = Zp + (int64_t)dst[mi][q] * O_total + o0 + r16;
+#pragma unroll
+            for (int ni = 0; ni < NI; ++ni) zr[(wc * NI + ni) * 16] = tot[mi][ni][q];
+          }
+    } else {
+      float *zt = Zp + (int64_t)row0 * O_total + o0;
+#pragma unroll
+      for (int mi = 0; mi < MI; ++mi)
+#pragma unroll
+        for (int ni = 0; ni < NI; ++ni)
+#pragma unroll
+          for (int q = 0; q < 4; ++q)
+            zt[(int64_t)((wr * MI + mi) * 16 + 4 * g + q) * O_total + (wc * NI + ni) * 16 + r16] = tot[mi][ni][q];
+    }
+#pragma unroll
+    for (int mi = 0; mi < MI; ++mi)
+#pragma unroll
+      for (int ni = 0; ni < NI; ++ni) tot[mi][ni] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  };
+
+  // stream position s: slice s multiplies from LDS while the weights of slice s + 1 and the gathered rows of slice s + NS are in
+  // flight (NS == 2: issued in that order, so waiting for the weights leaves the rows of s + 2 outstanding); e[i] = slice s + i
+  ld_valid = next_step(sld);
+  if (!ld_valid) return;
+  fetch(sld);
+  bind(sld);
+  has_f = next_step(sf);
+  if (has_f) fetch(sf);
+  CgWalkSlice e[NS + 1];
+  e[0] = issue_a(std::integral_constant<int, 0>{});
+  load_b(e[0]);
+  if (NS == 2) e[1] = issue_a(std::integral_constant<int, 1>{});
+  bool first = true, more = true;
+  auto body = [&](auto set_c) __attribute__((always_inline)) {
+    if (!first) __syncthreads();           // the previous slice's fragments have been read
+    first = false;
+    store_lds(set_c);
+    __syncthreads();
+    if (NS == 2) {
+      load_b(e[1]);                        // (an invalid slice: the head of the weight)
+      e[2 % (NS + 1)] = issue_a(set_c);
+    } else {
+      e[1] = issue_a(set_c);
+      load_b(e[1]);
+    }
+    mma();
+    if (e[0].off_done) {
+#pragma unroll
+      for (int mi = 0; mi < MI; ++mi)
+#pragma unroll
+        for (int ni = 0; ni < NI; ++ni) {
+          tot[mi][ni] += acc[mi][ni];
+          acc[mi][ni] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        }
+      if (e[0].tile_done) store_tile(e[0].row0);
+    }
+    more = e[1].valid != 0;
+    e[0] = e[1];
+    if (NS == 2) e[1] = e[2 % (NS + 1)];
+  };
+  // ONE exit, at the bottom: with a second one between the two passes the compiler cannot tell the loads behind set 0 on the way
+  // round from those on the way out and waits for all of them.  A stream of an odd length ends with an idle pass (zeros staged,
+  // nothing added, nothing stored).
+  do {
+    body(std::integral_constant<int, 0>{});
+    if (NS == 2) body(std::integral_constant<int, NS - 1>{});
+  } while (more);
+}
+
 struct CgArgs {          // what a class-GEMM launch takes beyond operands and result
   const int *src;
   int64_t m_pad;
@@ -568,6 +895,8 @@ struct CgArgs {          // what a class-GEMM launch takes beyond operands and r
   TsWgradReduce side;
   CgFinish fin;          // phase 0: plain launch
   int groups;
+  const unsigned short *planes;      // pre-split planes of the weight (conv_pairs_s.hip), NULL: none - the one-tile kernel splits
+  int64_t plane_n;
 };
 static int64_t cg_tile_bound(const CgArgs &a) { return a.m_pad / CG_BM; }      // tiles a launch can meet (every phase walks the list)
 
@@ -583,6 +912,48 @@ static int launch_class(const float *X, int R, const float *W, int O_total, cons
   return TS_OK;
 }
 static int cg_tile_columns(int c_out) { return c_out % 128 == 0 ? 128 : c_out % 96 == 0 ? 96 : c_out % 64 == 0 ? 64 : c_out % 32 == 0 ? 32 : 0; }
+
+// workgroups of class_gemm_p_kernel<BN, WR, WT> the chip holds at once (registers and LDS of THIS instantiation)
+// register sets of gathered rows in flight: two where the instantiation holds them at two workgroups per CU without spilling
+// (128 columns: acc and tot alone are 128 registers - one set)
+template <int BN>
+constexpr int cg_row_sets() { return BN <= 96 ? 2 : 1; }
+template <int BN, int WR, bool WT>
+static int class_p_resident() {
+  static const int resident = [] {
+    const size_t lds = (size_t)(3 * CG_BM * CG_AP + 3 * (WT ? BN * CG_AP : CG_BK * (BN + 8))) * 2;
+    int nb = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, class_gemm_p_kernel<BN, WR, WT, cg_row_sets<BN>()>, 256, lds) != hipSuccess || nb < 1) nb = 1;
+    return ts_cu_count() * nb;
+  }();
+  return resident;
+}
+template <int BN, int WR, bool WT>
+static int launch_class_p(const float *X, int R, const float *W, int O_total, const CgArgs &a, float *Zp, hipStream_t stream) {
+  const size_t lds = (size_t)(3 * CG_BM * CG_AP + 3 * (WT ? BN * CG_AP : CG_BK * (BN + 8))) * 2;
+  const int64_t tiles = cg_tile_bound(a);
+  const int ny = O_total / BN;
+  // (ts_set_conv_impl(15): a workgroup per tile of the bound - the kernel without the walk, for A/B runs)
+  const int G = g_ts_class_one_tile == 2 ? (int)tiles
+                                         : (int)std::max<int64_t>(1, std::min<int64_t>(tiles, class_p_resident<BN, WR, WT>() / ny));
+  dim3 grid((unsigned)G + (a.side.K > 0 ? 64u : 0u), (unsigned)ny);
+  class_gemm_p_kernel<BN, WR, WT, cg_row_sets<BN>()><<<grid, 256, lds, stream>>>(X, R, W, O_total, a.src, a.m_pad, a.tile_info, a.n_tiles, (int)tiles,
+                                                              a.K, a.gk, a.mirror, a.rows, Zp, a.side, G, a.planes, a.plane_n);
+  TS_CHECK_LAUNCH("ts_conv_class_gemm (persistent)");
+  return TS_OK;
+}
+
+// slots of the persistent walk for a c_out-column product (wt: the transposed one): a launch on a plan with more tiles than this
+// runs this many workgroups per column tile, each taking tile round * slots + slot (tests size their tables from it)
+extern "C" int32_t ts_conv_class_walk_slots(int32_t c_out, int32_t wt) {
+  const int bn = cg_tile_columns(c_out);
+  if (bn == 0) return 0;
+  const int ny = c_out / bn;
+#define CG_RES(BN, WR) (wt ? class_p_resident<BN, WR, true>() : class_p_resident<BN, WR, false>())
+  const int res = bn == 128 ? CG_RES(128, 2) : bn == 96 ? CG_RES(96, 2) : bn == 64 ? CG_RES(64, 2) : CG_RES(32, 4);
+#undef CG_RES
+  return std::max(1, res / ny);
+}
 
 extern "C" int32_t ts_conv_class_supported(int32_t c_red, int32_t c_out) {
   return c_red > 0 && c_red % CG_BK == 0 && cg_tile_columns(c_out) != 0;
@@ -626,22 +997,37 @@ static int cg_finish(const char *what, const TsClassFinish *fin, int K, int grou
   return TS_OK;
 }
 
+// the one-shot hint of the calling thread (ts_conv_planes_hint), if it names this weight [K, c_in, c_out]; cleared either way
+static const void *cg_take_hint(const float *kernel, int K, int c_in, int c_out) {
+  const TsPlanesHint h = g_ts_planes_hint;
+  g_ts_planes_hint = TsPlanesHint{nullptr, nullptr, 0, 0, 0};
+  return (h.w == kernel && h.planes && h.K == K && h.c_in == c_in && h.c_out == c_out) ? h.planes : nullptr;
+}
+
 // library-internal form (csrc/block.hip): + the weight-gradient sum riding on the launch, + the finish inside the product
 int ts_conv_class_gemm_ex(const float *feat, int32_t c_red, const float *kernel, int32_t K, int32_t groups, int32_t c_out,
                           const int32_t *src, int64_t m_pad, const int32_t *tile_info, const int32_t *n_tiles, int32_t wt,
                           int32_t mirror, const int32_t *rows, float *zp, const TsWgradReduce *side, const TsClassFinish *fin,
-                          ts_stream_t stream_) {
+                          const void *planes, ts_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   const int rc = cg_check("ts_conv_class_gemm", K, groups, c_red, c_out, m_pad, feat, kernel, zp, src, tile_info, n_tiles);
   if (rc != TS_OK) return rc;
-  CgArgs a = {src, m_pad, (const int2 *)tile_info, n_tiles, K, K / groups, mirror ? 1 : 0, rows, {}, {}, groups};
+  TS_REQUIRE((((uintptr_t)planes) & 15) == 0, TS_ERR_INVALID_ARGUMENT, "ts_conv_class_gemm: planes must be 16-byte aligned");
+  CgArgs a = {src, m_pad, (const int2 *)tile_info, n_tiles, K, K / groups, mirror ? 1 : 0, rows, {}, {}, groups,
+              (const unsigned short *)planes, (int64_t)K * c_red * c_out};
   {
     const int frc = cg_finish("ts_conv_class_gemm", fin, K, groups, rows, a.fin);
     if (frc != TS_OK) return frc;
   }
-#define CG_GO(BN, WR)                                                                  \
-  (wt ? launch_class<BN, WR, true>(feat, c_red, kernel, c_out, a, zp, stream)          \
-      : launch_class<BN, WR, false>(feat, c_red, kernel, c_out, a, zp, stream))
+  // the plain launch on a weight whose planes the caller keeps walks the list with persistent workgroups and reads the planes;
+  // a call without planes, the phases of the finish inside the product (and ts_set_conv_impl(14): the A/B parent and bit oracle
+  // of the walk) keep one workgroup per tile, which splits the fp32 slice itself - the same bits
+  const bool walk = !fin && planes && g_ts_class_one_tile != 1;
+#define CG_GO(BN, WR)                                                                              \
+  (walk ? (wt ? launch_class_p<BN, WR, true>(feat, c_red, kernel, c_out, a, zp, stream)            \
+              : launch_class_p<BN, WR, false>(feat, c_red, kernel, c_out, a, zp, stream))          \
+        : (wt ? launch_class<BN, WR, true>(feat, c_red, kernel, c_out, a, zp, stream)              \
+              : launch_class<BN, WR, false>(feat, c_red, kernel, c_out, a, zp, stream)))
   // phase 1 (or the one plain launch), then - finish inside the product - phase 2, which also carries the side job
   for (int phase = a.fin.phase; phase <= (fin ? 2 : 0); ++phase) {
     a.fin.phase = phase;
@@ -667,7 +1053,22 @@ extern "C" int ts_conv_class_gemm(const float *feat, int32_t c_red, const float 
                                   const int32_t *src, int64_t m_pad, const int32_t *tile_info, const int32_t *n_tiles, int32_t wt,
                                   int32_t mirror, const int32_t *rows, float *zp, ts_stream_t stream) {
   return ts_conv_class_gemm_ex(feat, c_red, kernel, K, groups, c_out, src, m_pad, tile_info, n_tiles, wt, mirror, rows, zp, nullptr,
-                               nullptr, stream);
+                               nullptr, cg_take_hint(kernel, K, wt ? c_out : c_red, wt ? c_red : c_out), stream);
+}
+
+// ... with the job the block calls let ride on the launch (64 more workgroups): the ordered sum of weight-gradient partial tiles,
+// dw [side_k][cacb] = for offset k the sum, ascending, of part[c + k][cacb] over the chunks c = nboffs[k] / chunk ..
+// (nboffs[k + 1] - 1) / chunk of its pairs (zeros for an offset without pairs); part holds (nboffs[side_k] - 1) / chunk + 1 + side_k tiles
+extern "C" int ts_conv_class_gemm_wsum(const float *feat, int32_t c_red, const float *kernel, int32_t K, int32_t groups, int32_t c_out,
+                                       const int32_t *src, int64_t m_pad, const int32_t *tile_info, const int32_t *n_tiles, int32_t wt,
+                                       int32_t mirror, const int32_t *rows, float *zp, const float *part, const int32_t *side_nboffs,
+                                       float *dw, int32_t side_k, int32_t chunk, int64_t cacb, ts_stream_t stream) {
+  TS_REQUIRE(part && side_nboffs && dw && side_k > 0 && chunk > 0 && cacb > 0 && cacb % 4 == 0 &&
+                 ((((uintptr_t)part) | ((uintptr_t)dw)) & 15) == 0,
+             TS_ERR_INVALID_ARGUMENT, "ts_conv_class_gemm_wsum: bad side job");
+  const TsWgradReduce side = {part, side_nboffs, dw, side_k, chunk, cacb / 4};
+  return ts_conv_class_gemm_ex(feat, c_red, kernel, K, groups, c_out, src, m_pad, tile_info, n_tiles, wt, mirror, rows, zp, &side,
+                               nullptr, cg_take_hint(kernel, K, wt ? c_out : c_red, wt ? c_red : c_out), stream);
 }
 
 
@@ -680,7 +1081,7 @@ extern "C" int ts_conv_class_conv(const float *feat, int32_t c_red, const float 
                                   ts_stream_t stream) {
   const TsClassFinish fin = {pos, n, out, addend};
   return ts_conv_class_gemm_ex(feat, c_red, kernel, K, groups, c_out, src, m_pad, tile_info, n_tiles, wt, mirror, nullptr, zp, nullptr,
-                               &fin, stream);
+                               &fin, nullptr, stream);
 }
 
 // ------------------------------------------------------------------------------------------- half storage

@@ -58,10 +58,12 @@ def _wide(c):
 
 
 def eligible(weight) -> bool:
-    """fp32 [K, C_in, C_out] weight on a ROCm device whose forward product or input gradient runs on 128-column tiles."""
+    """fp32 [K, C_in, C_out] weight on a ROCm device whose forward product or input gradient reads planes: the direct-rows
+    kernel on 128-column tiles, or the persistent class GEMM (csrc/conv_class.hip), which takes every multiple of 32 both ways
+    on the maps that have a class plan (K > 1)."""
     return (_ENABLED and weight.is_cuda and weight.dtype == torch.float32 and weight.dim() == 3 and weight.is_contiguous()
             and weight.shape[0] <= 63 and weight.shape[1] % 32 == 0 and weight.shape[2] % 32 == 0
-            and (_wide(weight.shape[1]) or _wide(weight.shape[2])))
+            and (weight.shape[0] > 1 or _wide(weight.shape[1]) or _wide(weight.shape[2])))
 
 
 def _refresh(stream, device, entries=None, fn="ts_conv_split_planes_batch"):

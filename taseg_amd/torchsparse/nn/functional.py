@@ -397,14 +397,16 @@ _DIRECT_DOWN_MIN_ROWS = 8000        # smallest destination-row count any "down" 
 _DIRECT_FORCE = options.direct_conv == "force"        # every fitting 2x2x2 product on its direct plan (tests, probes)
 
 
-def class_conv(x, w, plan, f16, wt=False):
+def class_conv(x, w, plan, f16, wt=False, planes=None):
     """the convolution (wt: its transposed product) on a class plan: a direct plan's product IS the result; a three-group plan
     finishes inside the product where that pays (B.class_finish_pays), else through pass 2 - the same bits either way"""
     if plan["rows"] is not None:
-        return (B.conv_class_gemm_f16 if f16 else B.conv_class_gemm)(x, w, plan, weight_transposed=wt)
+        return B.conv_class_gemm_f16(x, w, plan, weight_transposed=wt) if f16 else \
+            B.conv_class_gemm(x, w, plan, weight_transposed=wt, planes=planes)
     if plan["groups"] == 3 and B.class_finish_pays(plan["n"], f16):
         return (B.conv_class_conv_f16 if f16 else B.conv_class_conv)(x, w, plan, weight_transposed=wt)
-    z = (B.conv_class_gemm_f16 if f16 else B.conv_class_gemm)(x, w, plan, weight_transposed=wt)
+    z = B.conv_class_gemm_f16(x, w, plan, weight_transposed=wt) if f16 else \
+        B.conv_class_gemm(x, w, plan, weight_transposed=wt, planes=planes)
     return (B.conv_gather_sum_f16 if f16 else B.conv_gather_sum)(z, plan["pos"], plan["n"])
 
 
@@ -517,7 +519,7 @@ class _SparseConv(Function):
                 if w32.data_ptr() != weight.data_ptr():
                     planes = None             # a converted copy: the planes belong to the parameter's own storage
                 if cls is not None:
-                    out = class_conv(f32, w32, cls, False)
+                    out = class_conv(f32, w32, cls, False, planes=planes)
                 else:
                     _planes.hint(w32, planes)
                     z = B.conv_pair_gemm(f32, w32, kmap.nbmaps_buf, kmap.nboffs, kmap.total, gather_col=gcol)
@@ -556,7 +558,7 @@ class _SparseConv(Function):
             else:
                 g32 = grad_out.contiguous().float()
                 if ctx.needs_input_grad[0] and ctx.cls is not None:
-                    grad_feats = class_conv(g32, weight, ctx.cls, False, True).to(ctx.in_dtype)
+                    grad_feats = class_conv(g32, weight, ctx.cls, False, True, planes=ctx.planes).to(ctx.in_dtype)
                 elif ctx.needs_input_grad[0]:
                     _planes.hint(weight, ctx.planes)
                     z = B.conv_pair_gemm(g32, weight, kmap.nbmaps_buf, kmap.nboffs, kmap.total, gather_col=gcol,

@@ -5,7 +5,7 @@ import argparse, ctypes, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import bench
-from taseg_amd import backend as B, _lib as L
+from taseg_amd import backend as B, _lib as L, planes as _planes
 from taseg_amd.torchsparse import SparseTensor
 from taseg_amd.torchsparse.nn import functional as spF
 
@@ -76,9 +76,14 @@ def class_gemm(feat, wt, c_out):
 
     def go():
         holder["z"] = (B.conv_class_gemm_f16(feat, w, plan, weight_transposed=bool(wt)) if args.half else
-                       B.conv_class_gemm(feat, w, plan, weight_transposed=bool(wt)))
+                       B.conv_class_gemm(feat, w, plan, weight_transposed=bool(wt), planes=_planes.planes_for(w)))
     go()
+    go.holder = holder
     return go, holder["z"]
+
+
+def holder_of(go):
+    return go.holder["z"]
 
 
 if args.half:
@@ -112,6 +117,23 @@ for wt, name, feat, c_out in ((0, "fwd", xf, args.cout), (1, "dgrad", gy, args.c
     e64 = [float((y[sel].double() - ref).abs().max()) / float(ref.abs().max()) for y in (y2, y1)]
     t_a, t_b = timed(two1), timed(lambda: gsum(z, table, n))
     t_c, t_d = timed(go), timed(lambda: gsum(zp, pos, n))
+    # the fp32 product with one workgroup per tile (ts_set_conv_impl(14)) beside the persistent walk: the same bits
+    walk = ""
+    if not args.half:
+        t_alt, same_alt = {}, {}
+        for impl in (14, 15):              # 14: class_gemm_kernel; 15: the walk's kernel with a workgroup per tile
+            B.set_conv_impl(impl)
+            try:
+                go()
+                z_alt = holder_of(go).clone()
+                t_alt[impl] = timed(go)
+            finally:
+                B.set_conv_impl(0)
+            go()
+            same_alt[impl] = bool(torch.equal(z_alt.view(torch.int32), holder_of(go).view(torch.int32)))
+        t_c2 = timed(go)
+        walk = (f"\n       product alone: one workgroup per tile {t_alt[14]:7.1f} us | walk's kernel, a workgroup per tile {t_alt[15]:7.1f} us | "
+                f"walk {t_c:7.1f} / {t_c2:7.1f} us ({t_alt[14] / t_c2:.2f}x)   same bits: {same_alt[14]}, {same_alt[15]}")
     conv = B.conv_class_conv_f16 if args.half else B.conv_class_conv
     yf = conv(feat, w, plan, weight_transposed=bool(wt))
     t_f = timed(lambda: conv(feat, w, plan, weight_transposed=bool(wt)))
@@ -121,4 +143,4 @@ for wt, name, feat, c_out in ((0, "fwd", xf, args.cout), (1, "dgrad", gy, args.c
         print(f"plan build {t_plan:.1f} us (once per batch and stride, staging stream)")
     print(f"{name:6s} two passes {t_a:7.1f} + {t_b:6.1f} = {t_a + t_b:7.1f} us   class-sorted {t_c:7.1f} + {t_d:6.1f} = {t_c + t_d:7.1f} us   "
           f"ratio {(t_a + t_b) / (t_c + t_d):.2f}x   finished in the product {t_f:7.1f} us ({(t_a + t_b) / t_f:.2f}x, same bits: {same})   "
-          f"max |diff| / max |y| {err:.1e}   vs float64: two passes {e64[0]:.1e}, class-sorted {e64[1]:.1e}")
+          f"max |diff| / max |y| {err:.1e}   vs float64: two passes {e64[0]:.1e}, class-sorted {e64[1]:.1e}" + walk)
