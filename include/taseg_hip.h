@@ -516,6 +516,47 @@ int ts_point_tail_forward(const void *y, const void *vox, const int32_t *idx, co
                           const float *invstd, const float *gamma, const float *beta, int64_t n, int32_t c, int64_t m, int32_t half,
                           void *out, uint8_t *mask, ts_stream_t stream);
 
+/* RPVNet's range <-> point transfers (rpvnet.py:32-91) as maps the point <-> voxel kernels above already serve.  A feature map
+ * [B, C, h, w] in channels-last memory is B h w rows of C: row b h w + y w + x.
+ *   ts_range_plan   pxpy [n, 3] float = (batch, px, py), px and py in [-1, 1]; one call per resolution (batch, h, w), coordinates only.
+ *                   pix [n] int32: the pixel row a point is averaged into by `point_to_range`,
+ *                     x = (int32)(((px + 1) / 2) * (float)(w - 1)), y likewise with h - float32, one rounding per operation,
+ *                     truncation (rpvnet.py:88).  ts_point_groups(pix, n, B h w) + ts_voxelize_mean_forward is the mean per pixel
+ *                     (zeros for a pixel without points) with that kernel's summation rule; ts_voxelize_mean_backward the adjoint.
+ *                   bidx int32 / bweight float [n, 8]: grid_sample's corners (bilinear, zeros padding, align_corners = False) in
+ *                     the layout of ts_trilinear_map: ix = ((px + 1) w - 1) / 2, x0 = floor(ix), x1 = x0 + 1, columns 0 .. 3 =
+ *                     nw, ne, sw, se with weights (x1 - ix)(y1 - iy), (ix - x0)(y1 - iy), (x1 - ix)(iy - y0), (ix - x0)(iy - y0) in
+ *                     float32; a corner outside the map, and columns 4 .. 7: index -1, weight 0.  ts_devoxelize_forward over the
+ *                     B h w rows is `range_to_point`; ts_devox_csr / ts_devox_order and ts_devoxelize_backward_* its adjoint.
+ *                   err [1] int32 (caller-zeroed, OR-ed into): 1 a batch index that is no integer of [0, batch), 2 a non-finite
+ *                     px / py, 4 px / py outside [-1, 1]; such a row takes no part either way (pix -1, all corners -1).  No host read.
+ *   ts_range_point_tail_forward   ts_point_tail_forward with one more gathered operand, one pass:
+ *                     out[i, :] = (sum_{k<8} weight[i, k] vox[idx[i, k], :] + sum_{j<4} bweight[i, j] pix[bidx[i, j], :])
+ *                                 + relu((y[i, :] - mean) invstd gamma + beta)
+ *                   over the m rows of vox and the mp rows of the map pix; the trilinear sum in k order, the bilinear sum in corner
+ *                   order from its own zero, the two added, then the BatchNorm term (rpvnet.py:651 left to right).  mask, half, c and
+ *                   alignment as ts_point_tail_forward. */
+int ts_range_plan(const float *pxpy, int64_t n, int32_t batch, int32_t h, int32_t w, int32_t *pix, int32_t *bidx, float *bweight,
+                  int32_t *err, ts_stream_t stream);
+int ts_range_point_tail_forward(const void *y, const void *vox, const int32_t *idx, const float *weight, const void *pix,
+                                const int32_t *bidx, const float *bweight, const float *mean, const float *invstd,
+                                const float *gamma, const float *beta, int64_t n, int32_t c, int64_t m, int64_t mp, int32_t half,
+                                void *out, uint8_t *mask, ts_stream_t stream);
+
+/* RPVNet's inputs from a batch's point rows (SemkittiFusionDataset.get_range_image, semantickitti_fusion.py:64-114), two launches for
+ * the whole batch.  feat [n, ld >= 5] float = x, y, z, reflectivity, ring per row; batch [n] int32; cut [B] float = the random cut of
+ * every sample ((rand() - 0.5) * 2 pi, rounded to float as numpy does when it adds it).
+ *   pxpy [n, 3] float   (batch, px, py): yaw = (float)atan2((double)y, -(double)x) + cut; yaw % 2 pi - pi; 0.5 (yaw / pi + 1) (W - 1)
+ *                       in float32, rounded half-to-even to the column; the row is the rounded ring; px = 2 (column / (W - 1) - 0.5),
+ *                       py likewise, in float64, cast once.  (numpy's own float32 arctan2 is not correctly rounded; this one is.)
+ *   table [B, H, W] int32, pre-filled with -1: the LAST row index that lands on a pixel (integer atomicMax: order-free)
+ *   image [B, 5, H, W] float: the winner's 25 (1 / depth - 0.4), 20 (reflectivity - 0.5) - float64 on the float32 depth quotient
+ *                       and value, cast once - and x, y, z; a pixel without rows: -10, -10, 0, 0, 0
+ *   err [1] int32, OR-ed into: 8 a ring above H - 1 or below 0, 16 a non-finite coordinate, 1 a batch index outside [0, B); such a
+ *                       row takes no part and gets px = py = NaN, which ts_range_plan drops again. */
+int ts_range_inputs(const float *feat, int64_t ld, const int32_t *batch, const float *cut, int64_t n, int32_t B, int32_t H, int32_t W,
+                    float *pxpy, int32_t *table, float *image, int32_t *err, ts_stream_t stream);
+
 /* The gate of Cylinder_TS's ReconBlock (cylinder_ts.py:368-384) on rows [n, c]: out = x * (sigmoid(u) + sigmoid(v) + sigmoid(w)),
  * one pass; the backward forms grad_x, grad_u, grad_v, grad_w from grad_out and the four inputs in one pass.  float arithmetic;
  * half != 0: IEEE half storage (c % 8 == 0), else float (c % 4 == 0); 16-byte aligned pointers. */

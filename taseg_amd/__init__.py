@@ -19,14 +19,15 @@ def install_as_dropin():
     from . import pcseg as pc
     from .pcseg.model import segmentor as seg
     from .pcseg.model.segmentor import fusion
-    from .pcseg.model.segmentor.fusion import spvcnn
+    from .pcseg.model.segmentor.fusion import rpvnet, spvcnn
     names = {"torchsparse": ts, "torchsparse.nn": ts.nn, "torchsparse.nn.functional": ts.nn.functional,
              "torchsparse.nn.utils": ts.nn.utils, "torchsparse.utils": ts.utils,
              "torchsparse.utils.quantize": ts.utils.quantize, "torchsparse.utils.collate": ts.utils.collate,
              "torchsparse.backend": ts.backend, "torchsparse.tensor": ts.tensor,
              "pcseg": pc, "pcseg.model": pc.model, "pcseg.loss": pc.loss, "pcseg.optim": pc.optim,
-             # (SPVCNN is reached by the reference's module path, not by the registry: pcseg/model/segmentor/__init__.py)
-             "pcseg.model.segmentor": seg, "pcseg.model.segmentor.fusion": fusion, "pcseg.model.segmentor.fusion.spvcnn": spvcnn}
+             # (SPVCNN and RPVNet are reached by the reference's module path, not by the registry: pcseg/model/segmentor/__init__.py)
+             "pcseg.model.segmentor": seg, "pcseg.model.segmentor.fusion": fusion, "pcseg.model.segmentor.fusion.spvcnn": spvcnn,
+             "pcseg.model.segmentor.fusion.rpvnet": rpvnet}
     for name, mod in names.items():
         sys.modules.setdefault(name, mod)
     return names

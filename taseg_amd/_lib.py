@@ -102,6 +102,10 @@ SIGNATURES = {
     "ts_voxelize_mean_forward": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i64, _i32, _vp, _vp, _sz, _vp]),
     "ts_voxelize_mean_backward": (_i32, [_vp, _vp, _vp, _i64, _i32, _i64, _i32, _vp, _vp]),
     "ts_point_tail_forward": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i64, _i32, _vp, _vp, _vp]),
+    "ts_range_plan": (_i32, [_vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "ts_range_inputs": (_i32, [_vp, _i64, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "ts_range_point_tail_forward": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i64, _i64, _i32, _vp,
+                                           _vp, _vp]),
     "ts_sigmoid3_gate_forward": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp]),
     "ts_sigmoid3_gate_backward": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "ts_conv3x3c32_packed_bytes": (_sz, []),

@@ -24,6 +24,7 @@ __all__ = [
     "eval_confusion", "eval_votes", "eval_confusion_rows", "eval_votes_rows",
     "voxelize_max_forward", "voxelize_max_backward", "sigmoid3_gate_forward", "sigmoid3_gate_backward",
     "point_groups", "voxelize_mean_piece_rows", "voxelize_mean_forward", "voxelize_mean_backward", "point_tail_forward",
+    "range_plan", "range_point_tail_forward", "range_inputs",
 ]
 
 
@@ -2277,3 +2278,67 @@ def _same_cols(t, like, who):
     if t.dtype != like.dtype or t.dim() != 2 or t.shape[1] != like.shape[1]:
         raise ValueError(f"{who}: vox must have the dtype and width of y ({like.dtype}, {like.shape[1]})")
     return t.contiguous()
+
+
+# --------------------------------------------------------------------------- RPVNet (csrc/rpvnet.hip)
+def range_plan(pxpy, batch, h, w, err=None):
+    """(pix [n] int32, bidx [n, 8] int32, bweight [n, 8] float32, err [1] int32) of range_pxpy [n, 3] float32 = (batch, px, py) at
+    one resolution (ts_range_plan): the pixel row of `point_to_range`'s mean and grid_sample's four bilinear corners in the layout of
+    `trilinear_map`, over batch * h * w channels-last rows.  err is OR-ed into (bits in include/taseg_hip.h) - hand one word through
+    the calls of a batch; it is never read here."""
+    L.require_device(pxpy)
+    pxpy = _f32(pxpy, "range_pxpy")
+    if pxpy.dim() != 2 or pxpy.shape[1] != 3:
+        raise ValueError("range_plan: range_pxpy must be [n, 3] (batch, px, py)")
+    n = pxpy.shape[0]
+    dev = pxpy.device
+    if err is None:
+        err = torch.zeros(1, dtype=torch.int32, device=dev)
+    pix = torch.empty(n, dtype=torch.int32, device=dev)
+    bidx = torch.empty((n, 8), dtype=torch.int32, device=dev)
+    bw = torch.empty((n, 8), dtype=torch.float32, device=dev)
+    L.check(L.load().ts_range_plan(L.ptr(pxpy), n, int(batch), int(h), int(w), L.ptr(pix), L.ptr(bidx), L.ptr(bw),
+                                   L.ptr(_i32(err, "err")), L.stream()), "ts_range_plan")
+    return pix, bidx, bw, err
+
+
+def range_point_tail_forward(y, vox, idx, weight, pix, bidx, bweight, mean, invstd, gamma, beta, want_mask=False):
+    """(out [n, c], mask | None): `point_tail_forward` with the bilinear read of the map rows pix [mp, c] through (bidx, bweight) of
+    `range_plan` added to the trilinear sum before the BatchNorm term (ts_range_point_tail_forward).  y, vox and pix of one dtype."""
+    L.require_device(y, vox, idx, weight, pix, bidx, bweight, mean, invstd, gamma, beta)
+    y, half = _rows_f32_f16(y, "y")
+    vox, pix = _same_cols(vox, y, "range_point_tail_forward"), _same_cols(pix, y, "range_point_tail_forward")
+    idx, weight, bidx, bweight = _i32(idx, "idx"), _f32(weight, "weight"), _i32(bidx, "bidx"), _f32(bweight, "bweight")
+    mean, invstd, gamma, beta = (_f32(t, "statistics") for t in (mean, invstd, gamma, beta))
+    n, c = y.shape
+    if any(t.shape != (n, 8) for t in (idx, weight, bidx, bweight)) or any(t.shape != (c,) for t in (mean, invstd, gamma, beta)):
+        raise ValueError("range_point_tail_forward: maps [n, 8] and per-channel vectors [c] must match y [n, c]")
+    out = torch.empty_like(y)
+    mask = torch.empty(n * (c // (8 if half else 4)), dtype=torch.uint8, device=y.device) if want_mask else None
+    L.check(L.load().ts_range_point_tail_forward(L.ptr(y), L.ptr(vox), L.ptr(idx), L.ptr(weight), L.ptr(pix), L.ptr(bidx),
+                                                 L.ptr(bweight), L.ptr(mean), L.ptr(invstd), L.ptr(gamma), L.ptr(beta), n, c,
+                                                 vox.shape[0], pix.shape[0], half, L.ptr(out), L.ptr(mask), L.stream()),
+            "ts_range_point_tail_forward")
+    return out, mask
+
+
+def range_inputs(feat, batch, cut, b, h, w, err=None):
+    """(range_image [b, 5, h, w] float32, range_pxpy [n, 3] float32, err [1] int32) from point rows feat [n, >= 5] float32 (x, y, z,
+    reflectivity, ring), their samples batch [n] int32 and the samples' cuts cut [b] float32 (ts_range_inputs: two kernels behind one
+    fill of the winner table)."""
+    L.require_device(feat, batch, cut)
+    if feat.dtype != torch.float32 or feat.dim() != 2 or feat.shape[1] < 5 or feat.stride(1) != 1:
+        raise ValueError("range_inputs: feat must be float32 rows [n, >= 5] (x, y, z, reflectivity, ring)")
+    batch, cut = _i32(batch, "batch"), _f32(cut, "cut")
+    n, b, h, w = feat.shape[0], int(b), int(h), int(w)
+    if batch.shape != (n,) or cut.shape != (b,):
+        raise ValueError("range_inputs: one batch index per row and one cut per sample")
+    dev = feat.device
+    if err is None:
+        err = torch.zeros(1, dtype=torch.int32, device=dev)
+    table = torch.full((b, h, w), -1, dtype=torch.int32, device=dev)
+    image = torch.empty((b, 5, h, w), dtype=torch.float32, device=dev)
+    pxpy = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    L.check(L.load().ts_range_inputs(L.ptr(feat), feat.stride(0) if n else 5, L.ptr(batch), L.ptr(cut), n, b, h, w, L.ptr(pxpy),
+                                     L.ptr(table), L.ptr(image), L.ptr(_i32(err, "err")), L.stream()), "ts_range_inputs")
+    return image, pxpy, err

@@ -13,7 +13,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 PKG = os.path.dirname(HERE)
 ROOT = os.path.dirname(PKG)
-SOURCES = ["hash.hip", "coords.hip", "pointops.hip", "conv.hip", "conv_pairs.hip", "bn.hip", "quantize.hip", "stage.hip", "image.hip", "conv_pairs_h.hip", "conv_pairs_s.hip", "conv_class.hip", "optim.hip", "rccl.hip", "block.hip", "loss.hip", "evaltail.hip", "conv2d_rows.hip", "shuffle_cat.hip", "mix.hip", "moving.hip", "compact.hip", "kd_stage.hip", "tiaf_stage.hip", "nusc_tiaf_stage.hip", "cylinder.hip", "cylinder_stage.hip", "spvcnn.hip"]
+SOURCES = ["hash.hip", "coords.hip", "pointops.hip", "conv.hip", "conv_pairs.hip", "bn.hip", "quantize.hip", "stage.hip", "image.hip", "conv_pairs_h.hip", "conv_pairs_s.hip", "conv_class.hip", "optim.hip", "rccl.hip", "block.hip", "loss.hip", "evaltail.hip", "conv2d_rows.hip", "shuffle_cat.hip", "mix.hip", "moving.hip", "compact.hip", "kd_stage.hip", "tiaf_stage.hip", "nusc_tiaf_stage.hip", "cylinder.hip", "cylinder_stage.hip", "spvcnn.hip", "rpvnet.hip", "range_stage.hip"]
 # measured-and-shelved kernels (HISTORY.md section 3.1 step 11) live in tools/experiments/ and are NOT part of libtaseg_hip.so:
 # `python -m taseg_amd.csrc.build --experiments` builds them into tools/experiments/build/libtaseg_exp.so for the probes there
 EXP_DIR = os.path.join(ROOT, "tools", "experiments")
@@ -26,7 +26,8 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 EXTRA = {"pointops.hip": ["-ffp-contract=off"], "quantize.hip": ["-ffp-contract=off"],
          "mix.hip": ["-ffp-contract=off"], "moving.hip": ["-ffp-contract=off"], "tiaf_stage.hip": ["-ffp-contract=off"],
          "nusc_tiaf_stage.hip": ["-ffp-contract=off"], "cylinder_stage.hip": ["-ffp-contract=off"],
-         "spvcnn.hip": ["-ffp-contract=off"]}
+         "spvcnn.hip": ["-ffp-contract=off"], "rpvnet.hip": ["-ffp-contract=off"],
+         "range_stage.hip": ["-ffp-contract=off"]}
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
          "-I", os.path.join(ROOT, "include")]
 
@@ -37,7 +38,7 @@ def _newer(src, dst):
 
 def _deps():
     return [os.path.join(HERE, "common.h"), os.path.join(HERE, "compact.h"), os.path.join(HERE, "stage_rules.h"),
-            os.path.join(HERE, "quantize_keys.h"),
+            os.path.join(HERE, "quantize_keys.h"), os.path.join(HERE, "point_tail.h"),
             os.path.join(ROOT, "include", "taseg_hip.h"), os.path.abspath(__file__)]
 
 

@@ -7,18 +7,9 @@
 // Both are bandwidth kernels in the idiom of csrc/cylinder.hip: 16-byte accesses per lane, one group of c / V lanes per row, voxel or
 // piece, every output element written exactly once, no atomics, no fill.  Compiled with -ffp-contract=off (csrc/build.py): every
 // product and sum below keeps its own rounding, so tests/spvcnn_ref.py restates the mean bit for bit.
-#include <hip/hip_fp16.h>
-
-#include "common.h"
+#include "point_tail.h"
 
 namespace {
-
-template <typename T, int V>
-using ts_vec = T __attribute__((ext_vector_type(V)));
-
-template <typename T> struct Lanes;                     // elements of one 16-byte access
-template <> struct Lanes<float> { static constexpr int V = 4; };
-template <> struct Lanes<_Float16> { static constexpr int V = 8; };
 
 int g_piece_rows = 32;                                  // P: rows per piece (16, 32 or 64; profiles/spvcnn_step.txt has the comparison)
 
@@ -184,79 +175,7 @@ __global__ __launch_bounds__(256) void voxel_mean_bwd_kernel(const T *__restrict
   *(vec *)(gfeat + i * c + V * lane) = g;
 }
 
-// ------------------------------------------------------------------------------------------------------------ point tail
-// out[i, :] = sum_k w[i, k] vox[idx[i, k], :] + relu((y[i, :] - mean) invstd gamma + beta): the trilinear sum over k = 0 .. 7 in k
-// order with float32 accumulation, a missing corner (idx < 0, or w == 0) adding nothing - the arithmetic of devoxelize_fwd_kernel
-// (csrc/pointops.hip) - and the BatchNorm term in the operation order of bn_act_fwd_kernel (csrc/bn.hip).  mask (optional) takes one
-// sign bit of the BatchNorm term per element, a byte per 16-byte chunk of a row as ts_bn_act_forward lays it out: what
-// ts_bn_act_train_backward needs to send the gradient of `out` through the ReLU.  A lane keeps mean, invstd, gamma and beta of its
-// V channels in registers and walks the rows grid-stride.
-template <typename T>
-__global__ __launch_bounds__(256) void point_tail_fwd_kernel(const T *__restrict__ y, const T *__restrict__ vox,
-                                                             const int *__restrict__ idx, const float *__restrict__ w,
-                                                             const float *__restrict__ mean, const float *__restrict__ invstd,
-                                                             const float *__restrict__ gamma, const float *__restrict__ beta,
-                                                             int64_t n, int c, int64_t m, T *__restrict__ out,
-                                                             unsigned char *__restrict__ mask) {
-  constexpr int V = Lanes<T>::V;
-  typedef ts_vec<T, V> vec;
-  const int cq = c / V, groups = 256 / cq;
-  const int grp = threadIdx.x / cq, lane = threadIdx.x - grp * cq;
-  if (grp >= groups) return;
-  float mu[V], is[V], ga[V], be[V];
-#pragma unroll
-  for (int j = 0; j < V; ++j) {
-    mu[j] = mean[V * lane + j];
-    is[j] = invstd[V * lane + j];
-    ga[j] = gamma[V * lane + j];
-    be[j] = beta[V * lane + j];
-  }
-  const int64_t step = (int64_t)gridDim.x * groups;
-  for (int64_t i = (int64_t)blockIdx.x * groups + grp; i < n; i += step) {
-    const int4 ia = *(const int4 *)(idx + i * 8), ib = *(const int4 *)(idx + i * 8 + 4);
-    const float4 wa = *(const float4 *)(w + i * 8), wb = *(const float4 *)(w + i * 8 + 4);
-    const int id[8] = {ia.x, ia.y, ia.z, ia.w, ib.x, ib.y, ib.z, ib.w};
-    const float wk[8] = {wa.x, wa.y, wa.z, wa.w, wb.x, wb.y, wb.z, wb.w};
-    const vec yv = *(const vec *)(y + i * c + V * lane);
-    vec f[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-#pragma unroll
-      for (int j = 0; j < V; ++j) f[k][j] = (T)0;
-      if (id[k] >= 0 && id[k] < m && wk[k] != 0.f) f[k] = *(const vec *)(vox + (int64_t)id[k] * c + V * lane);
-    }
-    float acc[V];
-#pragma unroll
-    for (int j = 0; j < V; ++j) acc[j] = 0.f;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-#pragma unroll
-      for (int j = 0; j < V; ++j) acc[j] += wk[k] * (float)f[k][j];
-    }
-    vec o;
-    unsigned mk = 0;
-#pragma unroll
-    for (int j = 0; j < V; ++j) {
-      float t = ((float)yv[j] - mu[j]) * is[j] * ga[j] + be[j];
-      t = fmaxf(t, 0.f);
-      mk |= (t > 0.f ? 1u : 0u) << j;
-      o[j] = (T)(acc[j] + t);
-    }
-    if (mask) mask[i * cq + lane] = (unsigned char)mk;
-    *(vec *)(out + i * c + V * lane) = o;
-  }
-}
-
-int rows_check(const char *who, int64_t n, int32_t c, int64_t m, int32_t half) {
-  TS_REQUIRE(n >= 0 && m >= 0 && c > 0 && n < (1LL << 30) && m < (1LL << 31) - 1, TS_ERR_INVALID_ARGUMENT, "%s: bad sizes", who);
-  TS_REQUIRE(c % (half ? 8 : 4) == 0 && c <= 1024, TS_ERR_UNSUPPORTED,
-             "%s: C must be a multiple of %d (16-byte pieces of a row), <= 1024", who, half ? 8 : 4);
-  return TS_OK;
-}
-
-inline bool aligned16(const void *a, const void *b = nullptr, const void *c = nullptr, const void *d = nullptr) {
-  return ((((uintptr_t)a) | ((uintptr_t)b) | ((uintptr_t)c) | ((uintptr_t)d)) & 15) == 0;
-}
+// The point tail (ts_point_tail_forward) launches point_tail_fwd_kernel<T, false> of point_tail.h, which csrc/rpvnet.hip shares.
 
 }  // namespace
 
@@ -349,11 +268,12 @@ extern "C" int ts_point_tail_forward(const void *y, const void *vox, const int32
   const int groups = 256 / (c / (half ? 8 : 4));
   const unsigned grid = (unsigned)std::min<int64_t>(ts_cdiv(n, (int64_t)groups), 8192);
   if (half)
-    point_tail_fwd_kernel<_Float16><<<grid, 256, 0, stream>>>((const _Float16 *)y, (const _Float16 *)vox, idx, weight, mean, invstd,
-                                                              gamma, beta, n, c, m, (_Float16 *)out, mask);
+    point_tail_fwd_kernel<_Float16, false><<<grid, 256, 0, stream>>>((const _Float16 *)y, (const _Float16 *)vox, idx, weight, nullptr,
+                                                                     nullptr, nullptr, 0, mean, invstd, gamma, beta, n, c, m,
+                                                                     (_Float16 *)out, mask);
   else
-    point_tail_fwd_kernel<float><<<grid, 256, 0, stream>>>((const float *)y, (const float *)vox, idx, weight, mean, invstd, gamma, beta,
-                                                           n, c, m, (float *)out, mask);
+    point_tail_fwd_kernel<float, false><<<grid, 256, 0, stream>>>((const float *)y, (const float *)vox, idx, weight, nullptr, nullptr,
+                                                                  nullptr, 0, mean, invstd, gamma, beta, n, c, m, (float *)out, mask);
   TS_CHECK_LAUNCH("ts_point_tail_forward");
   return TS_OK;
 }

@@ -246,3 +246,13 @@ def synth_nusc_sequence(n_key=6, frames_per_key=10, metres_per_frame=0.5, yaw_de
                        l2e_q=np.tile(l2e_q, (len(keys), 1)), l2e_t=np.tile(l2e_t, (len(keys), 1)), e2g_q=e2g_q[keys],
                        e2g_t=e2g_t[keys])
     return seq, world
+
+
+def ring_column(points, n_beams=64, rows=64):
+    """A ring (laser) index per point of a synthetic scan, float32 [n]: the elevation angle binned into `n_beams` equal steps between
+    the scan's own extremes, spread over `rows` image rows - the fifth feature column RPVNet's range image is built from."""
+    xyz = np.asarray(points)[:, :3].astype(np.float64)
+    pitch = np.arctan2(xyz[:, 2], np.hypot(xyz[:, 0], xyz[:, 1]))
+    lo, hi = pitch.min(), pitch.max()
+    beam = np.clip(np.floor((pitch - lo) / max(hi - lo, 1e-12) * n_beams), 0, n_beams - 1)
+    return (beam * (rows // n_beams)).astype(np.float32)

@@ -223,7 +223,7 @@ def evaluate(model, batches: Iterable[Dict], num_class: int, tta_votes: int = 0,
     Without it `save_dir` is ignored in a validation run.
     remap: a {class: raw id} dictionary (data.semantickitti.LEARNING_MAP_INV) or a table as remap_lut builds; the payloads of a
     TTA run or of predictions=True go through it (remap_labels: R/tta_remap.py --inverse) before they are returned or written.
-    on_device=True (all seven segmentors: MinkUNet, MinkUNetMs, MinkUNetMsMm, MinkUNetMsMmNus, MinkUNetMsKd, Cylinder_TS, SPVCNN - every
+    on_device=True (all eight segmentors: MinkUNet, MinkUNetMs, MinkUNetMsMm, MinkUNetMsMmNus, MinkUNetMsKd, Cylinder_TS, SPVCNN, RPVNet - every
     forward that takes `device_tail`): the tail of every batch stays on the device (csrc/evaltail.hip).  Validation adds into a resident
     confusion matrix - no device -> host copy per batch, ONE host read at the end (after parallel.reduce_confusion); with
     predictions=True the label bytes and the per-scan counts of each batch follow it to the host, one batch in flight.  TTA sums

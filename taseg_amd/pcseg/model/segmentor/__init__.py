@@ -4,7 +4,8 @@ scope.
 
 SPVCNN is built too (`fusion/spvcnn/`), but is not in this registry: it is constructed through the reference's module path,
 `from pcseg.model.segmentor.fusion.spvcnn import SPVCNN; SPVCNN(model_cfgs, num_class)`, and `build_segmentor(NAME="SPVCNN")` keeps
-raising NotImplementedError - two existing tests pin that and `_OUT_OF_SCOPE` as they stand (tests/test_spvcnn_host.py says which)."""
+raising NotImplementedError - two existing tests pin that and `_OUT_OF_SCOPE` as they stand (tests/test_spvcnn_host.py says which).
+RPVNet (`fusion/rpvnet/`) is built and reached the same way, for the same reason."""
 from .base_segmentors import BaseSegmentor
 from .voxel.cylinder3d.cylinder_ts import Cylinder_TS
 from .voxel.minkunet.minkunet import MinkUNet

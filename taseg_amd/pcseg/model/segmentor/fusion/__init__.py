@@ -1,1 +1,1 @@
-"""Point-voxel fusion segmentors (reference pcseg/model/segmentor/fusion): SPVCNN.  RPVNet is not built."""
+"""Point-voxel fusion segmentors (reference pcseg/model/segmentor/fusion): SPVCNN and RPVNet (range-point-voxel)."""

@@ -1,0 +1,244 @@
+"""RPVNet segmentor (reference pcseg/model/segmentor/fusion/rpvnet/rpvnet.py:392-752): MinkUNet plus a point branch plus a range
+branch, the three meeting four times per pass.
+
+Module tree, attribute names and therefore every state_dict key, their order and shapes are the reference's for both blocks
+(`stem.0.kernel` .. `up4.1.*`, `classifier.0.weight`, `point_transforms.0.0.weight` .. `point_transforms.3.1.*`,
+`range_branch.stem.0.conv1.weight` .. `range_branch.up4.bn1.num_batches_tracked`), so reference checkpoints load here and vice versa.
+The voxel branch, index plan, losses and the evaluation tail are `minkunet.py`'s, `point_to_voxel` is SPVCNN's, and the range branch
+(`SalsaNext`, rpvnet.py:205-253) is built from the three blocks of `minkunet/unet2d.py` - the reference's ResContextBlock / ResBlock /
+UpBlock with the same parameter names - in the memory layout `options.image_layout` names.  What this file adds:
+
+  range plans      `prepare()` builds, per resolution of the range branch a hand-over happens at (full, 1/16, 1/4), the plan of
+                   `functional.range_plan` from `range_pxpy` alone: pixel + grouping for `point_to_range`, bilinear corners + inverse
+                   map for `range_to_point`.  The flag word of rows left out is carried as plan['range_err'] (never read here).
+  point_to_range   `spvoxelize_mean` over B h w pixel rows - the reference's `range_lib` extension adds feat / count with one float
+                   atomic per element; here the sum has ts_voxelize_mean_forward's fixed order and a training step has the same bits
+                   every run.
+  the hand-over    z_k.F = voxel_to_point(x).F + range_to_point(r) + point_transforms[k](z_{k-1}.F), four times per pass: the Linear as
+                   in SPVCNN, then ONE node on ts_range_point_tail_forward (`functional.range_point_tail`).
+
+Reproduced from the reference, not repaired: `forward_ensemble` passes `ensemble=True` to `forward`, which has no such parameter
+(rpvnet.py:751-752: TypeError); with MULTI_SCALE other than 'concat' no `classifier` is built and `forward` fails on a missing
+attribute (:567-569, :706-716); `grid_sample` runs with align_corners=False on coordinates the dataset built for align_corners=True
+(:44, semantickitti_fusion.py:103-104); `point_to_range` truncates ((px + 1) / 2 * (w - 1)).int() where the dataset rounded (:88), so
+a share of the columns lands one pixel below its own index.  `range_to_point` there is a Python loop over the samples and assumes
+batch-sorted points; here it is one launch, every point reading its own sample's map.
+
+Stated difference: with IF_DIST False the reference's `point_transforms` put a sparse-tensor BatchNorm behind a plain tensor and raise
+AttributeError at the first pass (:574); here they are nn.BatchNorm1d under the same keys.
+"""
+import torch
+from torch import nn
+
+from taseg_amd.options import options
+from taseg_amd import torchsparse
+from taseg_amd.torchsparse import PointTensor, SparseTensor
+from taseg_amd.torchsparse import nn as spnn
+from taseg_amd.torchsparse.nn import functional as spF
+from ...voxel.minkunet.minkunet import MinkUNetBackbone, unvoxelise_predictions
+from ...voxel.minkunet.unet2d import ResBlock, ResContextBlock, UNet2D, UpBlock
+from ..spvcnn.spvcnn import SPVCNN
+from ..spvcnn.utils import point_to_voxel
+
+__all__ = ["RPVNet", "SalsaNext"]
+
+_PLANES = [32, 32, 64, 128, 256, 256, 128, 96, 96]
+
+
+def _pooled(size: int, times: int = 4) -> int:
+    """the size AvgPool2d(3, stride 2, padding 1) leaves, `times` times over"""
+    for _ in range(times):
+        size = (size - 1) // 2 + 1
+    return size
+
+
+class SalsaNext(UNet2D):
+    """rpvnet.py:205-253: UNet2D's stem, four pooled stages, mid stage and four up blocks at widths int(cr * x), no classifier.  The
+    layout handling (parameters take `options.image_layout`'s format when the module moves to the device) is UNet2D's."""
+
+    def __init__(self, model_cfgs, input_channels=5):
+        nn.Module.__init__(self)
+        self.in_channels = input_channels
+        self.cr = model_cfgs.get("cr", 1.75)
+        self.cs = cs = [int(self.cr * x) for x in _PLANES]
+        self.stem = nn.Sequential(ResContextBlock(input_channels, cs[0]), ResContextBlock(cs[0], cs[0]),
+                                  ResContextBlock(cs[0], cs[0]))
+        self.stage1 = ResBlock(cs[0], cs[1], 0.2, pooling=True, drop_out=False)
+        self.stage2 = ResBlock(cs[1], cs[2], 0.2, pooling=True)
+        self.stage3 = ResBlock(cs[2], cs[3], 0.2, pooling=True)
+        self.stage4 = ResBlock(cs[3], cs[4], 0.2, pooling=True)
+        self.mid_stage = ResBlock(cs[4], cs[4], 0.2, pooling=False)
+        self.up1 = UpBlock(cs[4], cs[5], 0.2, mid_filters=cs[4] // 4 + cs[4])
+        self.up2 = UpBlock(cs[5], cs[6], 0.2, mid_filters=cs[5] // 4 + cs[3])
+        self.up3 = UpBlock(cs[6], cs[7], 0.2, mid_filters=cs[6] // 4 + cs[2])
+        self.up4 = UpBlock(cs[7], cs[8], 0.2, drop_out=False, mid_filters=cs[7] // 4 + cs[1])
+        self.num_point_features = cs[8]
+
+    def forward(self, batch_dict):
+        """the range branch alone (rpvnet.py:234-253): `point_features` = the last map read at every point"""
+        image = batch_dict["range_image"].contiguous(memory_format=self._set_layout())
+        x5, skips = self._encode(image)
+        u4 = self._decode_u4(self._decode_u2(x5, skips), skips)
+        plan = spF.range_plan(batch_dict["range_pxpy"], *image.shape[0:1], *image.shape[2:], backward=torch.is_grad_enabled())
+        batch_dict["point_features"] = spF.range_to_point(u4, plan)
+        return batch_dict
+
+
+class RPVNet(MinkUNetBackbone):
+    def __init__(self, model_cfgs, num_class: int):
+        cfgs = _with_defaults(model_cfgs)
+        super().__init__(cfgs, num_class)              # stem .. up4, classifier, dropout, losses: rpvnet.py:432-624 == minkunet.py
+        self.model_cfgs = model_cfgs
+        self.name = "rpvnet"
+        cs = [int(cfgs.get("cr") * x) for x in cfgs.get("PLANES", _PLANES)]
+        exp = self.block.expansion
+        if_dist = model_cfgs.IF_DIST
+        self.multi_scale = model_cfgs.get("MULTI_SCALE", "concat")
+        if self.multi_scale != "concat":
+            del self.classifier                        # (:567-569: built for 'concat' only; forward then fails as the reference's does)
+
+        def transform(inc, outc):
+            return nn.Sequential(nn.Linear(inc, outc), nn.SyncBatchNorm(outc) if if_dist else nn.BatchNorm1d(outc), nn.ReLU(True))
+
+        self.point_transforms = nn.ModuleList([transform(self.in_feature_dim, cs[0]), transform(cs[0], cs[4] * exp),
+                                               transform(cs[4] * exp, cs[6] * exp), transform(cs[6] * exp, cs[8] * exp)])
+        self.range_branch = SalsaNext(model_cfgs=model_cfgs, input_channels=5)
+        if if_dist:
+            self.range_branch = nn.SyncBatchNorm.convert_sync_batchnorm(self.range_branch)
+        self.grid_sample_mode = "bilinear"
+        self.weight_initialization()
+
+    def prepare(self, batch_dict):
+        """SPVCNN's plan (MinkUNet's index plan plus the point -> voxel groupings) plus plan['range'] = the three range plans keyed by
+        (h, w) - coordinates only; left under batch_dict['_plan']"""
+        plan = SPVCNN.prepare(self, batch_dict)
+        image, pxpy = batch_dict["range_image"], batch_dict["range_pxpy"]
+        b, h, w = int(image.shape[0]), int(image.shape[2]), int(image.shape[3])
+        h16, w16 = _pooled(h), _pooled(w)
+        err = torch.zeros(1, dtype=torch.int32, device=pxpy.device)
+        ranges = {}
+        for hh, ww in ((h, w), (h16, w16), (4 * h16, 4 * w16)):
+            # (at 1/16 hundreds of points share four corners: the cell-reduced adjoint, as MinkUNet's stride 16)
+            ranges[(hh, ww)] = spF.range_plan(pxpy, b, hh, ww, backward=self.training, err=err,
+                                              cells=options.devox_cells and (hh, ww) == (h16, w16) and pxpy.is_cuda)
+        plan["range"], plan["range_err"] = ranges, err
+        batch_dict["_plan"] = plan
+        return plan
+
+    def _tail(self, k: int, x: SparseTensor, z: PointTensor, fmap: torch.Tensor, ranges: dict) -> PointTensor:
+        """z_k.F = voxel_to_point(x, z_{k-1}).F + range_to_point(fmap) + point_transforms[k](z_{k-1}.F)   (rpvnet.py:648-704)"""
+        lin, bn = self.point_transforms[k][0], self.point_transforms[k][1]
+        if z.F.is_cuda and z.F.dtype in (torch.float32, torch.float16) and spF._dense_ok(lin.in_features, lin.out_features):
+            y = spF._PointwiseConv.apply(z.F, lin.weight.t().contiguous(), spF._identity_rows(z.F.shape[0], z.F.device))
+            y = y + lin.bias.to(y.dtype)
+        else:
+            y = torch.nn.functional.linear(z.F, lin.weight, lin.bias)
+        order = (z.additional_features.get("devox_order") or {}).get(x.s)
+        rplan = ranges[(int(fmap.shape[2]), int(fmap.shape[3]))]
+        out = PointTensor(spF.range_point_tail(y, bn, x.F, z.idx_query[x.s], z.weights[x.s], order, fmap, rplan), z.C,
+                          idx_query=z.idx_query, weights=z.weights)
+        out.additional_features = z.additional_features
+        return out
+
+    def _to_range(self, z: PointTensor, ranges: dict, b: int, h: int, w: int) -> torch.Tensor:
+        """point_to_range (rpvnet.py:73-91) in the range branch's layout"""
+        fmap = spF.point_to_range(z.F, ranges[(h, w)], b, h, w)
+        return fmap if options.image_layout == "nhwc" else fmap.contiguous()
+
+    def forward(self, batch_dict, return_logit=False, return_tta=False, defer=False, device_tail=None):
+        x = batch_dict["lidar"]
+        rb = self.range_branch
+        range_image = batch_dict["range_image"].contiguous(memory_format=rb._set_layout())
+        b, h, w = int(range_image.shape[0]), int(range_image.shape[2]), int(range_image.shape[3])
+        x.F = x.F[:, :self.in_feature_dim]
+        plan = batch_dict.get("_plan") or self.prepare(batch_dict)
+        ranges = plan["range"]
+        x0 = SparseTensor(spF.spvoxelize(x.F, plan["vox_idx"], plan["vox_counts"]), plan["coords"], 1)     # initial_voxelize
+        x0.cmaps, x0.kmaps = plan["cmaps"], plan["kmaps"]
+        z = PointTensor(x.F, plan["point_coords"], idx_query=plan["tri_idx"], weights=plan["tri_w"])
+        cache = z.additional_features
+        cache["devox_order"], cache["groups"] = plan["tri_order"], {}
+        for key, (idx, counts, groups) in plan["p2v"].items():
+            cache["idx_query"][key], cache["counts"][key], cache["groups"][key] = idx, counts, groups
+
+        r_x0 = rb.stem(range_image)
+        x0 = spnn.conv_bn_act(self.stem[0], self.stem[1], x0, relu=True)
+        x0 = spnn.conv_bn_act(self.stem[3], self.stem[4], x0, relu=True)
+
+        z0 = self._tail(0, x0, z, r_x0, ranges)
+
+        x1 = point_to_voxel(x0, z0)
+        x1 = self.stage1(x1)
+        x2 = self.stage2(x1)
+        x3 = self.stage3(x2)
+        x4 = self.stage4(x3)
+        r_x1 = self._to_range(z0, ranges, b, h, w)
+        r_x1, r_s1 = rb.stage1(r_x1)
+        r_x2, r_s2 = rb.stage2(r_x1)
+        r_x3, r_s3 = rb.stage3(r_x2)
+        r_x4, r_s4 = rb.stage4(r_x3)
+        r_x4 = rb.mid_stage(r_x4)
+
+        z1 = self._tail(1, x4, z0, r_x4, ranges)
+
+        y1 = point_to_voxel(x4, z1)
+        r_y1 = self._to_range(z1, ranges, b, int(r_x4.shape[2]), int(r_x4.shape[3]))
+        y1.F = torch.nn.functional.dropout(y1.F, self.dropout.p, self.training, False)
+        y1 = self.up1[1](torchsparse.cat([self.up1[0](y1), x3]))
+        y2 = self.up2[1](torchsparse.cat([self.up2[0](y1), x2]))
+        r_y1 = rb.up1(r_y1, r_s4)
+        r_y2 = rb.up2(r_y1, r_s3)
+
+        z2 = self._tail(2, y2, z1, r_y2, ranges)
+
+        y3 = point_to_voxel(y2, z2)
+        r_y3 = self._to_range(z2, ranges, b, int(r_y2.shape[2]), int(r_y2.shape[3]))
+        y3.F = torch.nn.functional.dropout(y3.F, self.dropout.p, self.training, False)
+        y3 = self.up3[1](torchsparse.cat([self.up3[0](y3), x1]))
+        y4 = self.up4[1](torchsparse.cat([self.up4[0](y3), x0]))
+        r_y3 = rb.up3(r_y3, r_s2)
+        r_y4 = rb.up4(r_y3, r_s1)
+
+        z3 = self._tail(3, y4, z2, r_y4, ranges)
+
+        if self.multi_scale == "concat":
+            out = self.classifier(torch.cat([z1.F, z2.F, z3.F], dim=1))
+        elif self.multi_scale == "sum":
+            out = self.classifier(self.l1(z1.F) + self.l2(z2.F) + z3.F)
+        elif self.multi_scale == "se":
+            attn = torch.cat([z1.F, z2.F, z3.F], dim=1)
+            attn = self.attn(self.pool(attn.permute(1, 0)).permute(1, 0))
+            out = self.classifier(torch.cat([z1.F, z2.F, z3.F], dim=1) * attn)
+        else:
+            out = self.classifier(z3.F)
+
+        if self.training:
+            target = batch_dict["targets"].F.long().cuda(non_blocking=True)
+            return self._train_outputs(out, target, batch_dict["lidar"].C[:, :3].float(), batch_dict["offset"])
+
+        if device_tail is not None:       # evaluation on the device (DeviceEvalTail): nothing is un-voxelised to the host
+            return device_tail.run(out, x.C[:, -1], batch_dict["inverse_map"], batch_dict["targets_mapped"], batch_dict["num_points"],
+                                   names=batch_dict["name"])
+        return unvoxelise_predictions(out, x.C[:, -1], batch_dict["inverse_map"], batch_dict["targets_mapped"],
+                                      batch_dict["num_points"], return_logit or return_tta, names=batch_dict["name"], defer=defer)
+
+    def forward_ensemble(self, batch_dict):
+        return self.forward(batch_dict, ensemble=True)
+
+
+class _Defaults:
+    """model_cfgs with the reference RPVNet's own default for `cr` (1.75, rpvnet.py:442) where MinkUNetBackbone's is 1.0; every other
+    default (NUM_LAYER, BLOCK, PLANES, pres / vres, DROPOUT_P, the loss) is the same in both files"""
+
+    def __init__(self, cfgs):
+        self._cfgs = cfgs
+
+    def get(self, key, default=None):
+        return self._cfgs.get(key, 1.75 if key == "cr" else default)
+
+    def __getattr__(self, name):
+        return getattr(self._cfgs, name)
+
+
+def _with_defaults(model_cfgs):
+    return _Defaults(model_cfgs)

@@ -32,7 +32,7 @@ from ..utils import make_ntuple
 from .utils import get_kernel_offsets
 
 __all__ = ["conv3d", "conv_geometry", "conv_block_ok", "conv_block_eval", "sphash", "sphashquery", "spcount", "spvoxelize", "spdevoxelize", "spdevoxelize_cat", "calc_ti_weights",
-           "spdownsample", "KernelMap", "build_kernel_map", "build_pyramid", "point_linear", "spvoxelize_max", "sigmoid3_gate", "spvoxelize_mean", "point_tail",
+           "spdownsample", "KernelMap", "build_kernel_map", "build_pyramid", "point_linear", "spvoxelize_max", "sigmoid3_gate", "spvoxelize_mean", "point_tail", "range_plan", "range_to_point", "point_to_range", "range_point_tail",
            "gather_rows"]
 
 _fwd = torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
@@ -1220,6 +1220,47 @@ def spvoxelize_mean(feats: torch.Tensor, idx: torch.Tensor, num: int, groups=Non
         return _VoxelizeMean.apply(feats, idx, groups)
 
 
+def _tail_batch_stats(y, running_mean, running_var, nbt, momentum, eps):
+    """(mean, invstd) [2, c] float32 of the rows y from ts_bn_sync_stats + ts_bn_finalize, which also moves the running buffers"""
+    n, c = y.shape
+    sfx = "_f16" if y.dtype == torch.float16 else ""
+    L = B.L
+    lib = L.load()
+    pack = torch.empty(2 * c + 1, dtype=torch.float64, device=y.device)
+    stats = torch.empty((2, c), dtype=torch.float32, device=y.device)        # mean, invstd
+    ws = L.workspace(lib.ts_bn_train_workspace_bytes(c), y.device)
+    L.check(getattr(lib, "ts_bn_sync_stats" + sfx)(L.ptr(y), n, c, L.ptr(pack), L.ptr(ws), ws.numel(), L.stream()),
+            "ts_bn_sync_stats" + sfx)
+    L.check(lib.ts_bn_finalize(L.ptr(pack), None, float(n), c, float(eps), float(momentum), L.ptr(running_mean),
+                               L.ptr(running_var), L.ptr(stats[0]), L.ptr(stats[1]), L.stream()), "ts_bn_finalize")
+    if nbt is not None:
+        nbt.add_(1)
+    return stats
+
+
+def _tail_gather_adjoint(g, idx, w, m, order):
+    """the devoxelisation adjoint the plan's order selects, of the gradient rows g over m source rows"""
+    c = g.shape[1]
+    if g.dtype == torch.float16 and not isinstance(order, tuple):       # (the half adjoints walk an inverse map or a cell plan)
+        return B.devoxelize_backward_from(g.float(), 0, c, idx, w, m, order).half()
+    return B.devoxelize_backward_from(g, 0, c, idx, w, m, order)
+
+
+def _tail_bn_backward(g, mask, y, stats, weight):
+    """(grad_y, [grad_gamma, grad_beta]) from ts_bn_act_train_backward with the mask the tail's forward wrote"""
+    n, c = y.shape
+    L = B.L
+    lib = L.load()
+    sfx = "_f16" if y.dtype == torch.float16 else ""
+    grad_y = torch.empty_like(y)
+    gwb = torch.empty((2, c), dtype=torch.float32, device=y.device)
+    ws = L.workspace(lib.ts_bn_train_workspace_bytes(c), y.device)
+    L.check(getattr(lib, "ts_bn_act_train_backward" + sfx)(
+        L.ptr(g), L.ptr(mask), L.ptr(y), L.ptr(stats[0]), L.ptr(stats[1]), L.ptr(weight), n, c, L.ptr(grad_y), None,
+        L.ptr(gwb[0]), L.ptr(gwb[1]), L.ptr(ws), ws.numel(), L.stream()), "ts_bn_act_train_backward" + sfx)
+    return grad_y, gwb
+
+
 class _PointTail(Function):
     """devoxelize(vox) + relu(BN_train(y)) as ONE node: batch statistics from ts_bn_sync_stats + ts_bn_finalize (which also moves the
     running buffers), one launch of ts_point_tail_forward; the gradient of the result goes unchanged to the devoxelisation adjoint the
@@ -1228,20 +1269,7 @@ class _PointTail(Function):
     @staticmethod
     def forward(ctx, y, vox, weight, bias, running_mean, running_var, nbt, momentum, eps, idx, w, order):
         from .batchnorm import _bump
-        n, c = y.shape
-        half = y.dtype == torch.float16
-        sfx = "_f16" if half else ""
-        L = B.L
-        lib = L.load()
-        pack = torch.empty(2 * c + 1, dtype=torch.float64, device=y.device)
-        stats = torch.empty((2, c), dtype=torch.float32, device=y.device)        # mean, invstd
-        ws = L.workspace(lib.ts_bn_train_workspace_bytes(c), y.device)
-        L.check(getattr(lib, "ts_bn_sync_stats" + sfx)(L.ptr(y), n, c, L.ptr(pack), L.ptr(ws), ws.numel(), L.stream()),
-                "ts_bn_sync_stats" + sfx)
-        L.check(lib.ts_bn_finalize(L.ptr(pack), None, float(n), c, float(eps), float(momentum), L.ptr(running_mean),
-                                   L.ptr(running_var), L.ptr(stats[0]), L.ptr(stats[1]), L.stream()), "ts_bn_finalize")
-        if nbt is not None:
-            nbt.add_(1)
+        stats = _tail_batch_stats(y, running_mean, running_var, nbt, momentum, eps)
         out, mask = B.point_tail_forward(y, vox, idx, w, stats[0], stats[1], weight, bias, want_mask=True)
         _bump(running_mean, running_var)
         ctx.save_for_backward(y, weight, stats, mask)
@@ -1252,24 +1280,9 @@ class _PointTail(Function):
     def backward(ctx, grad_out):
         y, weight, stats, mask = ctx.saved_tensors
         idx, w, order = ctx.maps
-        n, c = y.shape
-        half = y.dtype == torch.float16
         g = grad_out.contiguous().to(y.dtype)
-        grad_vox = None
-        if ctx.needs_input_grad[1]:
-            if half and not isinstance(order, tuple):       # (the half adjoints walk an inverse map or a cell plan)
-                grad_vox = B.devoxelize_backward_from(g.float(), 0, c, idx, w, ctx.m, order).half()
-            else:
-                grad_vox = B.devoxelize_backward_from(g, 0, c, idx, w, ctx.m, order)
-        L = B.L
-        lib = L.load()
-        sfx = "_f16" if half else ""
-        grad_y = torch.empty_like(y)
-        gwb = torch.empty((2, c), dtype=torch.float32, device=y.device)
-        ws = L.workspace(lib.ts_bn_train_workspace_bytes(c), y.device)
-        L.check(getattr(lib, "ts_bn_act_train_backward" + sfx)(
-            L.ptr(g), L.ptr(mask), L.ptr(y), L.ptr(stats[0]), L.ptr(stats[1]), L.ptr(weight), n, c, L.ptr(grad_y), None,
-            L.ptr(gwb[0]), L.ptr(gwb[1]), L.ptr(ws), ws.numel(), L.stream()), "ts_bn_act_train_backward" + sfx)
+        grad_vox = _tail_gather_adjoint(g, idx, w, ctx.m, order) if ctx.needs_input_grad[1] else None
+        grad_y, gwb = _tail_bn_backward(g, mask, y, stats, weight)
         return grad_y, grad_vox, gwb[0], gwb[1], None, None, None, None, None, None, None, None
 
 
@@ -1303,3 +1316,148 @@ def point_tail(y: torch.Tensor, bn, vox_feats: torch.Tensor, idx: torch.Tensor, 
                                           w.contiguous().float(), bn.running_mean.float(), invstd, bn.weight.detach(), bn.bias.detach())
         return out.half() if half else out
     return spdevoxelize(vox_feats, idx, w, order) + torch.relu(bn(y))
+
+
+# ------------------------------------------------------------------------------ RPVNet pieces (csrc/rpvnet.hip)
+# Private switch, as above: False selects the chain for tools/time_rpvnet_step.py's baseline.  Nothing else reads it.
+_RANGE_TAIL_KERNEL = True
+
+
+def _range_plan_host(pxpy, b, h, w):
+    """ts_range_plan in tensor ops, float32 operation by operation (the host, and what the tests restate in numpy)"""
+    f32 = torch.float32
+    bf, px, py = pxpy[:, 0].to(f32), pxpy[:, 1].to(f32), pxpy[:, 2].to(f32)
+    bad_b = ~((bf >= 0) & (bf < b)) | (bf != torch.trunc(bf))
+    bad_f = ~(torch.isfinite(px) & torch.isfinite(py))
+    bad_r = ~bad_f & ((px < -1) | (px > 1) | (py < -1) | (py > 1))
+    flag = bad_b.int() | (bad_f.int() << 1) | (bad_r.int() << 2)
+    ok = flag == 0
+    zero = torch.zeros_like(px)
+    bi = torch.where(ok, bf, zero).int()
+    px, py = torch.where(ok, px, zero), torch.where(ok, py, zero)
+    base = bi * (h * w)
+    x = (((px + 1) / 2) * float(w - 1)).int()
+    y = (((py + 1) / 2) * float(h - 1)).int()
+    pix = torch.where(ok, base + y * w + x, torch.full_like(base, -1))
+    ix, iy = ((px + 1) * float(w) - 1) / 2, ((py + 1) * float(h) - 1) / 2
+    fx0, fy0 = torch.floor(ix), torch.floor(iy)
+    fx1, fy1 = fx0 + 1, fy0 + 1
+    x0, y0 = fx0.int(), fy0.int()
+    wx, wy, xs, ys = (fx1 - ix, ix - fx0), (fy1 - iy, iy - fy0), (x0, x0 + 1), (y0, y0 + 1)
+    bidx = torch.full((pxpy.shape[0], 8), -1, dtype=torch.int32, device=pxpy.device)
+    bw = torch.zeros((pxpy.shape[0], 8), dtype=f32, device=pxpy.device)
+    for k, (jy, jx) in enumerate(((0, 0), (0, 1), (1, 0), (1, 1))):          # nw, ne, sw, se
+        inside = ok & (xs[jx] >= 0) & (xs[jx] < w) & (ys[jy] >= 0) & (ys[jy] < h)
+        bidx[:, k] = torch.where(inside, base + ys[jy] * w + xs[jx], torch.full_like(base, -1))
+        bw[:, k] = torch.where(inside, wx[jx] * wy[jy], zero)
+    err = torch.zeros(1, dtype=torch.int32, device=pxpy.device)
+    if flag.numel():
+        err |= (flag & 1).max() | (flag & 2).max() | (flag & 4).max()
+    return pix, bidx, bw, err
+
+
+def range_plan(pxpy: torch.Tensor, b: int, h: int, w: int, backward: bool = True, err=None, cells: bool = False) -> dict:
+    """What the range <-> point transfers of RPVNet need at one resolution of the range branch, from coordinates alone
+    (`range_pxpy` [n, 3] = batch, px, py; include/taseg_hip.h: ts_range_plan):
+      pix, groups    the pixel row of every point under rpvnet.py:88's truncating rule and its grouping - `point_to_range`;
+      bidx, bw       grid_sample's bilinear corners (align_corners=False, zeros padding) as a `trilinear_map` - `range_to_point`;
+      order          the inverse map of (bidx, bw) for the adjoint (None without `backward`); `cells`: the cell-reduced plan of
+                     backend.devox_cells instead, for a coarse map where hundreds of points share four corners (one host read);
+      range_err      a device word, non-zero where a row was left out (never read here).
+    One call of ts_range_plan, ts_point_groups and ts_devox_csr each on the device; tensor ops on the host."""
+    b, h, w = int(b), int(h), int(w)
+    rows = b * h * w
+    with torch.no_grad():
+        if pxpy.is_cuda:
+            pix, bidx, bw, err = B.range_plan(pxpy.float().contiguous(), b, h, w, err)
+            groups = B.point_groups(pix, rows)
+            order = (B.devox_cells if cells else B.devox_csr)(bidx, bw, rows) if backward else None
+        else:
+            pix, bidx, bw, e = _range_plan_host(pxpy, b, h, w)
+            err = e if err is None else err.bitwise_or_(e)
+            groups = order = None
+    return {"pix": pix, "groups": groups, "bidx": bidx, "bw": bw, "order": order, "range_err": err, "shape": (b, h, w)}
+
+
+def _map_rows(fmap: torch.Tensor) -> torch.Tensor:
+    """[B, C, h, w] -> its channels-last rows [B h w, C]: a view of a `torch.channels_last` map, one copy of any other"""
+    return fmap.permute(0, 2, 3, 1).reshape(-1, fmap.shape[1])
+
+
+def range_to_point(fmap: torch.Tensor, plan: dict) -> torch.Tensor:
+    """rpvnet.py:32-51 `range_to_point(feature_map, pxpy)` for batch-sorted points: F.grid_sample(bilinear, zeros,
+    align_corners=False) of every point in its sample's map - `spdevoxelize` of the map's channels-last rows through the plan's
+    corners, one launch for the batch; the adjoint runs in the plan's fixed order."""
+    assert tuple(fmap.shape[0:1] + fmap.shape[2:]) == plan["shape"], "range_to_point: the plan was built for another resolution"
+    return spdevoxelize(_map_rows(fmap), plan["bidx"], plan["bw"], plan["order"])
+
+
+def point_to_range(feats: torch.Tensor, plan: dict, b: int, h: int, w: int) -> torch.Tensor:
+    """rpvnet.py:73-91 `point_to_range(pf, pxpy, b, h, w)`: the mean of the rows of every pixel, zeros where a pixel has none, as a
+    [b, C, h, w] map in channels-last memory - `spvoxelize_mean` over b h w rows with the summation rule of
+    ts_voxelize_mean_forward (the reference adds with float atomics)."""
+    assert (int(b), int(h), int(w)) == plan["shape"], "point_to_range: the plan was built for another resolution"
+    rows = spvoxelize_mean(feats, plan["pix"], b * h * w, plan["groups"])
+    return rows.view(b, h, w, feats.shape[1]).permute(0, 3, 1, 2)
+
+
+class _RangePointTail(Function):
+    """devoxelize(vox) + range_to_point(map rows) + relu(BN_train(y)) as ONE node on ts_range_point_tail_forward: `_PointTail` with
+    one more gathered operand.  The gradient of the result goes unchanged to the two devoxelisation adjoints and to
+    ts_bn_act_train_backward with the mask."""
+
+    @staticmethod
+    def forward(ctx, y, vox, pix, weight, bias, running_mean, running_var, nbt, momentum, eps, idx, w, order, bidx, bw, border):
+        from .batchnorm import _bump
+        stats = _tail_batch_stats(y, running_mean, running_var, nbt, momentum, eps)
+        out, mask = B.range_point_tail_forward(y, vox, idx, w, pix, bidx, bw, stats[0], stats[1], weight, bias, want_mask=True)
+        _bump(running_mean, running_var)
+        ctx.save_for_backward(y, weight, stats, mask)
+        ctx.maps, ctx.m = (idx, w, order, bidx, bw, border), (vox.shape[0], pix.shape[0])
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        y, weight, stats, mask = ctx.saved_tensors
+        idx, w, order, bidx, bw, border = ctx.maps
+        g = grad_out.contiguous().to(y.dtype)
+        grad_vox = _tail_gather_adjoint(g, idx, w, ctx.m[0], order) if ctx.needs_input_grad[1] else None
+        grad_pix = _tail_gather_adjoint(g, bidx, bw, ctx.m[1], border) if ctx.needs_input_grad[2] else None
+        grad_y, gwb = _tail_bn_backward(g, mask, y, stats, weight)
+        return (grad_y, grad_vox, grad_pix, gwb[0], gwb[1]) + (None,) * 11
+
+
+def range_point_tail(y: torch.Tensor, bn, vox_feats: torch.Tensor, idx: torch.Tensor, w: torch.Tensor, order, fmap: torch.Tensor,
+                     range_plan: dict) -> torch.Tensor:
+    """(spdevoxelize(vox_feats, idx, w, order) + range_to_point(fmap, range_plan)) + relu(bn(y)): RPVNet's three-way hand-over
+    `z.F + r_z + z_point` (rpvnet.py:648-704, behind the Linear of `point_transforms`) for a BatchNorm1d / SyncBatchNorm module `bn`
+    on point rows y [N, C] and a map fmap [B, C, h, w].  One launch of ts_range_point_tail_forward under the conditions of
+    `point_tail`; the chain where statistics are shared between ranks, where an evaluation-mode pass records a graph, on the host,
+    and for widths the kernel does not take."""
+    from .modules import _sync_group
+    group = _sync_group(bn)
+    c = y.shape[1] if y.dim() == 2 else 0
+    half = y.is_cuda and (_amp_half(y) or vox_feats.dtype == torch.float16)
+    dt = _rows_dtype(half, c)
+    ok_types = (torch.float32, torch.float16)
+    usable = _RANGE_TAIL_KERNEL and group is None and y.is_cuda and y.dim() == 2 and vox_feats.shape[0] > 0 \
+        and y.dtype in ok_types and vox_feats.dtype in ok_types and fmap.dtype in ok_types \
+        and bn.affine and bn.track_running_stats and bn.weight.dtype == torch.float32 and y.shape[0] > 0 and c <= 1024 \
+        and c % (8 if dt == torch.float16 else 4) == 0
+    graph = torch.is_grad_enabled() and (y.requires_grad or vox_feats.requires_grad or fmap.requires_grad or bn.weight.requires_grad)
+    if usable and ((bn.training and bn.momentum is not None and y.shape[0] > 1) or (not bn.training and not graph)):
+        assert tuple(fmap.shape[0:1] + fmap.shape[2:]) == range_plan["shape"], "range_point_tail: plan of another resolution"
+        idx, w = idx.int().contiguous(), w.contiguous().float()
+        bidx, bw = range_plan["bidx"], range_plan["bw"]
+        with _no_autocast():
+            rows = _map_rows(fmap).contiguous().to(dt)
+            if bn.training:
+                out = _RangePointTail.apply(y.contiguous().to(dt), vox_feats.contiguous().to(dt), rows, bn.weight, bn.bias,
+                                            bn.running_mean, bn.running_var, bn.num_batches_tracked, bn.momentum, bn.eps, idx, w,
+                                            order, bidx, bw, range_plan["order"])
+            else:
+                invstd = torch.rsqrt(bn.running_var.float() + bn.eps)
+                out, _ = B.range_point_tail_forward(y.contiguous().to(dt), vox_feats.contiguous().to(dt), idx, w, rows, bidx, bw,
+                                                    bn.running_mean.float(), invstd, bn.weight.detach(), bn.bias.detach())
+        return out.half() if half else out
+    return spdevoxelize(vox_feats, idx, w, order) + range_to_point(fmap, range_plan) + torch.relu(bn(y))
