@@ -2197,6 +2197,7 @@ def _same_rows(t, like, who):
 
 
 # --------------------------------------------------------------------------- SPVCNN (csrc/spvcnn.hip)
+# (`_point_tail` is the worker of `point_tail_forward` here and of `range_point_tail_forward` in the RPVNet section)
 def point_groups(idx, m):
     """(offsets [m + 1], entries [n]) int32: the rows i of a point -> voxel map idx [n] grouped by voxel, ascending inside a voxel;
     rows with idx < 0 or idx >= m belong to no voxel.  One grouping serves every voxelize_mean_* call through that map."""
@@ -2254,24 +2255,36 @@ def voxelize_mean_backward(grad_out, idx, groups):
     return out
 
 
+def _point_tail(who, y, vox, idx, weight, pix, bidx, bweight, mean, invstd, gamma, beta, want_mask):
+    """the checks, the allocations and the call of `point_tail_forward` (pix, bidx and bweight None) and `range_point_tail_forward`"""
+    L.require_device(y, vox, idx, weight, pix, bidx, bweight, mean, invstd, gamma, beta)
+    y, half = _rows_f32_f16(y, "y")
+    vox = _same_cols(vox, y, who)
+    maps = [_i32(idx, "idx"), _f32(weight, "weight")]
+    if pix is not None:
+        pix = _same_cols(pix, y, who)
+        maps += [_i32(bidx, "bidx"), _f32(bweight, "bweight")]
+    stats = [_f32(t, "statistics") for t in (mean, invstd, gamma, beta)]
+    n, c = y.shape
+    if any(t.shape != (n, 8) for t in maps) or any(t.shape != (c,) for t in stats):
+        raise ValueError(f"{who}: maps [n, 8] and per-channel vectors [c] must match y [n, c]")
+    out = torch.empty_like(y)
+    mask = torch.empty(n * (c // (8 if half else 4)), dtype=torch.uint8, device=y.device) if want_mask else None
+    rows, stats = [L.ptr(y), L.ptr(vox), L.ptr(maps[0]), L.ptr(maps[1])], [L.ptr(t) for t in stats]
+    if pix is None:
+        rc = L.load().ts_point_tail_forward(*rows, *stats, n, c, vox.shape[0], half, L.ptr(out), L.ptr(mask), L.stream())
+    else:
+        rc = L.load().ts_range_point_tail_forward(*rows, L.ptr(pix), L.ptr(maps[2]), L.ptr(maps[3]), *stats, n, c, vox.shape[0],
+                                                  pix.shape[0], half, L.ptr(out), L.ptr(mask), L.stream())
+    L.check(rc, "ts_" + who)
+    return out, mask
+
+
 def point_tail_forward(y, vox, idx, weight, mean, invstd, gamma, beta, want_mask=False):
     """(out [n, c], mask | None): out = sum_k weight[:, k] vox[idx[:, k]] + relu((y - mean) invstd gamma + beta) in one pass
     (ts_point_tail_forward); mask = the sign bits of the BatchNorm term in ts_bn_act_forward's layout, for ts_bn_act_train_backward.
     y and vox of one dtype: float32 (c % 4 == 0) or float16 (c % 8 == 0)."""
-    L.require_device(y, vox, idx, weight, mean, invstd, gamma, beta)
-    y, half = _rows_f32_f16(y, "y")
-    vox = _same_cols(vox, y, "point_tail_forward")
-    idx, weight = _i32(idx, "idx"), _f32(weight, "weight")
-    mean, invstd, gamma, beta = (_f32(t, "statistics") for t in (mean, invstd, gamma, beta))
-    n, c = y.shape
-    if idx.shape != (n, 8) or weight.shape != (n, 8) or any(t.shape != (c,) for t in (mean, invstd, gamma, beta)):
-        raise ValueError("point_tail_forward: maps [n, 8] and per-channel vectors [c] must match y [n, c]")
-    out = torch.empty_like(y)
-    mask = torch.empty(n * (c // (8 if half else 4)), dtype=torch.uint8, device=y.device) if want_mask else None
-    L.check(L.load().ts_point_tail_forward(L.ptr(y), L.ptr(vox), L.ptr(idx), L.ptr(weight), L.ptr(mean), L.ptr(invstd), L.ptr(gamma),
-                                           L.ptr(beta), n, c, vox.shape[0], half, L.ptr(out), L.ptr(mask), L.stream()),
-            "ts_point_tail_forward")
-    return out, mask
+    return _point_tail("point_tail_forward", y, vox, idx, weight, None, None, None, mean, invstd, gamma, beta, want_mask)
 
 
 def _same_cols(t, like, who):
@@ -2305,21 +2318,7 @@ def range_plan(pxpy, batch, h, w, err=None):
 def range_point_tail_forward(y, vox, idx, weight, pix, bidx, bweight, mean, invstd, gamma, beta, want_mask=False):
     """(out [n, c], mask | None): `point_tail_forward` with the bilinear read of the map rows pix [mp, c] through (bidx, bweight) of
     `range_plan` added to the trilinear sum before the BatchNorm term (ts_range_point_tail_forward).  y, vox and pix of one dtype."""
-    L.require_device(y, vox, idx, weight, pix, bidx, bweight, mean, invstd, gamma, beta)
-    y, half = _rows_f32_f16(y, "y")
-    vox, pix = _same_cols(vox, y, "range_point_tail_forward"), _same_cols(pix, y, "range_point_tail_forward")
-    idx, weight, bidx, bweight = _i32(idx, "idx"), _f32(weight, "weight"), _i32(bidx, "bidx"), _f32(bweight, "bweight")
-    mean, invstd, gamma, beta = (_f32(t, "statistics") for t in (mean, invstd, gamma, beta))
-    n, c = y.shape
-    if any(t.shape != (n, 8) for t in (idx, weight, bidx, bweight)) or any(t.shape != (c,) for t in (mean, invstd, gamma, beta)):
-        raise ValueError("range_point_tail_forward: maps [n, 8] and per-channel vectors [c] must match y [n, c]")
-    out = torch.empty_like(y)
-    mask = torch.empty(n * (c // (8 if half else 4)), dtype=torch.uint8, device=y.device) if want_mask else None
-    L.check(L.load().ts_range_point_tail_forward(L.ptr(y), L.ptr(vox), L.ptr(idx), L.ptr(weight), L.ptr(pix), L.ptr(bidx),
-                                                 L.ptr(bweight), L.ptr(mean), L.ptr(invstd), L.ptr(gamma), L.ptr(beta), n, c,
-                                                 vox.shape[0], pix.shape[0], half, L.ptr(out), L.ptr(mask), L.stream()),
-            "ts_range_point_tail_forward")
-    return out, mask
+    return _point_tail("range_point_tail_forward", y, vox, idx, weight, pix, bidx, bweight, mean, invstd, gamma, beta, want_mask)
 
 
 def range_inputs(feat, batch, cut, b, h, w, err=None):

@@ -38,7 +38,7 @@ def _newer(src, dst):
 
 def _deps():
     return [os.path.join(HERE, "common.h"), os.path.join(HERE, "compact.h"), os.path.join(HERE, "stage_rules.h"),
-            os.path.join(HERE, "quantize_keys.h"), os.path.join(HERE, "point_tail.h"),
+            os.path.join(HERE, "quantize_keys.h"), os.path.join(HERE, "point_tail.h"), os.path.join(HERE, "rows.h"),
             os.path.join(ROOT, "include", "taseg_hip.h"), os.path.abspath(__file__)]
 
 

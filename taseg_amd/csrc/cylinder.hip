@@ -1,19 +1,11 @@
 // Kernels of the Cylinder_TS segmentor (reference pcseg/model/segmentor/voxel/cylinder3d/cylinder_ts.py) that the rest of the
 // library does not already serve: the max-voxelisation of point features (tools/utils/common/seg_utils.py:385-401,
 // `torch_scatter.scatter_max(z.F, idx_query, dim=0)[0]`) and the sigmoid gate of ReconBlock (cylinder_ts.py:368-384).  Both are
-// bandwidth kernels: 16-byte accesses per lane, every output element written exactly once, no atomics, no fill.
-#include <hip/hip_fp16.h>
-
-#include "common.h"
+// bandwidth kernels of the csrc/rows.h family: 16-byte accesses per lane, every output element written exactly once, no atomics, no
+// fill.
+#include "rows.h"
 
 namespace {
-
-template <typename T, int V>
-using ts_vec = T __attribute__((ext_vector_type(V)));
-
-template <typename T> struct Lanes;                     // elements of one 16-byte access
-template <> struct Lanes<float> { static constexpr int V = 4; };
-template <> struct Lanes<_Float16> { static constexpr int V = 8; };
 
 // ------------------------------------------------------------------------------------------------------ max-voxelisation
 // The rows are grouped by voxel first (ts_group_slots: stable, ascending row index inside a voxel).  One group of c / V lanes
@@ -112,13 +104,6 @@ __global__ __launch_bounds__(256) void voxel_max_bwd_kernel(const T *__restrict_
   *(vec *)(gfeat + i * c + V * lane) = g;
 }
 
-int voxel_max_check(const char *who, int64_t n, int32_t c, int64_t m, int32_t half) {
-  TS_REQUIRE(n >= 0 && m >= 0 && c > 0 && n < (1LL << 30) && m < (1LL << 31) - 1, TS_ERR_INVALID_ARGUMENT, "%s: bad sizes", who);
-  TS_REQUIRE(c % (half ? 8 : 4) == 0 && c <= 1024, TS_ERR_UNSUPPORTED,
-             "%s: C must be a multiple of %d (16-byte pieces of a row), <= 1024", who, half ? 8 : 4);
-  return TS_OK;
-}
-
 // ------------------------------------------------------------------------------------------------------------ sigmoid gate
 __device__ __forceinline__ float sigmoidf(float a) { return 1.f / (1.f + expf(-a)); }
 
@@ -175,10 +160,6 @@ int gate_check(const char *who, int64_t n, int32_t c, int32_t half, int64_t *nv)
   return TS_OK;
 }
 
-inline bool aligned16(const void *a, const void *b = nullptr, const void *c = nullptr, const void *d = nullptr) {
-  return ((((uintptr_t)a) | ((uintptr_t)b) | ((uintptr_t)c) | ((uintptr_t)d)) & 15) == 0;
-}
-
 }  // namespace
 
 extern "C" size_t ts_voxelize_max_workspace_bytes(int64_t n, int64_t m) {
@@ -189,7 +170,7 @@ extern "C" size_t ts_voxelize_max_workspace_bytes(int64_t n, int64_t m) {
 extern "C" int ts_voxelize_max_forward(const void *feat, const int32_t *idx, int64_t n, int32_t c, int64_t m, int32_t half,
                                        void *out, int32_t *arg, void *ws, size_t ws_bytes, ts_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  const int rc = voxel_max_check("ts_voxelize_max_forward", n, c, m, half);
+  const int rc = rows_check("ts_voxelize_max_forward", n, c, m, half);
   if (rc != TS_OK) return rc;
   if (m == 0) return TS_OK;
   TS_REQUIRE(out && arg && ws && (n == 0 || (feat && idx)), TS_ERR_INVALID_ARGUMENT, "ts_voxelize_max_forward: null pointer");
@@ -204,12 +185,11 @@ extern "C" int ts_voxelize_max_forward(const void *feat, const int32_t *idx, int
   const int grc = ts_group_slots(idx, nullptr, n, m, off, ent, p, ws_bytes - (size_t)(p - (char *)ws), stream,
                                  "ts_voxelize_max_forward");
   if (grc != TS_OK) return grc;
-  const int groups = 256 / (c / (half ? 8 : 4));
-  const unsigned grid = (unsigned)ts_cdiv(m, groups);
-  if (half)
-    voxel_max_fwd_kernel<_Float16><<<grid, 256, 0, stream>>>((const _Float16 *)feat, off, ent, m, c, (_Float16 *)out, arg);
-  else
-    voxel_max_fwd_kernel<float><<<grid, 256, 0, stream>>>((const float *)feat, off, ent, m, c, (float *)out, arg);
+  const unsigned grid = (unsigned)ts_cdiv(m, row_groups(c, half));
+  by_half(half, [&](auto t) {
+    using T = decltype(t);
+    voxel_max_fwd_kernel<T><<<grid, 256, 0, stream>>>((const T *)feat, off, ent, m, c, (T *)out, arg);
+  });
   TS_CHECK_LAUNCH("ts_voxelize_max_forward");
   return TS_OK;
 }
@@ -217,17 +197,16 @@ extern "C" int ts_voxelize_max_forward(const void *feat, const int32_t *idx, int
 extern "C" int ts_voxelize_max_backward(const void *grad_out, const int32_t *idx, const int32_t *arg, int64_t n, int32_t c,
                                         int64_t m, int32_t half, void *grad_feat, ts_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  const int rc = voxel_max_check("ts_voxelize_max_backward", n, c, m, half);
+  const int rc = rows_check("ts_voxelize_max_backward", n, c, m, half);
   if (rc != TS_OK) return rc;
   if (n == 0) return TS_OK;
   TS_REQUIRE(grad_feat && idx && (m == 0 || (grad_out && arg)), TS_ERR_INVALID_ARGUMENT, "ts_voxelize_max_backward: null pointer");
   TS_REQUIRE(aligned16(grad_out, grad_feat, arg), TS_ERR_INVALID_ARGUMENT, "ts_voxelize_max_backward: rows must be 16-byte aligned");
-  const int groups = 256 / (c / (half ? 8 : 4));
-  const unsigned grid = (unsigned)ts_cdiv(n, groups);
-  if (half)
-    voxel_max_bwd_kernel<_Float16><<<grid, 256, 0, stream>>>((const _Float16 *)grad_out, idx, arg, n, c, m, (_Float16 *)grad_feat);
-  else
-    voxel_max_bwd_kernel<float><<<grid, 256, 0, stream>>>((const float *)grad_out, idx, arg, n, c, m, (float *)grad_feat);
+  const unsigned grid = (unsigned)ts_cdiv(n, row_groups(c, half));
+  by_half(half, [&](auto t) {
+    using T = decltype(t);
+    voxel_max_bwd_kernel<T><<<grid, 256, 0, stream>>>((const T *)grad_out, idx, arg, n, c, m, (T *)grad_feat);
+  });
   TS_CHECK_LAUNCH("ts_voxelize_max_backward");
   return TS_OK;
 }
@@ -243,12 +222,10 @@ extern "C" int ts_sigmoid3_gate_forward(const void *x, const void *u, const void
   TS_REQUIRE(aligned16(x, u, v, w) && aligned16(out), TS_ERR_INVALID_ARGUMENT,
              "ts_sigmoid3_gate_forward: pointers must be 16-byte aligned");
   const unsigned grid = (unsigned)ts_cdiv(nv, 256);
-  if (half)
-    sigmoid3_gate_fwd_kernel<_Float16><<<grid, 256, 0, stream>>>((const _Float16 *)x, (const _Float16 *)u, (const _Float16 *)v,
-                                                                (const _Float16 *)w, nv, (_Float16 *)out);
-  else
-    sigmoid3_gate_fwd_kernel<float><<<grid, 256, 0, stream>>>((const float *)x, (const float *)u, (const float *)v,
-                                                             (const float *)w, nv, (float *)out);
+  by_half(half, [&](auto t) {
+    using T = decltype(t);
+    sigmoid3_gate_fwd_kernel<T><<<grid, 256, 0, stream>>>((const T *)x, (const T *)u, (const T *)v, (const T *)w, nv, (T *)out);
+  });
   TS_CHECK_LAUNCH("ts_sigmoid3_gate_forward");
   return TS_OK;
 }
@@ -266,14 +243,11 @@ extern "C" int ts_sigmoid3_gate_backward(const void *grad_out, const void *x, co
   TS_REQUIRE(aligned16(x, u, v, w) && aligned16(grad_out, grad_x, grad_u, grad_v) && aligned16(grad_w), TS_ERR_INVALID_ARGUMENT,
              "ts_sigmoid3_gate_backward: pointers must be 16-byte aligned");
   const unsigned grid = (unsigned)ts_cdiv(nv, 256);
-  if (half)
-    sigmoid3_gate_bwd_kernel<_Float16><<<grid, 256, 0, stream>>>(
-        (const _Float16 *)grad_out, (const _Float16 *)x, (const _Float16 *)u, (const _Float16 *)v, (const _Float16 *)w, nv,
-        (_Float16 *)grad_x, (_Float16 *)grad_u, (_Float16 *)grad_v, (_Float16 *)grad_w);
-  else
-    sigmoid3_gate_bwd_kernel<float><<<grid, 256, 0, stream>>>((const float *)grad_out, (const float *)x, (const float *)u,
-                                                             (const float *)v, (const float *)w, nv, (float *)grad_x,
-                                                             (float *)grad_u, (float *)grad_v, (float *)grad_w);
+  by_half(half, [&](auto t) {
+    using T = decltype(t);
+    sigmoid3_gate_bwd_kernel<T><<<grid, 256, 0, stream>>>((const T *)grad_out, (const T *)x, (const T *)u, (const T *)v, (const T *)w,
+                                                          nv, (T *)grad_x, (T *)grad_u, (T *)grad_v, (T *)grad_w);
+  });
   TS_CHECK_LAUNCH("ts_sigmoid3_gate_backward");
   return TS_OK;
 }

@@ -1,19 +1,12 @@
 // The point-branch tail shared by csrc/spvcnn.hip (ts_point_tail_forward) and csrc/rpvnet.hip (ts_range_point_tail_forward): one
-// kernel template, the range operand compiled in or out.  Row kernels of this family use 16-byte accesses per lane and one group of
-// c / V lanes per row; both files are compiled with -ffp-contract=off, so every product and sum below keeps its own rounding.
+// kernel template, the range operand compiled in or out, and one launcher with the checks of both entry points.  A row kernel of
+// csrc/rows.h's family; both files are compiled with -ffp-contract=off, so every product and sum below keeps its own rounding.
 #pragma once
-#include <hip/hip_fp16.h>
+#include <algorithm>
 
-#include "common.h"
+#include "rows.h"
 
 namespace {
-
-template <typename T, int V>
-using ts_vec = T __attribute__((ext_vector_type(V)));
-
-template <typename T> struct Lanes;                     // elements of one 16-byte access
-template <> struct Lanes<float> { static constexpr int V = 4; };
-template <> struct Lanes<_Float16> { static constexpr int V = 8; };
 
 // out[i, :] = sum_k w[i, k] vox[idx[i, k], :] + relu((y[i, :] - mean) invstd gamma + beta): the trilinear sum over k = 0 .. 7 in k
 // order with float32 accumulation, a missing corner (idx < 0, or w == 0) adding nothing - the arithmetic of devoxelize_fwd_kernel
@@ -106,15 +99,30 @@ __global__ __launch_bounds__(256) void point_tail_fwd_kernel(const T *__restrict
   }
 }
 
-inline int rows_check(const char *who, int64_t n, int32_t c, int64_t m, int32_t half) {
-  TS_REQUIRE(n >= 0 && m >= 0 && c > 0 && n < (1LL << 30) && m < (1LL << 31) - 1, TS_ERR_INVALID_ARGUMENT, "%s: bad sizes", who);
-  TS_REQUIRE(c % (half ? 8 : 4) == 0 && c <= 1024, TS_ERR_UNSUPPORTED,
-             "%s: C must be a multiple of %d (16-byte pieces of a row), <= 1024", who, half ? 8 : 4);
+// The checks, the grid rule and the launch of both entry points; `who` is the entry point that was called.  Without RANGE pix, bidx,
+// bw and mp are not looked at (the callers pass null and 0).
+template <bool RANGE>
+int launch_point_tail(const char *who, const void *y, const void *vox, const int32_t *idx, const float *weight, const void *pix,
+                      const int32_t *bidx, const float *bweight, int64_t mp, const float *mean, const float *invstd,
+                      const float *gamma, const float *beta, int64_t n, int32_t c, int64_t m, int32_t half, void *out, uint8_t *mask,
+                      hipStream_t stream) {
+  const int rc = rows_check(who, n, c, m, half);
+  if (rc != TS_OK) return rc;
+  if (RANGE) TS_REQUIRE(mp >= 0 && mp < (1LL << 31) - 1, TS_ERR_INVALID_ARGUMENT, "%s: bad sizes", who);
+  if (n == 0) return TS_OK;
+  TS_REQUIRE(y && idx && weight && mean && invstd && gamma && beta && out && (vox || m == 0) &&
+                 (!RANGE || (bidx && bweight && (pix || mp == 0))),
+             TS_ERR_INVALID_ARGUMENT, "%s: null pointer", who);
+  TS_REQUIRE(aligned16(y, vox, out) && aligned16(idx, weight) && (!RANGE || aligned16(pix, bidx, bweight)), TS_ERR_INVALID_ARGUMENT,
+             "%s: rows and maps must be 16-byte aligned", who);
+  const unsigned grid = (unsigned)std::min<int64_t>(ts_cdiv(n, (int64_t)row_groups(c, half)), 8192);
+  by_half(half, [&](auto t) {
+    using T = decltype(t);
+    point_tail_fwd_kernel<T, RANGE><<<grid, 256, 0, stream>>>((const T *)y, (const T *)vox, idx, weight, (const T *)pix, bidx, bweight,
+                                                              mp, mean, invstd, gamma, beta, n, c, m, (T *)out, mask);
+  });
+  TS_CHECK_LAUNCH(who);
   return TS_OK;
-}
-
-inline bool aligned16(const void *a, const void *b = nullptr, const void *c = nullptr, const void *d = nullptr) {
-  return ((((uintptr_t)a) | ((uintptr_t)b) | ((uintptr_t)c) | ((uintptr_t)d)) & 15) == 0;
 }
 
 }  // namespace

@@ -5,7 +5,7 @@
 //     of ts_trilinear_map - so the mean is ts_voxelize_mean_forward over B h w "voxels", the bilinear read is ts_devoxelize_forward
 //     and both adjoints are the kernels those have already: fixed order, no atomics.
 //   * ts_range_point_tail_forward: z.F = voxel_to_point(x).F + range_to_point(r) + relu(BN(Linear(z_prev.F))) (rpvnet.py:648-704) in
-//     one pass over the rows - point_tail_fwd_kernel of point_tail.h with the range operand compiled in.
+//     one pass over the rows - launch_point_tail<true> of point_tail.h: the shared kernel with the range operand compiled in.
 // Compiled with -ffp-contract=off (csrc/build.py): tests/rpvnet_ref.py restates the plan operation by operation, bit for bit.
 #include "point_tail.h"
 
@@ -77,25 +77,6 @@ extern "C" int ts_range_point_tail_forward(const void *y, const void *vox, const
                                            const int32_t *bidx, const float *bweight, const float *mean, const float *invstd,
                                            const float *gamma, const float *beta, int64_t n, int32_t c, int64_t m, int64_t mp,
                                            int32_t half, void *out, uint8_t *mask, ts_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  const int rc = rows_check("ts_range_point_tail_forward", n, c, m, half);
-  if (rc != TS_OK) return rc;
-  TS_REQUIRE(mp >= 0 && mp < (1LL << 31) - 1, TS_ERR_INVALID_ARGUMENT, "ts_range_point_tail_forward: bad sizes");
-  if (n == 0) return TS_OK;
-  TS_REQUIRE(y && idx && weight && bidx && bweight && mean && invstd && gamma && beta && out && (vox || m == 0) && (pix || mp == 0),
-             TS_ERR_INVALID_ARGUMENT, "ts_range_point_tail_forward: null pointer");
-  TS_REQUIRE(aligned16(y, vox, out, pix) && aligned16(idx, weight, bidx, bweight), TS_ERR_INVALID_ARGUMENT,
-             "ts_range_point_tail_forward: rows and maps must be 16-byte aligned");
-  const int groups = 256 / (c / (half ? 8 : 4));
-  const unsigned grid = (unsigned)std::min<int64_t>(ts_cdiv(n, (int64_t)groups), 8192);
-  if (half)
-    point_tail_fwd_kernel<_Float16, true><<<grid, 256, 0, stream>>>((const _Float16 *)y, (const _Float16 *)vox, idx, weight,
-                                                                    (const _Float16 *)pix, bidx, bweight, mp, mean, invstd, gamma,
-                                                                    beta, n, c, m, (_Float16 *)out, mask);
-  else
-    point_tail_fwd_kernel<float, true><<<grid, 256, 0, stream>>>((const float *)y, (const float *)vox, idx, weight, (const float *)pix,
-                                                                 bidx, bweight, mp, mean, invstd, gamma, beta, n, c, m, (float *)out,
-                                                                 mask);
-  TS_CHECK_LAUNCH("ts_range_point_tail_forward");
-  return TS_OK;
+  return launch_point_tail<true>("ts_range_point_tail_forward", y, vox, idx, weight, pix, bidx, bweight, mp, mean, invstd, gamma, beta,
+                                 n, c, m, half, out, mask, (hipStream_t)stream_);
 }

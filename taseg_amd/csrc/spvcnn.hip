@@ -4,7 +4,7 @@
 //     pass at strides 1, 16 and 4; the float atomics of ts_voxelize_forward land 120 000 x 256 adds on 1 379 x 256 addresses at
 //     stride 16 and change their order from run to run);
 //   * the tail of the point branch, z.F = devoxelize(x.F) + ReLU(BN(Linear(z.F))) (spvcnn.py:417-444), in one pass over the rows.
-// Both are bandwidth kernels in the idiom of csrc/cylinder.hip: 16-byte accesses per lane, one group of c / V lanes per row, voxel or
+// Both are bandwidth kernels of the csrc/rows.h family: 16-byte accesses per lane, one group of c / V lanes per row, voxel or
 // piece, every output element written exactly once, no atomics, no fill.  Compiled with -ffp-contract=off (csrc/build.py): every
 // product and sum below keeps its own rounding, so tests/spvcnn_ref.py restates the mean bit for bit.
 #include "point_tail.h"
@@ -175,7 +175,7 @@ __global__ __launch_bounds__(256) void voxel_mean_bwd_kernel(const T *__restrict
   *(vec *)(gfeat + i * c + V * lane) = g;
 }
 
-// The point tail (ts_point_tail_forward) launches point_tail_fwd_kernel<T, false> of point_tail.h, which csrc/rpvnet.hip shares.
+// The point tail (ts_point_tail_forward) is launch_point_tail<false> of point_tail.h, which csrc/rpvnet.hip shares.
 
 }  // namespace
 
@@ -213,24 +213,22 @@ extern "C" int ts_voxelize_mean_forward(const void *feat, const int32_t *idx, co
   TS_REQUIRE(n == 0 || ws_bytes >= ts_voxelize_mean_workspace_bytes(n, c), TS_ERR_INVALID_ARGUMENT,
              "ts_voxelize_mean_forward: workspace too small");
   const int P = g_piece_rows;
-  const int groups = 256 / (c / (half ? 8 : 4));
+  const int groups = row_groups(c, half);
   const int64_t n_items = ts_cdiv(n, (int64_t)P);
   float *part = (float *)ws;
   if (n_items > 0) {
     const unsigned grid = (unsigned)ts_cdiv(n_items, (int64_t)groups);
-    if (half)
-      voxel_mean_pieces_kernel<_Float16><<<grid, 256, 0, stream>>>((const _Float16 *)feat, idx, offsets, entries, n, c, m, P, n_items,
-                                                                   part);
-    else
-      voxel_mean_pieces_kernel<float><<<grid, 256, 0, stream>>>((const float *)feat, idx, offsets, entries, n, c, m, P, n_items, part);
+    by_half(half, [&](auto t) {
+      using T = decltype(t);
+      voxel_mean_pieces_kernel<T><<<grid, 256, 0, stream>>>((const T *)feat, idx, offsets, entries, n, c, m, P, n_items, part);
+    });
     TS_CHECK_LAUNCH("ts_voxelize_mean_forward/pieces");
   }
   const unsigned grid = (unsigned)ts_cdiv(m, (int64_t)groups);
-  if (half)
-    voxel_mean_finish_kernel<_Float16><<<grid, 256, 0, stream>>>((const _Float16 *)feat, offsets, entries, n, c, m, P, part,
-                                                                 (_Float16 *)out);
-  else
-    voxel_mean_finish_kernel<float><<<grid, 256, 0, stream>>>((const float *)feat, offsets, entries, n, c, m, P, part, (float *)out);
+  by_half(half, [&](auto t) {
+    using T = decltype(t);
+    voxel_mean_finish_kernel<T><<<grid, 256, 0, stream>>>((const T *)feat, offsets, entries, n, c, m, P, part, (T *)out);
+  });
   TS_CHECK_LAUNCH("ts_voxelize_mean_forward/finish");
   return TS_OK;
 }
@@ -244,12 +242,11 @@ extern "C" int ts_voxelize_mean_backward(const void *grad_out, const int32_t *id
   TS_REQUIRE(grad_feat && idx && (m == 0 || (grad_out && offsets)), TS_ERR_INVALID_ARGUMENT,
              "ts_voxelize_mean_backward: null pointer");
   TS_REQUIRE(aligned16(grad_out, grad_feat), TS_ERR_INVALID_ARGUMENT, "ts_voxelize_mean_backward: rows must be 16-byte aligned");
-  const int groups = 256 / (c / (half ? 8 : 4));
-  const unsigned grid = (unsigned)ts_cdiv(n, (int64_t)groups);
-  if (half)
-    voxel_mean_bwd_kernel<_Float16><<<grid, 256, 0, stream>>>((const _Float16 *)grad_out, idx, offsets, n, c, m, (_Float16 *)grad_feat);
-  else
-    voxel_mean_bwd_kernel<float><<<grid, 256, 0, stream>>>((const float *)grad_out, idx, offsets, n, c, m, (float *)grad_feat);
+  const unsigned grid = (unsigned)ts_cdiv(n, (int64_t)row_groups(c, half));
+  by_half(half, [&](auto t) {
+    using T = decltype(t);
+    voxel_mean_bwd_kernel<T><<<grid, 256, 0, stream>>>((const T *)grad_out, idx, offsets, n, c, m, (T *)grad_feat);
+  });
   TS_CHECK_LAUNCH("ts_voxelize_mean_backward");
   return TS_OK;
 }
@@ -257,23 +254,6 @@ extern "C" int ts_voxelize_mean_backward(const void *grad_out, const int32_t *id
 extern "C" int ts_point_tail_forward(const void *y, const void *vox, const int32_t *idx, const float *weight, const float *mean,
                                      const float *invstd, const float *gamma, const float *beta, int64_t n, int32_t c, int64_t m,
                                      int32_t half, void *out, uint8_t *mask, ts_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  const int rc = rows_check("ts_point_tail_forward", n, c, m, half);
-  if (rc != TS_OK) return rc;
-  if (n == 0) return TS_OK;
-  TS_REQUIRE(y && idx && weight && mean && invstd && gamma && beta && out && (vox || m == 0), TS_ERR_INVALID_ARGUMENT,
-             "ts_point_tail_forward: null pointer");
-  TS_REQUIRE(aligned16(y, vox, out) && aligned16(idx, weight), TS_ERR_INVALID_ARGUMENT,
-             "ts_point_tail_forward: rows and maps must be 16-byte aligned");
-  const int groups = 256 / (c / (half ? 8 : 4));
-  const unsigned grid = (unsigned)std::min<int64_t>(ts_cdiv(n, (int64_t)groups), 8192);
-  if (half)
-    point_tail_fwd_kernel<_Float16, false><<<grid, 256, 0, stream>>>((const _Float16 *)y, (const _Float16 *)vox, idx, weight, nullptr,
-                                                                     nullptr, nullptr, 0, mean, invstd, gamma, beta, n, c, m,
-                                                                     (_Float16 *)out, mask);
-  else
-    point_tail_fwd_kernel<float, false><<<grid, 256, 0, stream>>>((const float *)y, (const float *)vox, idx, weight, nullptr, nullptr,
-                                                                  nullptr, 0, mean, invstd, gamma, beta, n, c, m, (float *)out, mask);
-  TS_CHECK_LAUNCH("ts_point_tail_forward");
-  return TS_OK;
+  return launch_point_tail<false>("ts_point_tail_forward", y, vox, idx, weight, nullptr, nullptr, nullptr, 0, mean, invstd, gamma,
+                                  beta, n, c, m, half, out, mask, (hipStream_t)stream_);
 }

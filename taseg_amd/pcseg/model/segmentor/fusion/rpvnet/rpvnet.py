@@ -4,7 +4,9 @@ branch, the three meeting four times per pass.
 Module tree, attribute names and therefore every state_dict key, their order and shapes are the reference's for both blocks
 (`stem.0.kernel` .. `up4.1.*`, `classifier.0.weight`, `point_transforms.0.0.weight` .. `point_transforms.3.1.*`,
 `range_branch.stem.0.conv1.weight` .. `range_branch.up4.bn1.num_batches_tracked`), so reference checkpoints load here and vice versa.
-The voxel branch, index plan, losses and the evaluation tail are `minkunet.py`'s, `point_to_voxel` is SPVCNN's, and the range branch
+The voxel branch, index plan, losses and the evaluation ending are `minkunet.py`'s; the class derives from `SPVCNN` and takes from it
+`point_to_voxel`, the construction of `point_transforms`, the plan of the point branch, `_seed` and the Linear-then-tail step `_tail`
+(here with a map and the range plans); the range branch
 (`SalsaNext`, rpvnet.py:205-253) is built from the three blocks of `minkunet/unet2d.py` - the reference's ResContextBlock / ResBlock /
 UpBlock with the same parameter names - in the memory layout `options.image_layout` names.  What this file adds:
 
@@ -32,17 +34,14 @@ from torch import nn
 
 from taseg_amd.options import options
 from taseg_amd import torchsparse
-from taseg_amd.torchsparse import PointTensor, SparseTensor
+from taseg_amd.torchsparse import PointTensor
 from taseg_amd.torchsparse import nn as spnn
 from taseg_amd.torchsparse.nn import functional as spF
-from ...voxel.minkunet.minkunet import MinkUNetBackbone, unvoxelise_predictions
 from ...voxel.minkunet.unet2d import ResBlock, ResContextBlock, UNet2D, UpBlock
-from ..spvcnn.spvcnn import SPVCNN
+from ..spvcnn.spvcnn import _PLANES, SPVCNN
 from ..spvcnn.utils import point_to_voxel
 
 __all__ = ["RPVNet", "SalsaNext"]
-
-_PLANES = [32, 32, 64, 128, 256, 256, 128, 96, 96]
 
 
 def _pooled(size: int, times: int = 4) -> int:
@@ -84,34 +83,23 @@ class SalsaNext(UNet2D):
         return batch_dict
 
 
-class RPVNet(MinkUNetBackbone):
+class RPVNet(SPVCNN):
     def __init__(self, model_cfgs, num_class: int):
-        cfgs = _with_defaults(model_cfgs)
-        super().__init__(cfgs, num_class)              # stem .. up4, classifier, dropout, losses: rpvnet.py:432-624 == minkunet.py
+        super().__init__(_with_defaults(model_cfgs), num_class)      # backbone (rpvnet.py:432-624 == minkunet.py), then the branches
         self.model_cfgs = model_cfgs
         self.name = "rpvnet"
-        cs = [int(cfgs.get("cr") * x) for x in cfgs.get("PLANES", _PLANES)]
-        exp = self.block.expansion
-        if_dist = model_cfgs.IF_DIST
-        self.multi_scale = model_cfgs.get("MULTI_SCALE", "concat")
-        if self.multi_scale != "concat":
-            del self.classifier                        # (:567-569: built for 'concat' only; forward then fails as the reference's does)
 
-        def transform(inc, outc):
-            return nn.Sequential(nn.Linear(inc, outc), nn.SyncBatchNorm(outc) if if_dist else nn.BatchNorm1d(outc), nn.ReLU(True))
-
-        self.point_transforms = nn.ModuleList([transform(self.in_feature_dim, cs[0]), transform(cs[0], cs[4] * exp),
-                                               transform(cs[4] * exp, cs[6] * exp), transform(cs[6] * exp, cs[8] * exp)])
-        self.range_branch = SalsaNext(model_cfgs=model_cfgs, input_channels=5)
-        if if_dist:
+    def _build_branches(self, cfgs):
+        self._build_point_branch(cfgs, lead=[self.in_feature_dim])
+        self.range_branch = SalsaNext(model_cfgs=cfgs, input_channels=5)
+        if cfgs.IF_DIST:
             self.range_branch = nn.SyncBatchNorm.convert_sync_batchnorm(self.range_branch)
         self.grid_sample_mode = "bilinear"
-        self.weight_initialization()
 
     def prepare(self, batch_dict):
         """SPVCNN's plan (MinkUNet's index plan plus the point -> voxel groupings) plus plan['range'] = the three range plans keyed by
         (h, w) - coordinates only; left under batch_dict['_plan']"""
-        plan = SPVCNN.prepare(self, batch_dict)
+        plan = super().prepare(batch_dict)
         image, pxpy = batch_dict["range_image"], batch_dict["range_pxpy"]
         b, h, w = int(image.shape[0]), int(image.shape[2]), int(image.shape[3])
         h16, w16 = _pooled(h), _pooled(w)
@@ -122,23 +110,7 @@ class RPVNet(MinkUNetBackbone):
             ranges[(hh, ww)] = spF.range_plan(pxpy, b, hh, ww, backward=self.training, err=err,
                                               cells=options.devox_cells and (hh, ww) == (h16, w16) and pxpy.is_cuda)
         plan["range"], plan["range_err"] = ranges, err
-        batch_dict["_plan"] = plan
         return plan
-
-    def _tail(self, k: int, x: SparseTensor, z: PointTensor, fmap: torch.Tensor, ranges: dict) -> PointTensor:
-        """z_k.F = voxel_to_point(x, z_{k-1}).F + range_to_point(fmap) + point_transforms[k](z_{k-1}.F)   (rpvnet.py:648-704)"""
-        lin, bn = self.point_transforms[k][0], self.point_transforms[k][1]
-        if z.F.is_cuda and z.F.dtype in (torch.float32, torch.float16) and spF._dense_ok(lin.in_features, lin.out_features):
-            y = spF._PointwiseConv.apply(z.F, lin.weight.t().contiguous(), spF._identity_rows(z.F.shape[0], z.F.device))
-            y = y + lin.bias.to(y.dtype)
-        else:
-            y = torch.nn.functional.linear(z.F, lin.weight, lin.bias)
-        order = (z.additional_features.get("devox_order") or {}).get(x.s)
-        rplan = ranges[(int(fmap.shape[2]), int(fmap.shape[3]))]
-        out = PointTensor(spF.range_point_tail(y, bn, x.F, z.idx_query[x.s], z.weights[x.s], order, fmap, rplan), z.C,
-                          idx_query=z.idx_query, weights=z.weights)
-        out.additional_features = z.additional_features
-        return out
 
     def _to_range(self, z: PointTensor, ranges: dict, b: int, h: int, w: int) -> torch.Tensor:
         """point_to_range (rpvnet.py:73-91) in the range branch's layout"""
@@ -153,13 +125,7 @@ class RPVNet(MinkUNetBackbone):
         x.F = x.F[:, :self.in_feature_dim]
         plan = batch_dict.get("_plan") or self.prepare(batch_dict)
         ranges = plan["range"]
-        x0 = SparseTensor(spF.spvoxelize(x.F, plan["vox_idx"], plan["vox_counts"]), plan["coords"], 1)     # initial_voxelize
-        x0.cmaps, x0.kmaps = plan["cmaps"], plan["kmaps"]
-        z = PointTensor(x.F, plan["point_coords"], idx_query=plan["tri_idx"], weights=plan["tri_w"])
-        cache = z.additional_features
-        cache["devox_order"], cache["groups"] = plan["tri_order"], {}
-        for key, (idx, counts, groups) in plan["p2v"].items():
-            cache["idx_query"][key], cache["counts"][key], cache["groups"][key] = idx, counts, groups
+        x0, z = self._seed(x, plan)
 
         r_x0 = rb.stem(range_image)
         x0 = spnn.conv_bn_act(self.stem[0], self.stem[1], x0, relu=True)
@@ -216,11 +182,7 @@ class RPVNet(MinkUNetBackbone):
             target = batch_dict["targets"].F.long().cuda(non_blocking=True)
             return self._train_outputs(out, target, batch_dict["lidar"].C[:, :3].float(), batch_dict["offset"])
 
-        if device_tail is not None:       # evaluation on the device (DeviceEvalTail): nothing is un-voxelised to the host
-            return device_tail.run(out, x.C[:, -1], batch_dict["inverse_map"], batch_dict["targets_mapped"], batch_dict["num_points"],
-                                   names=batch_dict["name"])
-        return unvoxelise_predictions(out, x.C[:, -1], batch_dict["inverse_map"], batch_dict["targets_mapped"],
-                                      batch_dict["num_points"], return_logit or return_tta, names=batch_dict["name"], defer=defer)
+        return self._eval_outputs(out, x, batch_dict, return_logit or return_tta, defer, device_tail)
 
     def forward_ensemble(self, batch_dict):
         return self.forward(batch_dict, ensemble=True)

@@ -12,6 +12,9 @@ Module tree, attribute names and therefore every state_dict key, their order and
                    of the 1x1x1 convolutions plus a bias add where both widths are multiples of 32, `torch.nn.functional.linear`
                    elsewhere; then ONE node on ts_point_tail_forward (`functional.point_tail`).
 
+`_build_point_branch`, `_seed` and `_tail` are written for RPVNet (`fusion/rpvnet`) as well, which derives from this class: it hands
+`_tail` a range map and its plans and overrides `_build_branches`.
+
 The stage programs of `minkunet.py` run the whole U-Net in one call and cannot take the point branch between the stages: this model
 always runs module by module.
 
@@ -27,12 +30,13 @@ from taseg_amd import torchsparse
 from taseg_amd.torchsparse import PointTensor, SparseTensor
 from taseg_amd.torchsparse import nn as spnn
 from taseg_amd.torchsparse.nn import functional as spF
-from ...voxel.minkunet.minkunet import MinkUNetBackbone, unvoxelise_predictions
+from ...voxel.minkunet.minkunet import MinkUNetBackbone
 from ...voxel.minkunet.utils import voxelize_index
 from .utils import point_to_voxel, voxel_to_point
 
 __all__ = ["SPVCNN"]
 
+_PLANES = [32, 32, 64, 128, 256, 256, 128, 96, 96]
 _STRIDES = ((1, 1, 1), (16, 16, 16), (4, 4, 4))        # where the point branch meets the U-Net: x0 / x4 / y2 (spvcnn.py:408-443)
 
 
@@ -40,9 +44,19 @@ class SPVCNN(MinkUNetBackbone):
     def __init__(self, model_cfgs, num_class: int):
         super().__init__(model_cfgs, num_class)        # stem .. up4, classifier, dropout, losses: spvcnn.py:212-326 == minkunet.py
         self.name = "spvcnn"
-        cr = model_cfgs.get("cr", 1.0)
-        cs = [int(cr * x) for x in model_cfgs.get("PLANES", [32, 32, 64, 128, 256, 256, 128, 96, 96])]
+        self._build_branches(model_cfgs)
+        self.weight_initialization()
+
+    def _build_branches(self, model_cfgs):
+        """what stands behind the backbone, in state_dict order; RPVNet: one more transform in front, then the range branch"""
+        self._build_point_branch(model_cfgs)
+
+    def _build_point_branch(self, model_cfgs, lead=()):
+        """`multi_scale` and `point_transforms`: Linear + BatchNorm + ReLU from each width to the next along `lead`, then the widths of
+        x0, x4, y2 and y4"""
+        cs = [int(model_cfgs.get("cr", 1.0) * x) for x in model_cfgs.get("PLANES", _PLANES)]
         exp = self.block.expansion
+        widths = [*lead, cs[0], cs[4] * exp, cs[6] * exp, cs[8] * exp]
         if_dist = model_cfgs.IF_DIST
         self.multi_scale = model_cfgs.get("MULTI_SCALE", "concat")
         if self.multi_scale != "concat":
@@ -51,9 +65,7 @@ class SPVCNN(MinkUNetBackbone):
         def transform(inc, outc):
             return nn.Sequential(nn.Linear(inc, outc), nn.SyncBatchNorm(outc) if if_dist else nn.BatchNorm1d(outc), nn.ReLU(True))
 
-        self.point_transforms = nn.ModuleList([transform(cs[0], cs[4] * exp), transform(cs[4] * exp, cs[6] * exp),
-                                               transform(cs[6] * exp, cs[8] * exp)])
-        self.weight_initialization()
+        self.point_transforms = nn.ModuleList([transform(inc, outc) for inc, outc in zip(widths[:-1], widths[1:])])
 
     def prepare(self, batch_dict):
         """the index plan of MinkUNet plus, per stride the point branch voxelises at, (idx_query, counts, grouping) - coordinates
@@ -71,8 +83,20 @@ class SPVCNN(MinkUNetBackbone):
         batch_dict["_plan"] = plan
         return plan
 
-    def _tail(self, k: int, x: SparseTensor, z: PointTensor) -> PointTensor:
-        """z_k = voxel_to_point(x, z_{k-1}); z_k.F += point_transforms[k](z_{k-1}.F)   (spvcnn.py:417-418, 430-431, 443-444)"""
+    def _seed(self, x, plan):
+        """(x0, z): the voxel tensor of initial_voxelize and the point tensor whose cache holds the plan's maps, orders and groupings"""
+        x0 = SparseTensor(spF.spvoxelize(x.F, plan["vox_idx"], plan["vox_counts"]), plan["coords"], 1)     # initial_voxelize
+        x0.cmaps, x0.kmaps = plan["cmaps"], plan["kmaps"]
+        z = PointTensor(x.F, plan["point_coords"], idx_query=plan["tri_idx"], weights=plan["tri_w"])
+        cache = z.additional_features
+        cache["devox_order"], cache["groups"] = plan["tri_order"], {}
+        for key, (idx, counts, groups) in plan["p2v"].items():
+            cache["idx_query"][key], cache["counts"][key], cache["groups"][key] = idx, counts, groups
+        return x0, z
+
+    def _tail(self, k: int, x: SparseTensor, z: PointTensor, fmap=None, ranges=None) -> PointTensor:
+        """z_k = voxel_to_point(x, z_{k-1}); z_k.F += point_transforms[k](z_{k-1}.F)   (spvcnn.py:417-418, 430-431, 443-444); with a
+        map: z_k.F = voxel_to_point(x, z_{k-1}).F + range_to_point(fmap) + point_transforms[k](z_{k-1}.F)   (rpvnet.py:648-704)"""
         lin, bn = self.point_transforms[k][0], self.point_transforms[k][1]
         if z.F.is_cuda and z.F.dtype in (torch.float32, torch.float16) and spF._dense_ok(lin.in_features, lin.out_features):
             # the GEMM of the 1x1x1 convolutions on the identity rulebook, then the bias: 2.0 - 2.6 x ahead of the library's linear,
@@ -82,8 +106,12 @@ class SPVCNN(MinkUNetBackbone):
         else:
             y = torch.nn.functional.linear(z.F, lin.weight, lin.bias)
         order = (z.additional_features.get("devox_order") or {}).get(x.s)
-        out = PointTensor(spF.point_tail(y, bn, x.F, z.idx_query[x.s], z.weights[x.s], order), z.C, idx_query=z.idx_query,
-                          weights=z.weights)
+        if fmap is None:
+            feats = spF.point_tail(y, bn, x.F, z.idx_query[x.s], z.weights[x.s], order)
+        else:
+            rplan = ranges[(int(fmap.shape[2]), int(fmap.shape[3]))]
+            feats = spF.range_point_tail(y, bn, x.F, z.idx_query[x.s], z.weights[x.s], order, fmap, rplan)
+        out = PointTensor(feats, z.C, idx_query=z.idx_query, weights=z.weights)
         out.additional_features = z.additional_features
         return out
 
@@ -91,13 +119,7 @@ class SPVCNN(MinkUNetBackbone):
         x = batch_dict["lidar"]
         x.F = x.F[:, :self.in_feature_dim]
         plan = batch_dict.get("_plan") or self.prepare(batch_dict)
-        x0 = SparseTensor(spF.spvoxelize(x.F, plan["vox_idx"], plan["vox_counts"]), plan["coords"], 1)     # initial_voxelize
-        x0.cmaps, x0.kmaps = plan["cmaps"], plan["kmaps"]
-        z = PointTensor(x.F, plan["point_coords"], idx_query=plan["tri_idx"], weights=plan["tri_w"])
-        cache = z.additional_features
-        cache["devox_order"], cache["groups"] = plan["tri_order"], {}
-        for key, (idx, counts, groups) in plan["p2v"].items():
-            cache["idx_query"][key], cache["counts"][key], cache["groups"][key] = idx, counts, groups
+        x0, z = self._seed(x, plan)
 
         x0 = spnn.conv_bn_act(self.stem[0], self.stem[1], x0, relu=True)
         x0 = spnn.conv_bn_act(self.stem[3], self.stem[4], x0, relu=True)
@@ -134,11 +156,7 @@ class SPVCNN(MinkUNetBackbone):
             target = batch_dict["targets"].F.long().cuda(non_blocking=True)
             return self._train_outputs(out, target, batch_dict["lidar"].C[:, :3].float(), batch_dict["offset"])
 
-        if device_tail is not None:       # evaluation on the device (DeviceEvalTail): nothing is un-voxelised to the host
-            return device_tail.run(out, x.C[:, -1], batch_dict["inverse_map"], batch_dict["targets_mapped"], batch_dict["num_points"],
-                                   names=batch_dict["name"])
-        return unvoxelise_predictions(out, x.C[:, -1], batch_dict["inverse_map"], batch_dict["targets_mapped"],
-                                      batch_dict["num_points"], return_logit or return_tta, names=batch_dict["name"], defer=defer)
+        return self._eval_outputs(out, x, batch_dict, return_logit or return_tta, defer, device_tail)
 
     def forward_ensemble(self, batch_dict):
         return self.forward(batch_dict, ensemble=True)

@@ -428,6 +428,19 @@ class MinkUNetBackbone(BaseSegmentor):
         lazy = LazyScalar(loss)
         return {"loss": loss}, {"loss": lazy}, {"loss": lazy}
 
+    @staticmethod
+    def _eval_outputs(out, x, batch_dict, want_probs, defer, device_tail, ms=False):
+        """The evaluation ending of every forward of this family: the logits `out` of the voxels of `x` leave through `device_tail`
+        (DeviceEvalTail: nothing is un-voxelised to the host) or through `unvoxelise_predictions`.  ms: the keys of a fused
+        multi-scan cloud - its own inverse map, and `point_mask` / `num_points_ms` to keep the current frame's points and trim to
+        the scan's own point count (minkunet_ms.py:433-458)."""
+        args = (out, x.C[:, -1], batch_dict["inverse_map_ms" if ms else "inverse_map"], batch_dict["targets_mapped"],
+                batch_dict["num_points"])
+        kw = {"point_mask": batch_dict["point_mask"], "num_points_ms": batch_dict["num_points_ms"]} if ms else {}
+        if device_tail is not None:
+            return device_tail.run(*args, names=batch_dict["name"], **kw)
+        return unvoxelise_predictions(*args, want_probs, names=batch_dict["name"], defer=defer, **kw)
+
 
 class _PinnedRing:
     """host buffers for the evaluation tail's device -> host copies: page-locked (the copies are asynchronous), grown on demand,
@@ -892,11 +905,7 @@ class MinkUNet(MinkUNetBackbone):
             target = batch_dict["targets"].F.long().cuda(non_blocking=True)
             return self._train_outputs(out, target, batch_dict["lidar"].C[:, :3].float(), batch_dict["offset"])
 
-        if device_tail is not None:       # evaluation on the device (DeviceEvalTail): nothing is un-voxelised to the host
-            return device_tail.run(out, x.C[:, -1], batch_dict["inverse_map"], batch_dict["targets_mapped"], batch_dict["num_points"],
-                                   names=batch_dict["name"])
-        return unvoxelise_predictions(out, x.C[:, -1], batch_dict["inverse_map"], batch_dict["targets_mapped"],
-                                      batch_dict["num_points"], return_logit or return_tta, names=batch_dict["name"], defer=defer)
+        return self._eval_outputs(out, x, batch_dict, return_logit or return_tta, defer, device_tail)
 
     def forward_ensemble(self, batch_dict):
         return self.forward(batch_dict, return_tta=True)

@@ -6,7 +6,7 @@ pose-aligned history scans + time flag, built by the data stage) is already voxe
 unlike `MinkUNet` there is no device re-voxelisation: the stem consumes it directly
 (minkunet_ms.py:386-392).  Same parameters / state_dict as `MinkUNet`.
 """
-from .minkunet import MinkUNetBackbone, unvoxelise_predictions
+from .minkunet import MinkUNetBackbone
 
 __all__ = ["MinkUNetMs"]
 
@@ -29,15 +29,7 @@ class MinkUNetMs(MinkUNetBackbone):
             return self._train_outputs(out_ms, target_ms, batch_dict["lidar_ms"].C[:, :3].float(),
                                        batch_dict["offset_ms"])
 
-        if device_tail is not None:       # evaluation on the device (minkunet.DeviceEvalTail): the mask is compacted there
-            return device_tail.run(out_ms, x_ms.C[:, -1], batch_dict["inverse_map_ms"], batch_dict["targets_mapped"],
-                                   batch_dict["num_points"], point_mask=batch_dict["point_mask"],
-                                   num_points_ms=batch_dict["num_points_ms"], names=batch_dict["name"])
-        # evaluation: un-voxelise onto every point of the fused cloud, keep the current-frame
-        # points (`point_mask`), trim to the scan's own point count (minkunet_ms.py:433-458)
-        return unvoxelise_predictions(out_ms, x_ms.C[:, -1], batch_dict["inverse_map_ms"], batch_dict["targets_mapped"],
-                                      batch_dict["num_points"], return_logit or return_tta, point_mask=batch_dict["point_mask"],
-                                      num_points_ms=batch_dict["num_points_ms"], names=batch_dict["name"], defer=defer)
+        return self._eval_outputs(out_ms, x_ms, batch_dict, return_logit or return_tta, defer, device_tail, ms=True)
 
     def forward_ensemble(self, batch_dict):
         return self.forward(batch_dict, return_tta=True)

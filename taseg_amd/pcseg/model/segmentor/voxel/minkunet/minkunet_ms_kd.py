@@ -16,7 +16,7 @@ from torch import nn
 
 from taseg_amd.torchsparse.nn import functional as spF
 from taseg_amd.options import options
-from .minkunet import LazyScalar, MinkUNetBackbone, unvoxelise_predictions
+from .minkunet import LazyScalar, MinkUNetBackbone
 
 __all__ = ["MinkUNetMsKd"]
 
@@ -121,14 +121,7 @@ class MinkUNetMsKd(MinkUNetBackbone):
             disp = {"loss": LazyScalar(loss), "loss_seg": LazyScalar(loss_seg), "loss_feat_kd": LazyScalar(loss_kd)}
             return {"loss": loss}, disp, dict(disp)
 
-        if device_tail is not None:       # evaluation on the device (minkunet.DeviceEvalTail): the student's tail, as MinkUNetMs
-            return device_tail.run(out_ms, x_ms.C[:, -1], batch_dict["inverse_map_ms"], batch_dict["targets_mapped"],
-                                   batch_dict["num_points"], point_mask=batch_dict["point_mask"],
-                                   num_points_ms=batch_dict["num_points_ms"], names=batch_dict["name"])
-        # the evaluation tail of MinkUNetMs for the whole batch at once (minkunet.unvoxelise_predictions)
-        return unvoxelise_predictions(out_ms, x_ms.C[:, -1], batch_dict["inverse_map_ms"], batch_dict["targets_mapped"],
-                                      batch_dict["num_points"], return_logit or return_tta, point_mask=batch_dict["point_mask"],
-                                      num_points_ms=batch_dict["num_points_ms"], names=batch_dict["name"], defer=defer)
+        return self._eval_outputs(out_ms, x_ms, batch_dict, return_logit or return_tta, defer, device_tail, ms=True)
 
     def forward_ensemble(self, batch_dict):
         return self.forward(batch_dict, return_tta=True)

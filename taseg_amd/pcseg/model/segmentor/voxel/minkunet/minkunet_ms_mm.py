@@ -14,7 +14,7 @@ import torch
 from torch import nn
 
 from taseg_amd.torchsparse import PointTensor
-from .minkunet import LazyScalar, MinkUNetBackbone, unvoxelise_predictions
+from .minkunet import LazyScalar, MinkUNetBackbone
 from .unet2d import UNet2D
 from .unet3d import UNet3D
 from .utils import voxel_to_point_fov
@@ -151,14 +151,7 @@ class MinkUNetMsMm(MinkUNetBackbone):
         if self.ensemble_type == "replace":
             # (out of place: `out_ms` is the classifier's own output - a hook or a caller that holds it keeps its rows)
             out_ms = out_ms.index_copy(0, overlap_rows, out_fusion.to(out_ms.dtype))
-        if device_tail is not None:       # evaluation on the device (minkunet.DeviceEvalTail), as MinkUNetMs
-            return device_tail.run(out_ms, x_ms.C[:, -1], batch_dict["inverse_map_ms"], batch_dict["targets_mapped"],
-                                   batch_dict["num_points"], point_mask=batch_dict["point_mask"],
-                                   num_points_ms=batch_dict["num_points_ms"], names=batch_dict["name"])
-        # the evaluation tail of MinkUNetMs for the whole batch at once (minkunet.unvoxelise_predictions)
-        return unvoxelise_predictions(out_ms, x_ms.C[:, -1], batch_dict["inverse_map_ms"], batch_dict["targets_mapped"],
-                                      batch_dict["num_points"], return_logit or return_tta, point_mask=batch_dict["point_mask"],
-                                      num_points_ms=batch_dict["num_points_ms"], names=batch_dict["name"], defer=defer)
+        return self._eval_outputs(out_ms, x_ms, batch_dict, return_logit or return_tta, defer, device_tail, ms=True)
 
     def forward_ensemble(self, batch_dict):
         return self.forward(batch_dict, return_tta=True)

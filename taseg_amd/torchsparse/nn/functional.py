@@ -1169,6 +1169,8 @@ def gather_rows(feats: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
 
 
 # ------------------------------------------------------------------------------ SPVCNN pieces (csrc/spvcnn.hip)
+# The hand-over of the point branch - one autograd node `_PointTail` and one body `_hand_over` - serves `point_tail` here and
+# `range_point_tail` of the RPVNet pieces below; the map operand is absent in the first.
 # Private switches, as above: False selects what the kernel replaces - ts_voxelize_forward's float atomics / the module chain -
 # for tools/time_spvcnn_step.py's baseline.  Nothing else reads them.
 _MEAN_KERNEL = True
@@ -1261,29 +1263,76 @@ def _tail_bn_backward(g, mask, y, stats, weight):
     return grad_y, gwb
 
 
+def _tail_launch(y, vox, idx, w, pix, bidx, bw, mean, invstd, gamma, beta, want_mask=False):
+    """(out, mask | None) of ts_point_tail_forward, or of ts_range_point_tail_forward where there are map rows `pix`"""
+    if pix is None:
+        return B.point_tail_forward(y, vox, idx, w, mean, invstd, gamma, beta, want_mask=want_mask)
+    return B.range_point_tail_forward(y, vox, idx, w, pix, bidx, bw, mean, invstd, gamma, beta, want_mask=want_mask)
+
+
 class _PointTail(Function):
-    """devoxelize(vox) + relu(BN_train(y)) as ONE node: batch statistics from ts_bn_sync_stats + ts_bn_finalize (which also moves the
-    running buffers), one launch of ts_point_tail_forward; the gradient of the result goes unchanged to the devoxelisation adjoint the
-    plan's order selects and to ts_bn_act_train_backward with the mask the forward wrote."""
+    """devoxelize(vox) [+ range_to_point(map rows pix)] + relu(BN_train(y)) as ONE node: batch statistics from ts_bn_sync_stats +
+    ts_bn_finalize (which also moves the running buffers), one launch of ts_point_tail_forward - of ts_range_point_tail_forward where
+    there is a map (pix, bidx, bw, border; all None without one: no second adjoint).  The gradient of the result goes unchanged to the
+    devoxelisation adjoints the plans' orders select and to ts_bn_act_train_backward with the mask the forward wrote."""
 
     @staticmethod
-    def forward(ctx, y, vox, weight, bias, running_mean, running_var, nbt, momentum, eps, idx, w, order):
+    def forward(ctx, y, vox, pix, weight, bias, running_mean, running_var, nbt, momentum, eps, idx, w, order, bidx, bw, border):
         from .batchnorm import _bump
         stats = _tail_batch_stats(y, running_mean, running_var, nbt, momentum, eps)
-        out, mask = B.point_tail_forward(y, vox, idx, w, stats[0], stats[1], weight, bias, want_mask=True)
+        out, mask = _tail_launch(y, vox, idx, w, pix, bidx, bw, stats[0], stats[1], weight, bias, want_mask=True)
         _bump(running_mean, running_var)
         ctx.save_for_backward(y, weight, stats, mask)
-        ctx.maps, ctx.m = (idx, w, order), vox.shape[0]
+        ctx.maps, ctx.m = (idx, w, order, bidx, bw, border), (vox.shape[0], None if pix is None else pix.shape[0])
         return out
 
     @staticmethod
     def backward(ctx, grad_out):
         y, weight, stats, mask = ctx.saved_tensors
-        idx, w, order = ctx.maps
+        idx, w, order, bidx, bw, border = ctx.maps
         g = grad_out.contiguous().to(y.dtype)
-        grad_vox = _tail_gather_adjoint(g, idx, w, ctx.m, order) if ctx.needs_input_grad[1] else None
+        grad_vox = _tail_gather_adjoint(g, idx, w, ctx.m[0], order) if ctx.needs_input_grad[1] else None
+        grad_pix = _tail_gather_adjoint(g, bidx, bw, ctx.m[1], border) if ctx.needs_input_grad[2] else None
         grad_y, gwb = _tail_bn_backward(g, mask, y, stats, weight)
-        return grad_y, grad_vox, gwb[0], gwb[1], None, None, None, None, None, None, None, None
+        return (grad_y, grad_vox, grad_pix, gwb[0], gwb[1]) + (None,) * 11
+
+
+def _hand_over(kernel, y, bn, vox_feats, idx, w, order, fmap=None, range_plan=None):
+    """the body of `point_tail` (no map) and `range_point_tail`; kernel: the caller's private switch"""
+    from .modules import _sync_group
+    group = _sync_group(bn)
+    c = y.shape[1] if y.dim() == 2 else 0
+    half = y.is_cuda and (_amp_half(y) or vox_feats.dtype == torch.float16)
+    dt = _rows_dtype(half, c)
+    ok_types = (torch.float32, torch.float16)
+    usable = kernel and group is None and y.is_cuda and y.dim() == 2 and vox_feats.shape[0] > 0 \
+        and y.dtype in ok_types and vox_feats.dtype in ok_types and (fmap is None or fmap.dtype in ok_types) \
+        and bn.affine and bn.track_running_stats and bn.weight.dtype == torch.float32 and y.shape[0] > 0 and c <= 1024 \
+        and c % (8 if dt == torch.float16 else 4) == 0
+    graph = torch.is_grad_enabled() and (y.requires_grad or vox_feats.requires_grad or bn.weight.requires_grad
+                                         or (fmap is not None and fmap.requires_grad))
+    if usable and ((bn.training and bn.momentum is not None and y.shape[0] > 1) or (not bn.training and not graph)):
+        rows = bidx = bw = border = None
+        if fmap is not None:
+            assert tuple(fmap.shape[0:1] + fmap.shape[2:]) == range_plan["shape"], "range_point_tail: plan of another resolution"
+            bidx, bw, border = range_plan["bidx"], range_plan["bw"], range_plan["order"]
+        idx, w = idx.int().contiguous(), w.contiguous().float()
+        with _no_autocast():
+            if fmap is not None:
+                rows = _map_rows(fmap).contiguous().to(dt)
+            y, vox = y.contiguous().to(dt), vox_feats.contiguous().to(dt)
+            if bn.training:
+                out = _PointTail.apply(y, vox, rows, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked,
+                                       bn.momentum, bn.eps, idx, w, order, bidx, bw, border)
+            else:
+                invstd = torch.rsqrt(bn.running_var.float() + bn.eps)
+                out, _ = _tail_launch(y, vox, idx, w, rows, bidx, bw, bn.running_mean.float(), invstd, bn.weight.detach(),
+                                      bn.bias.detach())
+        return out.half() if half else out
+    out = spdevoxelize(vox_feats, idx, w, order)
+    if fmap is not None:
+        out = out + range_to_point(fmap, range_plan)
+    return out + torch.relu(bn(y))
 
 
 def point_tail(y: torch.Tensor, bn, vox_feats: torch.Tensor, idx: torch.Tensor, w: torch.Tensor, order=None) -> torch.Tensor:
@@ -1292,33 +1341,11 @@ def point_tail(y: torch.Tensor, bn, vox_feats: torch.Tensor, idx: torch.Tensor, 
     ts_point_tail_forward (csrc/spvcnn.hip) where the module trains on local statistics, or evaluates without a graph; the chain of
     the module, ReLU, `spdevoxelize` and the add where statistics are shared between ranks, where an evaluation-mode pass records a
     graph (its BatchNorm backward has no kernel here), on the host, and for widths the kernel does not take."""
-    from .batchnorm import fast_path_ok
-    from .modules import _sync_group
-    group = _sync_group(bn)
-    c = y.shape[1] if y.dim() == 2 else 0
-    half = y.is_cuda and (_amp_half(y) or vox_feats.dtype == torch.float16)
-    dt = _rows_dtype(half, c)
-    usable = _POINT_TAIL_KERNEL and group is None and y.is_cuda and y.dim() == 2 and vox_feats.shape[0] > 0 \
-        and y.dtype in (torch.float32, torch.float16) and vox_feats.dtype in (torch.float32, torch.float16) \
-        and bn.affine and bn.track_running_stats and bn.weight.dtype == torch.float32 and y.shape[0] > 0 and c <= 1024 \
-        and c % (8 if dt == torch.float16 else 4) == 0
-    graph = torch.is_grad_enabled() and (y.requires_grad or vox_feats.requires_grad or bn.weight.requires_grad)
-    if usable and bn.training and bn.momentum is not None and y.shape[0] > 1:
-        idx, w = idx.int().contiguous(), w.contiguous().float()
-        with _no_autocast():
-            out = _PointTail.apply(y.contiguous().to(dt), vox_feats.contiguous().to(dt), bn.weight, bn.bias, bn.running_mean,
-                                   bn.running_var, bn.num_batches_tracked, bn.momentum, bn.eps, idx, w, order)
-        return out.half() if half else out
-    if usable and not bn.training and not graph:
-        with _no_autocast():
-            invstd = torch.rsqrt(bn.running_var.float() + bn.eps)
-            out, _ = B.point_tail_forward(y.contiguous().to(dt), vox_feats.contiguous().to(dt), idx.int().contiguous(),
-                                          w.contiguous().float(), bn.running_mean.float(), invstd, bn.weight.detach(), bn.bias.detach())
-        return out.half() if half else out
-    return spdevoxelize(vox_feats, idx, w, order) + torch.relu(bn(y))
+    return _hand_over(_POINT_TAIL_KERNEL, y, bn, vox_feats, idx, w, order)
 
 
 # ------------------------------------------------------------------------------ RPVNet pieces (csrc/rpvnet.hip)
+# `range_point_tail` is a call into `_hand_over` of the SPVCNN pieces with the map as one more operand.
 # Private switch, as above: False selects the chain for tools/time_rpvnet_step.py's baseline.  Nothing else reads it.
 _RANGE_TAIL_KERNEL = True
 
@@ -1401,63 +1428,11 @@ def point_to_range(feats: torch.Tensor, plan: dict, b: int, h: int, w: int) -> t
     return rows.view(b, h, w, feats.shape[1]).permute(0, 3, 1, 2)
 
 
-class _RangePointTail(Function):
-    """devoxelize(vox) + range_to_point(map rows) + relu(BN_train(y)) as ONE node on ts_range_point_tail_forward: `_PointTail` with
-    one more gathered operand.  The gradient of the result goes unchanged to the two devoxelisation adjoints and to
-    ts_bn_act_train_backward with the mask."""
-
-    @staticmethod
-    def forward(ctx, y, vox, pix, weight, bias, running_mean, running_var, nbt, momentum, eps, idx, w, order, bidx, bw, border):
-        from .batchnorm import _bump
-        stats = _tail_batch_stats(y, running_mean, running_var, nbt, momentum, eps)
-        out, mask = B.range_point_tail_forward(y, vox, idx, w, pix, bidx, bw, stats[0], stats[1], weight, bias, want_mask=True)
-        _bump(running_mean, running_var)
-        ctx.save_for_backward(y, weight, stats, mask)
-        ctx.maps, ctx.m = (idx, w, order, bidx, bw, border), (vox.shape[0], pix.shape[0])
-        return out
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        y, weight, stats, mask = ctx.saved_tensors
-        idx, w, order, bidx, bw, border = ctx.maps
-        g = grad_out.contiguous().to(y.dtype)
-        grad_vox = _tail_gather_adjoint(g, idx, w, ctx.m[0], order) if ctx.needs_input_grad[1] else None
-        grad_pix = _tail_gather_adjoint(g, bidx, bw, ctx.m[1], border) if ctx.needs_input_grad[2] else None
-        grad_y, gwb = _tail_bn_backward(g, mask, y, stats, weight)
-        return (grad_y, grad_vox, grad_pix, gwb[0], gwb[1]) + (None,) * 11
-
-
 def range_point_tail(y: torch.Tensor, bn, vox_feats: torch.Tensor, idx: torch.Tensor, w: torch.Tensor, order, fmap: torch.Tensor,
                      range_plan: dict) -> torch.Tensor:
     """(spdevoxelize(vox_feats, idx, w, order) + range_to_point(fmap, range_plan)) + relu(bn(y)): RPVNet's three-way hand-over
     `z.F + r_z + z_point` (rpvnet.py:648-704, behind the Linear of `point_transforms`) for a BatchNorm1d / SyncBatchNorm module `bn`
-    on point rows y [N, C] and a map fmap [B, C, h, w].  One launch of ts_range_point_tail_forward under the conditions of
-    `point_tail`; the chain where statistics are shared between ranks, where an evaluation-mode pass records a graph, on the host,
-    and for widths the kernel does not take."""
-    from .modules import _sync_group
-    group = _sync_group(bn)
-    c = y.shape[1] if y.dim() == 2 else 0
-    half = y.is_cuda and (_amp_half(y) or vox_feats.dtype == torch.float16)
-    dt = _rows_dtype(half, c)
-    ok_types = (torch.float32, torch.float16)
-    usable = _RANGE_TAIL_KERNEL and group is None and y.is_cuda and y.dim() == 2 and vox_feats.shape[0] > 0 \
-        and y.dtype in ok_types and vox_feats.dtype in ok_types and fmap.dtype in ok_types \
-        and bn.affine and bn.track_running_stats and bn.weight.dtype == torch.float32 and y.shape[0] > 0 and c <= 1024 \
-        and c % (8 if dt == torch.float16 else 4) == 0
-    graph = torch.is_grad_enabled() and (y.requires_grad or vox_feats.requires_grad or fmap.requires_grad or bn.weight.requires_grad)
-    if usable and ((bn.training and bn.momentum is not None and y.shape[0] > 1) or (not bn.training and not graph)):
-        assert tuple(fmap.shape[0:1] + fmap.shape[2:]) == range_plan["shape"], "range_point_tail: plan of another resolution"
-        idx, w = idx.int().contiguous(), w.contiguous().float()
-        bidx, bw = range_plan["bidx"], range_plan["bw"]
-        with _no_autocast():
-            rows = _map_rows(fmap).contiguous().to(dt)
-            if bn.training:
-                out = _RangePointTail.apply(y.contiguous().to(dt), vox_feats.contiguous().to(dt), rows, bn.weight, bn.bias,
-                                            bn.running_mean, bn.running_var, bn.num_batches_tracked, bn.momentum, bn.eps, idx, w,
-                                            order, bidx, bw, range_plan["order"])
-            else:
-                invstd = torch.rsqrt(bn.running_var.float() + bn.eps)
-                out, _ = B.range_point_tail_forward(y.contiguous().to(dt), vox_feats.contiguous().to(dt), idx, w, rows, bidx, bw,
-                                                    bn.running_mean.float(), invstd, bn.weight.detach(), bn.bias.detach())
-        return out.half() if half else out
-    return spdevoxelize(vox_feats, idx, w, order) + range_to_point(fmap, range_plan) + torch.relu(bn(y))
+    on point rows y [N, C] and a map fmap [B, C, h, w].  `point_tail`'s body with the map as one more gathered operand: one launch of
+    ts_range_point_tail_forward under the conditions of `point_tail`; the chain where statistics are shared between ranks, where an
+    evaluation-mode pass records a graph, on the host, and for widths the kernel does not take."""
+    return _hand_over(_RANGE_TAIL_KERNEL, y, bn, vox_feats, idx, w, order, fmap, range_plan)

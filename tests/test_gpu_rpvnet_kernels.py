@@ -307,3 +307,57 @@ def test_range_point_tail_falls_back_to_the_chain_where_it_must(monkeypatch):
     ref, bar, *_ = R.tail64(y, vox, idx, tw, rows, plan["bidx"].cpu().numpy(), plan["bw"].cpu().numpy(), mean, is64, gamma, beta)
     for got in (kernel, off):
         assert (np.abs(got.double().cpu().numpy() - ref) <= bar + R.U * np.abs(ref)).all()       # (+ invstd's own rounding)
+
+
+@pytest.mark.parametrize("half", [False, True], ids=["fp32", "half"])
+def test_range_hand_over_without_a_map_term_is_point_tail_bit_for_bit(half):
+    """Through the functional layer, in training mode: with every corner of the plan -1 and a map of zeros `range_point_tail` is
+    `point_tail` - the result, the gradient of y, the gradient of the voxel rows, and what the BatchNorm module takes home."""
+    from taseg_amd import backend as B
+    from taseg_amd.torchsparse.nn import functional as F
+    n, c, b, h, w = 65, 32, 2, 4, 128
+    idx, tw, m, pxpy, y, vox, _, _, _, gamma, beta = R.tail_inputs(n, c, half, 41, b, h, w)
+    it, wt = _dev(idx), _dev(tw)
+    order = B.devox_csr(it, wt, m)
+    plan = F.range_plan(_dev(pxpy), b, h, w, backward=False)
+    plan["bidx"], plan["bw"] = torch.full_like(plan["bidx"], -1), torch.zeros_like(plan["bw"])
+    fmap = torch.zeros((b, c, h, w), dtype=_dev(y).dtype, device="cuda").contiguous(memory_format=torch.channels_last)
+    g = _dev(np.random.RandomState(12).randn(n, c).astype(y.dtype))
+    got = []
+    for ranged in (False, True):
+        bn = torch.nn.BatchNorm1d(c).cuda().train()
+        with torch.no_grad():
+            bn.weight.copy_(torch.from_numpy(gamma))
+            bn.bias.copy_(torch.from_numpy(beta))
+        yt, vt = _dev(y).requires_grad_(), _dev(vox).requires_grad_()
+        out = F.range_point_tail(yt, bn, vt, it, wt, order, fmap, plan) if ranged else F.point_tail(yt, bn, vt, it, wt, order)
+        assert out.dtype == yt.dtype and out.grad_fn is not None and "_PointTail" in type(out.grad_fn).__name__
+        out.backward(g)
+        got.append((out.detach(), yt.grad, vt.grad, bn.weight.grad, bn.bias.grad, bn.running_mean, bn.running_var))
+    for name, p, q in zip(("out", "grad y", "grad vox", "grad gamma", "grad beta", "running mean", "running var"), *got):
+        assert torch.equal(p, q), name
+    assert bool(got[0][2].abs().sum() > 0)
+
+
+@pytest.mark.parametrize("half", [False, True], ids=["fp32", "half"])
+def test_range_point_tail_in_evaluation_mode_is_the_kernel_on_the_running_statistics(half):
+    """no graph, module in evaluation mode: the bits of the kernel the training node launches, fed the running buffers"""
+    from taseg_amd import backend as B
+    from taseg_amd.torchsparse.nn import functional as F
+    n, c, b, h, w = 2, 32, 2, 4, 128
+    idx, tw, m, pxpy, y, vox, rows, mean, invstd, gamma, beta = R.tail_inputs(n, c, half, 43, b, h, w)
+    bn = torch.nn.BatchNorm1d(c).cuda().eval()
+    with torch.no_grad():
+        bn.weight.copy_(torch.from_numpy(gamma))
+        bn.bias.copy_(torch.from_numpy(beta))
+        bn.running_mean.copy_(torch.from_numpy(mean))
+        bn.running_var.copy_(torch.from_numpy(1.0 / (invstd * invstd)))
+    yt, vt, it, wt, rt = (_dev(a) for a in (y, vox, idx, tw, rows))
+    ft = rt.view(b, h, w, c).permute(0, 3, 1, 2)
+    plan = F.range_plan(_dev(pxpy), b, h, w, backward=False)
+    with torch.no_grad():
+        out = F.range_point_tail(yt, bn, vt, it, wt, None, ft, plan)
+        want, _ = B.range_point_tail_forward(yt, vt, it, wt, rt, plan["bidx"], plan["bw"], bn.running_mean,
+                                             torch.rsqrt(bn.running_var + bn.eps), bn.weight, bn.bias, want_mask=True)
+    assert out.dtype == yt.dtype and torch.equal(out, want)
+    assert int(bn.num_batches_tracked) == 0 and np.array_equal(bn.running_mean.cpu().numpy(), mean)

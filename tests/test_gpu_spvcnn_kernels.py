@@ -269,3 +269,25 @@ def test_point_tail_falls_back_to_the_chain_where_it_must(monkeypatch):
     ref = d64 + np.maximum(bn64, 0.0)
     for got in (kernel, off):
         assert (np.abs(got.double().cpu().numpy() - ref) <= bar).all()
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float16], ids=["fp32", "half"])
+def test_point_tail_in_evaluation_mode_is_the_kernel_on_the_running_statistics(dtype):
+    """no graph, module in evaluation mode: the bits of the kernel the training node launches, fed the running buffers"""
+    from taseg_amd import backend as B
+    from taseg_amd.torchsparse.nn import functional as F
+    n, c = 2, 32
+    idx, w, m, y, vox, mean, invstd, gamma, beta = _tail_inputs(n, c, dtype, 43)
+    bn = torch.nn.BatchNorm1d(c).cuda().eval()
+    with torch.no_grad():
+        bn.weight.copy_(torch.from_numpy(gamma))
+        bn.bias.copy_(torch.from_numpy(beta))
+        bn.running_mean.copy_(torch.from_numpy(mean))
+        bn.running_var.copy_(torch.from_numpy(1.0 / (invstd * invstd)))
+    yt, vt, it, wt = (torch.from_numpy(a).cuda() for a in (y, vox, idx, w))
+    with torch.no_grad():
+        out = F.point_tail(yt, bn, vt, it, wt)
+        want, _ = B.point_tail_forward(yt, vt, it, wt, bn.running_mean, torch.rsqrt(bn.running_var + bn.eps), bn.weight, bn.bias,
+                                       want_mask=True)
+    assert out.dtype == dtype and torch.equal(out, want)
+    assert int(bn.num_batches_tracked) == 0 and np.array_equal(bn.running_mean.cpu().numpy(), mean)
