@@ -557,6 +557,48 @@ int ts_range_point_tail_forward(const void *y, const void *vox, const int32_t *i
 int ts_range_inputs(const float *feat, int64_t ld, const int32_t *batch, const float *cut, int64_t n, int32_t B, int32_t H, int32_t W,
                     float *pxpy, int32_t *table, float *image, int32_t *err, ts_stream_t stream);
 
+/* The range-view family's data stage (LaserScan.do_range_projection, pcseg/data/dataset/semantickitti/laserscan.py:182-238, and
+ * SemkittiRangeViewDataset.prepare_input_label_semantic_with_mask, semantickitti_rv.py:284-301), two launches for the whole batch.
+ * feat [n, ld >= 4] float = x, y, z, remission per row; batch [n] int32; first [B] int32 = the first row of every scan (the rows of
+ * a scan are consecutive); label [n] int32 or NULL (then label_rv is NULL too); fov_up / fov_down in degrees.
+ *   per row, in the reference's float32 chain (numpy 2: Python scalars are weak), operation by operation:
+ *     depth = sqrtf((x x + y y) + z z); yaw = -(float)atan2((double)y, (double)x); pitch = (float)asin((double)(z / depth));
+ *     proj_x = 0.5f (yaw / (float)pi + 1.0f) W; proj_y = (1.0f - (pitch + (float)|fov_down|) / (float)fov) H; floor; clamp to
+ *     [0, W - 1] / [0, H - 1].  (numpy's own float32 arctan2 / arcsin are not correctly rounded; these are.)
+ *   proj_x, proj_y [n] int32, unproj_range [n] float in input order
+ *   table [B, H, W] uint64, pre-filled with all ones: ONE atomicMin per row of (bits of depth) << 32 | (row - first[b]): the winner
+ *     of a pixel is the row of smallest depth, the lowest index among equal depths - the reference's descending stable argsort
+ *     followed by "last assignment wins" - in any arrival order
+ *   scan_rv [B, 6, H, W] float = the winner's x / 50, y / 50, z / 3, remission, depth / 80 (float32 divisions), mask
+ *   proj_range [B, H, W] float, proj_idx [B, H, W] int32 (index within the scan, -1: empty), label_rv [B, 1, H, W] int64
+ *   a pixel without rows: -1 / 50, -1 / 50, -1 / 3, -1, -1 / 80, 0; range -1; index -1; label 0
+ *   REPRODUCED: mask = (proj_idx > 0) (laserscan.py:238), so a pixel won by a scan's row 0 carries real values and mask 0
+ *   err [1] int32, OR-ed into: 16 a non-finite coordinate, 32 depth == 0, 1 a batch index outside [0, B) or a row in front of its
+ *     scan's first; such a row takes no part and gets proj_x = proj_y = -1, unproj_range = -1.  No host read. */
+#define TS_RV_ERR_BATCH 1
+#define TS_RV_ERR_PIXEL 2
+#define TS_RV_ERR_NONFINITE 16
+#define TS_RV_ERR_ORIGIN 32
+int ts_rv_project(const float *feat, int64_t ld, const int32_t *batch, const int32_t *first, const int32_t *label, int64_t n,
+                  int32_t B, int32_t H, int32_t W, double fov_up, double fov_down, int32_t *proj_x, int32_t *proj_y,
+                  float *unproj_range, uint64_t *table, float *scan_rv, float *proj_range, int32_t *proj_idx, int64_t *label_rv,
+                  int32_t *err, ts_stream_t stream);
+
+/* The range-view family's kNN post-processing (KNN.forward, pcseg/model/segmentor/range/utils.py:300-341) for a whole batch in one
+ * launch, one lane per point, selection and vote in registers.  proj_range [B, H, W] float, proj_class [B, H, W] int32 (the
+ * per-pixel arg-max); unproj_range, px, py, batch [n]; weight [S S] float = 1 - gaussian as the reference computes it (:320).
+ *   window slot s = (dy + pad) S + dx + pad, pad = (S - 1) / 2; a slot outside the image has range 0 and class 0 (F.unfold's zero
+ *   padding: no wrap in azimuth); a range < 0 becomes +inf (:315); the centre slot's range is the point's own, its class stays the
+ *   pixel's (:317); distance = fabsf(r - r_point) weight[s] (a NaN distance counts as +inf); the K smallest by ascending (distance,
+ *   slot) - THE TIE RULE OF THIS LIBRARY, the reference's topk(sorted=False) states none; with cutoff > 0 a selected slot whose
+ *   distance exceeds it votes for class nclasses (:330-333); label = 1 + the first maximum of the counts of classes 1 ..
+ *   nclasses - 1 (:338), so a point whose votes are all unlabelled or cut off gets class 1; classes outside [0, nclasses] do not vote.
+ *   S in {3, 5, 7}, 1 <= K <= S S, 2 <= nclasses <= 32: anything else returns TS_ERR_UNSUPPORTED.
+ *   err [1] int32, OR-ed into: 2 a px / py outside the image, 1 a batch index outside [0, B); such a point gets label 0. */
+int ts_rv_knn(const float *proj_range, const int32_t *proj_class, const float *unproj_range, const int32_t *px, const int32_t *py,
+              const int32_t *batch, const float *weight, int64_t n, int32_t B, int32_t H, int32_t W, int32_t K, int32_t S,
+              float cutoff, int32_t nclasses, int32_t *label, int32_t *err, ts_stream_t stream);
+
 /* The gate of Cylinder_TS's ReconBlock (cylinder_ts.py:368-384) on rows [n, c]: out = x * (sigmoid(u) + sigmoid(v) + sigmoid(w)),
  * one pass; the backward forms grad_x, grad_u, grad_v, grad_w from grad_out and the four inputs in one pass.  float arithmetic;
  * half != 0: IEEE half storage (c % 8 == 0), else float (c % 4 == 0); 16-byte aligned pointers. */

@@ -20,6 +20,12 @@ def install_as_dropin():
     from .pcseg.model import segmentor as seg
     from .pcseg.model.segmentor import fusion
     from .pcseg.model.segmentor.fusion import rpvnet, spvcnn
+    from .pcseg.model.segmentor import range as range_view
+    from .pcseg.model.segmentor.range import utils as range_utils
+    from .pcseg.model.segmentor.range import salsanext as sn
+    from .pcseg.model.segmentor.range.salsanext import model as sn_model
+    from .pcseg.model.segmentor.range.salsanext.model import semantic as sn_semantic
+    from .pcseg.model.segmentor.range.salsanext.model.semantic import salsanext as sn_file
     names = {"torchsparse": ts, "torchsparse.nn": ts.nn, "torchsparse.nn.functional": ts.nn.functional,
              "torchsparse.nn.utils": ts.nn.utils, "torchsparse.utils": ts.utils,
              "torchsparse.utils.quantize": ts.utils.quantize, "torchsparse.utils.collate": ts.utils.collate,
@@ -27,7 +33,12 @@ def install_as_dropin():
              "pcseg": pc, "pcseg.model": pc.model, "pcseg.loss": pc.loss, "pcseg.optim": pc.optim,
              # (SPVCNN and RPVNet are reached by the reference's module path, not by the registry: pcseg/model/segmentor/__init__.py)
              "pcseg.model.segmentor": seg, "pcseg.model.segmentor.fusion": fusion, "pcseg.model.segmentor.fusion.spvcnn": spvcnn,
-             "pcseg.model.segmentor.fusion.rpvnet": rpvnet}
+             "pcseg.model.segmentor.fusion.rpvnet": rpvnet,
+             # (SalsaNext and the range-view family's losses and kNN post-processing: by the reference's module path, like the two above)
+             "pcseg.model.segmentor.range": range_view, "pcseg.model.segmentor.range.utils": range_utils,
+             "pcseg.model.segmentor.range.salsanext": sn, "pcseg.model.segmentor.range.salsanext.model": sn_model,
+             "pcseg.model.segmentor.range.salsanext.model.semantic": sn_semantic,
+             "pcseg.model.segmentor.range.salsanext.model.semantic.salsanext": sn_file}
     for name, mod in names.items():
         sys.modules.setdefault(name, mod)
     return names

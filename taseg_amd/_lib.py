@@ -104,6 +104,9 @@ SIGNATURES = {
     "ts_point_tail_forward": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i64, _i32, _vp, _vp, _vp]),
     "ts_range_plan": (_i32, [_vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "ts_range_inputs": (_i32, [_vp, _i64, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "ts_rv_project": (_i32, [_vp, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _c.c_double, _c.c_double, _vp, _vp, _vp, _vp, _vp, _vp,
+                             _vp, _vp, _vp, _vp]),
+    "ts_rv_knn": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _c.c_float, _i32, _vp, _vp, _vp]),
     "ts_range_point_tail_forward": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i64, _i64, _i32, _vp,
                                            _vp, _vp]),
     "ts_sigmoid3_gate_forward": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp]),

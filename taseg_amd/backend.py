@@ -2341,3 +2341,62 @@ def range_inputs(feat, batch, cut, b, h, w, err=None):
     L.check(L.load().ts_range_inputs(L.ptr(feat), feat.stride(0) if n else 5, L.ptr(batch), L.ptr(cut), n, b, h, w, L.ptr(pxpy),
                                      L.ptr(table), L.ptr(image), L.ptr(_i32(err, "err")), L.stream()), "ts_range_inputs")
     return image, pxpy, err
+
+
+def rv_project(feat, batch, first, b, h, w, fov_up=3.0, fov_down=-25.0, label=None, err=None):
+    """The range-view projection of a batch of point rows (ts_rv_project: a points kernel and a pixels kernel behind one fill of the
+    winner table).  feat [n, >= 4] float32 (x, y, z, remission), batch [n] int32, first [b] int32 (the first row of every scan),
+    optional label [n] int32.  Returns a dict: scan_rv [b, 6, h, w] float32, proj_range [b, h, w] float32, proj_idx [b, h, w] int32,
+    label_rv [b, 1, h, w] int64 (None without labels), proj_x / proj_y [n] int32, unproj_range [n] float32, err [1] int32."""
+    L.require_device(feat, batch, first)
+    if feat.dtype != torch.float32 or feat.dim() != 2 or feat.shape[1] < 4 or feat.stride(1) != 1:
+        raise ValueError("rv_project: feat must be float32 rows [n, >= 4] (x, y, z, remission)")
+    batch, first = _i32(batch, "batch"), _i32(first, "first")
+    n, b, h, w = feat.shape[0], int(b), int(h), int(w)
+    if batch.shape != (n,) or first.shape != (b,):
+        raise ValueError("rv_project: one batch index per row and one first row per scan")
+    if label is not None:
+        label = _i32(label, "label")
+        if label.shape != (n,):
+            raise ValueError("rv_project: one label per row")
+    dev = feat.device
+    if err is None:
+        err = torch.zeros(1, dtype=torch.int32, device=dev)
+    table = torch.full((b, h, w), -1, dtype=torch.int64, device=dev)
+    out = {"scan_rv": torch.empty((b, 6, h, w), dtype=torch.float32, device=dev),
+           "proj_range": torch.empty((b, h, w), dtype=torch.float32, device=dev),
+           "proj_idx": torch.empty((b, h, w), dtype=torch.int32, device=dev),
+           "label_rv": torch.empty((b, 1, h, w), dtype=torch.int64, device=dev) if label is not None else None,
+           "proj_x": torch.empty(n, dtype=torch.int32, device=dev), "proj_y": torch.empty(n, dtype=torch.int32, device=dev),
+           "unproj_range": torch.empty(n, dtype=torch.float32, device=dev), "err": err}
+    L.check(L.load().ts_rv_project(L.ptr(feat), feat.stride(0) if n else 4, L.ptr(batch), L.ptr(first),
+                                   L.ptr(label) if label is not None else None, n, b, h, w, float(fov_up), float(fov_down),
+                                   L.ptr(out["proj_x"]), L.ptr(out["proj_y"]), L.ptr(out["unproj_range"]), L.ptr(table),
+                                   L.ptr(out["scan_rv"]), L.ptr(out["proj_range"]), L.ptr(out["proj_idx"]),
+                                   L.ptr(out["label_rv"]) if label is not None else None, L.ptr(_i32(err, "err")), L.stream()),
+            "ts_rv_project")
+    return out
+
+
+def rv_knn(proj_range, proj_class, unproj_range, px, py, batch, weight, k, search, cutoff, nclasses, err=None):
+    """(label [n] int32, err [1] int32): the kNN vote of a whole batch in one launch (ts_rv_knn).  proj_range [b, h, w] float32,
+    proj_class [b, h, w] int32, unproj_range [n] float32, px / py / batch [n] int32, weight [search * search] float32."""
+    L.require_device(proj_range, proj_class, unproj_range, px, py, batch, weight)
+    proj_range, unproj_range, weight = _f32(proj_range, "proj_range"), _f32(unproj_range, "unproj_range"), _f32(weight, "weight")
+    proj_class, px, py, batch = _i32(proj_class, "proj_class"), _i32(px, "px"), _i32(py, "py"), _i32(batch, "batch")
+    if proj_range.dim() != 3 or proj_class.shape != proj_range.shape:
+        raise ValueError("rv_knn: proj_range and proj_class must be [b, h, w]")
+    b, h, w = proj_range.shape
+    n, k, search, nclasses = unproj_range.numel(), int(k), int(search), int(nclasses)
+    if unproj_range.shape != (n,) or px.shape != (n,) or py.shape != (n,) or batch.shape != (n,):
+        raise ValueError("rv_knn: one range, px, py and batch index per point")
+    if weight.numel() != search * search:
+        raise ValueError("rv_knn: one weight per window slot")
+    dev = proj_range.device
+    if err is None:
+        err = torch.zeros(1, dtype=torch.int32, device=dev)
+    label = torch.empty(n, dtype=torch.int32, device=dev)
+    L.check(L.load().ts_rv_knn(L.ptr(proj_range), L.ptr(proj_class), L.ptr(unproj_range), L.ptr(px), L.ptr(py), L.ptr(batch),
+                               L.ptr(weight), n, b, h, w, k, search, float(cutoff), nclasses, L.ptr(label),
+                               L.ptr(_i32(err, "err")), L.stream()), "ts_rv_knn")
+    return label, err

@@ -418,16 +418,20 @@ class UpBlock(nn.Module):
         m2 = nn.functional.dropout2d(ones, self.dropout2.p, self.dropout2.training)
         return (torch.cat((m1, ones[:, cq:]), dim=1) * m2).reshape(t, cq + cs)
 
-    def forward(self, x, skip):
+    def _entry(self, x, skip):
+        """PixelShuffle(2), Dropout2d, concat with the skip map, Dropout2d (unet2d.py:104-108)"""
         if options.image_shuffle_cat and B.shuffle_cat_rows_takes(x, skip):
-            cat = _ShuffleCatRows.apply(x, skip, self._masks(x, skip))
-        else:
-            up = self.shuffle(x)
-            if self.drop_out:
-                up = self.dropout1(up)
-            cat = torch.cat((up, skip), dim=1)
-            if self.drop_out:
-                cat = self.dropout2(cat)
+            return _ShuffleCatRows.apply(x, skip, self._masks(x, skip))
+        up = self.shuffle(x)
+        if self.drop_out:
+            up = self.dropout1(up)
+        cat = torch.cat((up, skip), dim=1)
+        if self.drop_out:
+            cat = self.dropout2(cat)
+        return cat
+
+    def forward(self, x, skip):
+        cat = self._entry(x, skip)
         out = _act_bn(self.act1, self.bn1, _conv(self.conv1, cat))
         return self.dropout3(out) if self.drop_out else out
 
