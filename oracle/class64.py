@@ -4,8 +4,8 @@ is imported.  tests/test_class64_host.py checks this file (helpers against brute
 every bar, twelve emulated wrong kernels rejected); tests/test_gpu_class_float64.py holds the kernels against it.  The cases
 (tables, channel pairs, operand families) live here so that both files run the same ones.
 
-Out of scope: the weight-gradient sum that rides on a launch (`side`, an internal argument of ts_conv_class_gemm_ex) and the block
-calls of csrc/block.hip.
+The weight-gradient sum that rides on a launch (`side`, an internal argument of ts_conv_class_gemm_ex) and the block calls of
+csrc/block.hip, which reach these kernels with it: oracle/block64.py, tests/test_block64_host.py, tests/test_gpu_block_float64.py.
 
 The plan.  nbr [K, n] (input row feeding destination row j through offset k, -1 = none) is cut into `groups` groups of gk = K / groups
 offsets.  Per group a row's mask has bit kl set where nbr[gk g + kl][j] >= 0.  class_keys_kernel gives slot g npad + j the key

@@ -15,7 +15,8 @@ No case hands a kernel an index outside its arrays: class64.check_plan compares 
 element and every index against its range, before the first product launch on it, and nothing is launched on a plan that missed;
 every buffer has the size its entry point documents.
 
-Out of scope: the weight-gradient sum that rides on a launch (`side` of ts_conv_class_gemm_ex) and the block calls of csrc/block.hip."""
+The weight-gradient sum that rides on a launch (`side` of ts_conv_class_gemm_ex) and the block calls of csrc/block.hip:
+oracle/block64.py and tests/test_gpu_block_float64.py (tests/test_block64_host.py on the CPU)."""
 import numpy as np
 import pytest
 import torch
