@@ -599,6 +599,66 @@ int ts_rv_knn(const float *proj_range, const int32_t *proj_class, const float *u
               const int32_t *batch, const float *weight, int64_t n, int32_t B, int32_t H, int32_t W, int32_t K, int32_t S,
               float cutoff, int32_t nclasses, int32_t *label, int32_t *err, ts_stream_t stream);
 
+/* The range-view family's point augmentation (LaserScan.open_scan, laserscan.py:104-143) of a whole batch into a NEW cloud; the
+ * input rows are never written.  feat [n, ld >= 4] float, batch [n] int32 ascending, label [n] int32 or NULL (then out_label is
+ * NULL), first [B] int32 = the first input row of every cloud, params [B, TS_RV_AUG_RECORD] doubles
+ *   { c, s, scale, tx, ty, tz, bits, flip }   bits: 1 rotate, 2 scale, 4 flip, 8 jitter ; flip: 0 .. 3 (1: x, 2: y, 3: both)
+ * with c = cos, s = sin of the angle from the host.  drop [n_drop] int32 or NULL: the clouds' drop lists (np.unique of the
+ * reference's draws: indices WITHIN the cloud), concatenated; drop_off [B + 1] int32 their offsets; keep [n] bytes, pre-filled with
+ * ones by the caller.
+ *   drop   one thread per list entry clears the row's keep byte (a duplicate would write the same value); an index outside its
+ *          cloud sets TS_RV_ERR_DROP and is ignored.  Then the stable compaction of csrc/compact.h: the survivors keep their
+ *          input order, no atomics; a cloud's first output row is the sum of the survivors before it, which the host knows from
+ *          the lengths of the unique lists - no device read.
+ *   arithmetic, in the reference's order, EVERY STEP rounded to float32 (it assigns back into its float32 array after each; this
+ *          is not ts_stage_augment's single rounding):
+ *     flip    sign changes of x and / or y
+ *     scale   x, y (NOT z - reproduced) times (float)scale in float32: np.random.uniform returns a Python float, a weak scalar
+ *     rotate  np.dot(float32 [n, 2], float64 2 x 2) is dgemm: X = fma(y, -s, x c), Y = fma(y, c, x s) in float64, rounded once
+ *     jitter  (float)((double)v + t) per axis
+ *     remission passes through; a step whose bit is clear is skipped: a record without bits returns the input's bits
+ *   out [capacity >= n, 4] float (16-byte aligned), out_label [capacity] int32, out_sample [capacity] int64 and out_sample32
+ *   [capacity] int32 (the survivors' clouds), counts [B] int64 (the survivors per cloud, on the device); rows past the survivors
+ *   are not written.  At most TS_RV_MAX_CLOUDS clouds.  ws: ts_rv_augment_workspace_bytes(n, B) bytes.
+ *   err [1] int32, OR-ed into: TS_RV_ERR_DROP, TS_RV_ERR_BATCH (a batch index outside [0, B): the row is dropped).  One launch for
+ *   the drop lists and three for the compaction; no host read. */
+#define TS_RV_ERR_DROP 64
+#define TS_RV_AUG_RECORD 8
+#define TS_RV_MAX_CLOUDS 64
+size_t ts_rv_augment_workspace_bytes(int64_t n, int32_t B);
+int ts_rv_augment(const float *feat, int64_t ld, const int32_t *batch, const int32_t *label, const int32_t *first, int64_t n,
+                  int32_t B, const double *params, const int32_t *drop, const int32_t *drop_off, int64_t n_drop, uint8_t *keep,
+                  float *out, int32_t *out_label, int64_t *out_sample, int32_t *out_sample32, int64_t capacity, int64_t *counts,
+                  void *ws, size_t ws_bytes, int32_t *err, ts_stream_t stream);
+
+/* The pixels of every class in every image: label [B, 1, H, W] int64, counts [B, TS_RV_CLASSES] int32 pre-filled with zeros and
+ * added into.  Integer additions only: the result does not depend on their order.  A label outside [0, TS_RV_CLASSES) is not
+ * counted.  One launch. */
+#define TS_RV_CLASSES 32
+int ts_rv_label_counts(const int64_t *label, int32_t B, int32_t H, int32_t W, int32_t *counts, ts_stream_t stream);
+
+/* RangeShift, RangeMix, RangePaste and RangeUnion (SemkittiRangeViewDataset.__getitem__, semantickitti_rv.py:137-183;
+ * sample_transform :304-320, MixTeacherSemkitti :360-1700, RangePaste :210-281, RangeUnion :197-207) of a batch of projected
+ * images, one thread per output pixel, one launch.  scan_a [B, 6, H, W] float and label_a [B, 1, H, W] int64: the primaries;
+ * scan_b, label_b: the partners, counts [B, TS_RV_CLASSES] int32 = ts_rv_label_counts(label_b) - all three NULL without partners,
+ * then only the shift applies.  records [B, TS_RV_COMPOSE_RECORD] int32 on the device:
+ *   { shift_a, shift_b, n_row_bounds, n_col_bounds, row_bounds[5], col_bounds[5], mixture, flags }   flags: 1 paste, 2 union
+ * In the reference's order, for output pixel (y, x):
+ *   shift   the primary is read at column (x + shift_a) mod W, the partner at (x + shift_b) mod W (0: none) - the partner is
+ *           shifted before mix, paste and union see it
+ *   mix     every colCrowR strategy is a checkerboard: cell row = the number of row bounds <= y, cell column = the number of
+ *           column bounds <= x (the HOST computes the bounds with the reference's expressions; a bound at or beyond the size
+ *           selects nothing, as the reference's empty slices); mixture 1 takes the primary where cell row + cell column is even,
+ *           mixture 2 the partner there; 0: no mix
+ *   paste   the pixel takes the partner when the partner's label there is one of 2 .. 8, 12, 16, 18, 19 and counts[b][label] > 20
+ *   union   a pixel whose mask (channel 5) after mix and paste is 0 takes the partner - also a pixel won by a scan's row 0
+ *           (the reproduced `proj_idx > 0`)
+ * and ONE copy of the chosen pixel's six values and label to out_scan [B, 6, H, W], out_label [B, 1, H, W] (not in place).  A
+ * record of zeros copies the primary bit for bit. */
+#define TS_RV_COMPOSE_RECORD 16
+int ts_rv_compose(const float *scan_a, const int64_t *label_a, const float *scan_b, const int64_t *label_b, const int32_t *counts,
+                  const int32_t *records, int32_t B, int32_t H, int32_t W, float *out_scan, int64_t *out_label, ts_stream_t stream);
+
 /* The gate of Cylinder_TS's ReconBlock (cylinder_ts.py:368-384) on rows [n, c]: out = x * (sigmoid(u) + sigmoid(v) + sigmoid(w)),
  * one pass; the backward forms grad_x, grad_u, grad_v, grad_w from grad_out and the four inputs in one pass.  float arithmetic;
  * half != 0: IEEE half storage (c % 8 == 0), else float (c % 4 == 0); 16-byte aligned pointers. */

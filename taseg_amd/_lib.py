@@ -107,6 +107,11 @@ SIGNATURES = {
     "ts_rv_project": (_i32, [_vp, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _c.c_double, _c.c_double, _vp, _vp, _vp, _vp, _vp, _vp,
                              _vp, _vp, _vp, _vp]),
     "ts_rv_knn": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _c.c_float, _i32, _vp, _vp, _vp]),
+    "ts_rv_augment_workspace_bytes": (_sz, [_i64, _i32]),
+    "ts_rv_augment": (_i32, [_vp, _i64, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _sz,
+                             _vp, _vp]),
+    "ts_rv_label_counts": (_i32, [_vp, _i32, _i32, _i32, _vp, _vp]),
+    "ts_rv_compose": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
     "ts_range_point_tail_forward": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i64, _i64, _i32, _vp,
                                            _vp, _vp]),
     "ts_sigmoid3_gate_forward": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp]),

@@ -2400,3 +2400,98 @@ def rv_knn(proj_range, proj_class, unproj_range, px, py, batch, weight, k, searc
                                L.ptr(weight), n, b, h, w, k, search, float(cutoff), nclasses, L.ptr(label),
                                L.ptr(_i32(err, "err")), L.stream()), "ts_rv_knn")
     return label, err
+
+
+RV_MAX_CLOUDS, RV_AUG_RECORD, RV_CLASSES, RV_COMPOSE_RECORD = 64, 8, 32, 16           # include/taseg_hip.h: TS_RV_*
+
+
+def rv_augment(feat, batch, first, b, params, label=None, drop=None, drop_off=None, err=None):
+    """LaserScan.open_scan's point augmentation of a batch of clouds into a NEW cloud (ts_rv_augment: one kernel for the drop lists
+    and the three launches of the stable compaction, behind one fill of the keep bytes).  feat [n, >= 4] float32, batch [n] int32,
+    first [b] int32 (the clouds' first input rows), params [b, 8] float64 on the device (c, s, scale, tx, ty, tz, bits, flip),
+    optional label [n] int32, drop [n_drop] int32 (indices within their clouds, concatenated) with drop_off [b + 1] int32.  Returns
+    (out [n, 4] float32, out_label [n] int32 | None, out_batch [n] int32, counts [b] int64, err [1] int32): the survivors in input
+    order in the first rows - the caller knows how many from the lengths of its drop lists.  No host read."""
+    L.require_device(feat, batch, first, params, label, drop, drop_off)
+    if feat.dtype != torch.float32 or feat.dim() != 2 or feat.shape[1] < 4 or feat.stride(1) != 1:
+        raise ValueError("rv_augment: feat must be float32 rows [n, >= 4] (x, y, z, remission)")
+    batch, first = _i32(batch, "batch"), _i32(first, "first")
+    n, b = feat.shape[0], int(b)
+    if b < 1 or b > RV_MAX_CLOUDS:
+        raise ValueError("rv_augment: 1 .. %d clouds (got %d)" % (RV_MAX_CLOUDS, b))
+    if batch.shape != (n,) or first.shape != (b,):
+        raise ValueError("rv_augment: one batch index per row and one first row per cloud")
+    if params.dtype != torch.float64 or params.shape != (b, RV_AUG_RECORD) or not params.is_contiguous():
+        raise ValueError("rv_augment: params must be contiguous float64 [b, %d]" % RV_AUG_RECORD)
+    if label is not None:
+        label = _i32(label, "label")
+        if label.shape != (n,):
+            raise ValueError("rv_augment: one label per row")
+    dev = feat.device
+    keep, n_drop = None, 0
+    if drop is not None:
+        drop, drop_off = _i32(drop, "drop"), _i32(drop_off, "drop_off")
+        if drop.dim() != 1 or drop_off.shape != (b + 1,):
+            raise ValueError("rv_augment: drop [n_drop] and drop_off [b + 1]")
+        n_drop = drop.shape[0]
+        keep = torch.ones(n, dtype=torch.uint8, device=dev)
+    if err is None:
+        err = torch.zeros(1, dtype=torch.int32, device=dev)
+    out = torch.empty((n, 4), dtype=torch.float32, device=dev)
+    out_label = torch.empty(n, dtype=torch.int32, device=dev) if label is not None else None
+    sample = torch.empty(n, dtype=torch.int64, device=dev)
+    sample32 = torch.empty(n, dtype=torch.int32, device=dev)
+    counts = torch.empty(b, dtype=torch.int64, device=dev)
+    ws = torch.empty(L.load().ts_rv_augment_workspace_bytes(n, b), dtype=torch.uint8, device=dev)
+    L.check(L.load().ts_rv_augment(L.ptr(feat), feat.stride(0) if n else 4, L.ptr(batch), L.ptr(label), L.ptr(first), n, b,
+                                   L.ptr(params), L.ptr(drop), L.ptr(drop_off), n_drop, L.ptr(keep), L.ptr(out), L.ptr(out_label),
+                                   L.ptr(sample), L.ptr(sample32), n, L.ptr(counts), L.ptr(ws), ws.shape[0], L.ptr(_i32(err, "err")),
+                                   L.stream()), "ts_rv_augment")
+    return out, out_label, sample32, counts, err
+
+
+def _rv_images(scan, label, who):
+    if scan.dtype != torch.float32 or scan.dim() != 4 or scan.shape[1] != 6 or not scan.is_contiguous():
+        raise ValueError("%s: scan must be contiguous float32 [b, 6, h, w]" % who)
+    b, _, h, w = scan.shape
+    if label.dtype != torch.int64 or label.shape != (b, 1, h, w) or not label.is_contiguous():
+        raise ValueError("%s: label must be contiguous int64 [b, 1, h, w]" % who)
+    return b, h, w
+
+
+def rv_label_counts(label):
+    """[b, 32] int32: the pixels of every class in every image of label [b, 1, h, w] int64 (ts_rv_label_counts: one kernel behind
+    one fill)."""
+    L.require_device(label)
+    if label.dtype != torch.int64 or label.dim() != 4 or label.shape[1] != 1 or not label.is_contiguous():
+        raise ValueError("rv_label_counts: label must be contiguous int64 [b, 1, h, w]")
+    b, _, h, w = label.shape
+    counts = torch.zeros((b, RV_CLASSES), dtype=torch.int32, device=label.device)
+    L.check(L.load().ts_rv_label_counts(L.ptr(label), b, h, w, L.ptr(counts), L.stream()), "ts_rv_label_counts")
+    return counts
+
+
+def rv_compose(scan_a, label_a, records, scan_b=None, label_b=None, counts=None):
+    """(scan_rv [b, 6, h, w] float32, label_rv [b, 1, h, w] int64): RangeShift, RangeMix, RangePaste and RangeUnion of a batch of
+    projected images in one launch (ts_rv_compose).  records [b, 16] int32 on the device (shift_a, shift_b, n_row_bounds,
+    n_col_bounds, 5 row bounds, 5 column bounds, mixture, flags: 1 paste, 2 union); scan_b / label_b: the partner images, counts
+    [b, 32] int32 their class counts (rv_label_counts) - without them only the shift applies."""
+    L.require_device(scan_a, label_a, records, scan_b, label_b, counts)
+    b, h, w = _rv_images(scan_a, label_a, "rv_compose")
+    records = _i32(records, "records")
+    if records.shape != (b, RV_COMPOSE_RECORD) or not records.is_contiguous():
+        raise ValueError("rv_compose: records must be contiguous int32 [b, %d]" % RV_COMPOSE_RECORD)
+    if scan_b is not None:
+        if label_b is None or counts is None:
+            raise ValueError("rv_compose: the partner images come with their labels and class counts")
+        if _rv_images(scan_b, label_b, "rv_compose") != (b, h, w):
+            raise ValueError("rv_compose: primaries and partners of one shape")
+        counts = _i32(counts, "counts")
+        if counts.shape != (b, RV_CLASSES) or not counts.is_contiguous():
+            raise ValueError("rv_compose: counts must be contiguous int32 [b, %d]" % RV_CLASSES)
+    else:
+        label_b = counts = None
+    out_scan, out_label = torch.empty_like(scan_a), torch.empty_like(label_a)
+    L.check(L.load().ts_rv_compose(L.ptr(scan_a), L.ptr(label_a), L.ptr(scan_b), L.ptr(label_b), L.ptr(counts), L.ptr(records), b, h,
+                                   w, L.ptr(out_scan), L.ptr(out_label), L.stream()), "ts_rv_compose")
+    return out_scan, out_label

@@ -4,10 +4,17 @@
 //                   a norm, two inverse trigonometric functions, an argsort by depth and four fancy assignments - here two kernels.
 //   ts_rv_knn       KNN.forward (pcseg/model/segmentor/range/utils.py:300-341): per scan two [1, S S, n] unfold gathers, a topk, two
 //                   gathers and a scatter_add_ into a one-hot - here one lane per point, selection and vote in registers.
+//   ts_rv_augment   LaserScan.open_scan's point augmentation (laserscan.py:104-143: np.delete of the dropped rows, flip, scale, rotate,
+//                   jitter) of a whole batch into a NEW cloud: a kernel that clears a keep byte per dropped row, then the stable
+//                   compaction of compact.h with the augmentation in its rule.
+//   ts_rv_label_counts / ts_rv_compose   RangeShift, RangeMix, RangePaste, RangeUnion (semantickitti_rv.py:137-183, :197-320,
+//                   MixTeacherSemkitti) of a batch of projected images: class counts of the partner images, then one thread per
+//                   output pixel that decides between the primary and the partner and copies once.
 // Every value in the reference's own float32 chain, operation by operation (numpy 2: Python scalars are weak, so the chain stays
 // float32); compiled with -ffp-contract=off.  The one stated difference: numpy's float32 arctan2 / arcsin are not correctly rounded,
 // here they are the (float) of the double functions - as ts_cylinder_cells and ts_range_inputs.
 #include "common.h"
+#include "compact.h"
 
 namespace {
 
@@ -191,6 +198,149 @@ __global__ __launch_bounds__(256) void rv_knn_kernel(const float *__restrict__ p
   label[i] = best_c;
 }
 
+// ------------------------------------------------------------------------------------------------ training augmentation
+// LaserScan.open_scan's point augmentation (laserscan.py:113-143) of one row by one record of TS_RV_AUG_RECORD doubles
+//   { c, s, scale, tx, ty, tz, bits, flip }   bits: 1 rotate, 2 scale, 4 flip, 8 jitter ; flip: 0 .. 3
+// in the reference's order - flip, scale, rotate, jitter - and with ITS roundings: it assigns back into the float32 array after
+// every step, so every step rounds to float32 (not sr_augment's single rounding at the end).  Scale: x and y only, a float32
+// product with (float)scale (a Python float is a weak scalar).  Rotation: np.dot(float32 [n, 2], float64 2 x 2) is dgemm's
+// fused-multiply-add chain in k order, rounded once.  Jitter: float32 += float64 adds in float64.  A step that is off is skipped.
+__device__ __forceinline__ void rv_augment_row(const double *__restrict__ a, float &x, float &y, float &z) {
+#pragma clang fp contract(off)
+  const int bits = (int)a[6];
+  if (bits & 4) {
+    const int flip = (int)a[7];
+    if (flip & 1) x = -x;
+    if (flip & 2) y = -y;
+  }
+  if (bits & 2) {
+    const float f = (float)a[2];
+    x = __fmul_rn(x, f);
+    y = __fmul_rn(y, f);
+  }
+  if (bits & 1) {
+    const double X = x, Y = y, c = a[0], s = a[1];
+    x = (float)fma(Y, -s, X * c);
+    y = (float)fma(Y, c, X * s);
+  }
+  if (bits & 8) {
+    x = (float)((double)x + a[3]);
+    y = (float)((double)y + a[4]);
+    z = (float)((double)z + a[5]);
+  }
+}
+
+// One thread per entry of the concatenated drop lists: entry j belongs to the last cloud b with drop_off[b] <= j and names the
+// row first[b] + drop[j] of the input.  An index outside its cloud sets TS_RV_ERR_DROP and clears nothing.
+__global__ __launch_bounds__(256) void rv_drop_kernel(const int *__restrict__ drop, const int *__restrict__ drop_off, int64_t n_drop,
+                                                      const int *__restrict__ first, int64_t n, int B,
+                                                      unsigned char *__restrict__ keep, int *__restrict__ err) {
+  const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (j >= n_drop) return;
+  int b = 0;
+  for (int k = 1; k < B; ++k)
+    if ((int64_t)drop_off[k] <= j) b = k;
+  const int64_t lo = first[b], hi = b + 1 < B ? (int64_t)first[b + 1] : n, d = drop[j];
+  if (lo < 0 || hi > n || d < 0 || lo + d >= hi) {
+    atomicOr(err, TS_RV_ERR_DROP);
+    return;
+  }
+  keep[lo + d] = 0;
+}
+
+// ts_rv_augment's rule for cp_compact: a row survives when its keep byte is set (no table: every row) and its cloud is in [0, B);
+// the survivor is the augmented row, its label goes with it.
+struct RaRule : CpRule {
+  typedef float4 Row;
+  const float *feat;
+  int64_t ld;
+  const int *batch, *label;
+  const unsigned char *keep;
+  const double *params;      // [n_samples, TS_RV_AUG_RECORD]
+  float4 *out;               // [capacity]
+  int *out_label, *err;
+
+  __device__ __forceinline__ bool keeps(int64_t i, bool in, Row &o, int *s) const {
+    *s = -1;
+    if (!in) return false;
+    const int b = batch[i];
+    if (b < 0 || b >= n_samples) {
+      atomicOr(err, TS_RV_ERR_BATCH);
+      return false;
+    }
+    if (keep && keep[i] == 0) return false;
+    *s = b;
+    const float *p = feat + i * ld;
+    o = make_float4(p[0], p[1], p[2], p[3]);
+    rv_augment_row(params + (int64_t)TS_RV_AUG_RECORD * b, o.x, o.y, o.z);
+    return true;
+  }
+
+  __device__ __forceinline__ void store(int64_t dst, int64_t i, const Row &o) const {
+    out[dst] = o;
+    if (out_label) out_label[dst] = label[i];
+  }
+};
+
+// The pixels of every class in every image: LDS counters per block, then one integer atomicAdd per class that occurred.
+__global__ __launch_bounds__(256) void rv_counts_kernel(const int64_t *__restrict__ label, int64_t hw, int *__restrict__ counts) {
+  __shared__ int h[TS_RV_CLASSES];
+  if (threadIdx.x < TS_RV_CLASSES) h[threadIdx.x] = 0;
+  __syncthreads();
+  const int64_t b = blockIdx.y;
+  for (int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x; r < hw; r += (int64_t)gridDim.x * 256) {
+    const int64_t l = label[b * hw + r];
+    if (l >= 0 && l < TS_RV_CLASSES) atomicAdd(&h[(int)l], 1);
+  }
+  __syncthreads();
+  if (threadIdx.x < TS_RV_CLASSES && h[threadIdx.x] != 0) atomicAdd(counts + b * TS_RV_CLASSES + threadIdx.x, h[threadIdx.x]);
+}
+
+// RangePaste's classes (semantickitti_rv.py:215-279): 2 .. 8, 12, 16, 18, 19
+constexpr unsigned kPasteSet = 0x1FCu | (1u << 12) | (1u << 16) | (1u << 18) | (1u << 19);
+
+// One thread per output pixel (b, y, x): RangeShift, RangeMix, RangePaste, RangeUnion of semantickitti_rv.py:137-183 as ONE choice
+// between the primary's pixel (y, (x + shift_a) mod W) and the partner's (y, (x + shift_b) mod W), then one copy of six values and
+// the label.  rec = records + TS_RV_COMPOSE_RECORD b (layout: include/taseg_hip.h).
+__global__ __launch_bounds__(256) void rv_compose_kernel(const float *__restrict__ scan_a, const int64_t *__restrict__ label_a,
+                                                         const float *__restrict__ scan_b, const int64_t *__restrict__ label_b,
+                                                         const int *__restrict__ counts, const int *__restrict__ records, int B, int H,
+                                                         int W, float *__restrict__ out_scan, int64_t *__restrict__ out_label) {
+  const int64_t hw = (int64_t)H * W;
+  const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (q >= (int64_t)B * hw) return;
+  const int64_t b = q / hw, r = q - b * hw;
+  const int y = (int)(r / W), x = (int)(r - (int64_t)y * W);
+  const int *rec = records + (int64_t)TS_RV_COMPOSE_RECORD * b;
+  const int sa = ((rec[0] % W) + W) % W, sb = ((rec[1] % W) + W) % W;
+  int xa = x + sa, xb = x + sb;
+  if (xa >= W) xa -= W;
+  if (xb >= W) xb -= W;
+  const int64_t ra = (int64_t)y * W + xa, rb = (int64_t)y * W + xb;
+  bool take_b = false;
+  if (scan_b) {
+    const int mixture = rec[14], flags = rec[15];
+    if (mixture == 1 || mixture == 2) {
+      const int nr = min(max(rec[2], 0), 5), nc = min(max(rec[3], 0), 5);
+      int cell = 0;
+      for (int k = 0; k < nr; ++k) cell += rec[4 + k] <= y;
+      for (int k = 0; k < nc; ++k) cell += rec[9 + k] <= x;
+      const bool even = (cell & 1) == 0;
+      take_b = mixture == 1 ? !even : even;
+    }
+    if ((flags & 1) && !take_b) {
+      const int64_t lb = label_b[b * hw + rb];
+      if (lb >= 0 && lb < TS_RV_CLASSES && ((kPasteSet >> (int)lb) & 1u) && counts[b * TS_RV_CLASSES + lb] > 20) take_b = true;
+    }
+    if ((flags & 2) && !take_b && scan_a[(b * 6 + 5) * hw + ra] == 0.f) take_b = true;
+  }
+  const float *src = take_b ? scan_b + b * 6 * hw + rb : scan_a + b * 6 * hw + ra;
+  float *dst = out_scan + b * 6 * hw + r;
+#pragma unroll
+  for (int c = 0; c < 6; ++c) dst[c * hw] = src[c * hw];
+  out_label[q] = take_b ? label_b[b * hw + rb] : label_a[b * hw + ra];
+}
+
 }  // namespace
 
 extern "C" int ts_rv_project(const float *feat, int64_t ld, const int32_t *batch, const int32_t *first, const int32_t *label, int64_t n,
@@ -241,5 +391,58 @@ extern "C" int ts_rv_knn(const float *proj_range, const int32_t *proj_class, con
   else TS_RV_KNN(7);
 #undef TS_RV_KNN
   TS_CHECK_LAUNCH("ts_rv_knn");
+  return TS_OK;
+}
+
+extern "C" size_t ts_rv_augment_workspace_bytes(int64_t n, int32_t B) { return cp_compact_bytes(n, B); }
+
+extern "C" int ts_rv_augment(const float *feat, int64_t ld, const int32_t *batch, const int32_t *label, const int32_t *first, int64_t n,
+                             int32_t B, const double *params, const int32_t *drop, const int32_t *drop_off, int64_t n_drop,
+                             uint8_t *keep, float *out, int32_t *out_label, int64_t *out_sample, int32_t *out_sample32,
+                             int64_t capacity, int64_t *counts, void *ws, size_t ws_bytes, int32_t *err, ts_stream_t stream_) {
+  static_assert(TS_RV_MAX_CLOUDS == TS_WAVE, "cp_count_kernel keeps one LDS counter per (wave, sample)");
+  hipStream_t stream = (hipStream_t)stream_;
+  TS_REQUIRE(n >= 0 && n < (int64_t)1 << 30 && ld >= 4 && B >= 1 && B <= TS_RV_MAX_CLOUDS && capacity >= n && n_drop >= 0 &&
+                 n_drop < (int64_t)1 << 30,
+             TS_ERR_INVALID_ARGUMENT, "ts_rv_augment: bad sizes (at most %d clouds)", TS_RV_MAX_CLOUDS);
+  TS_REQUIRE(params && counts && err && ws && ((uintptr_t)ws & 3) == 0 && ((uintptr_t)params & 7) == 0, TS_ERR_INVALID_ARGUMENT,
+             "ts_rv_augment: null or misaligned pointer");
+  TS_REQUIRE(n == 0 || (feat && batch && out && out_sample && out_sample32), TS_ERR_INVALID_ARGUMENT, "ts_rv_augment: null pointer");
+  TS_REQUIRE(((uintptr_t)out & 15) == 0, TS_ERR_INVALID_ARGUMENT, "ts_rv_augment: out must be 16-byte aligned");
+  TS_REQUIRE((label == nullptr) == (out_label == nullptr) || n == 0, TS_ERR_INVALID_ARGUMENT,
+             "ts_rv_augment: label and out_label go together");
+  TS_REQUIRE(drop == nullptr || (drop_off && first && (keep || n == 0)), TS_ERR_INVALID_ARGUMENT,
+             "ts_rv_augment: drop lists need their offsets, the clouds' first rows and the keep bytes");
+  if (drop && n_drop > 0 && n > 0) {
+    rv_drop_kernel<<<(unsigned)ts_cdiv(n_drop, (int64_t)256), 256, 0, stream>>>(drop, drop_off, n_drop, first, n, B, keep, err);
+    TS_CHECK_LAUNCH("ts_rv_augment/drop");
+  }
+  const RaRule r = {{n, capacity, B, out_sample, out_sample32}, feat, ld, batch, label, drop ? keep : nullptr, params, (float4 *)out,
+                    out_label, err};
+  return cp_compact(r, "ts_rv_augment", counts, ws, ws_bytes, stream);
+}
+
+extern "C" int ts_rv_label_counts(const int64_t *label, int32_t B, int32_t H, int32_t W, int32_t *counts, ts_stream_t stream_) {
+  TS_REQUIRE(B > 0 && B <= 65535 && H > 0 && W > 0 && (int64_t)B * H * W < (1LL << 31) - 1, TS_ERR_INVALID_ARGUMENT,
+             "ts_rv_label_counts: bad sizes");
+  TS_REQUIRE(label && counts, TS_ERR_INVALID_ARGUMENT, "ts_rv_label_counts: null pointer");
+  const int64_t hw = (int64_t)H * W;
+  const dim3 grid((unsigned)ts_cdiv(hw, (int64_t)1024), (unsigned)B);
+  rv_counts_kernel<<<grid, 256, 0, (hipStream_t)stream_>>>(label, hw, counts);
+  TS_CHECK_LAUNCH("ts_rv_label_counts");
+  return TS_OK;
+}
+
+extern "C" int ts_rv_compose(const float *scan_a, const int64_t *label_a, const float *scan_b, const int64_t *label_b,
+                             const int32_t *counts, const int32_t *records, int32_t B, int32_t H, int32_t W, float *out_scan,
+                             int64_t *out_label, ts_stream_t stream_) {
+  TS_REQUIRE(B > 0 && H > 0 && W > 0 && (int64_t)B * H * W * 6 < (1LL << 31) - 1, TS_ERR_INVALID_ARGUMENT, "ts_rv_compose: bad sizes");
+  TS_REQUIRE(scan_a && label_a && records && out_scan && out_label, TS_ERR_INVALID_ARGUMENT, "ts_rv_compose: null pointer");
+  TS_REQUIRE(scan_b == nullptr || (label_b && counts), TS_ERR_INVALID_ARGUMENT,
+             "ts_rv_compose: the partner images come with their labels and class counts");
+  TS_REQUIRE(out_scan != scan_a && out_scan != scan_b, TS_ERR_INVALID_ARGUMENT, "ts_rv_compose: not in place");
+  rv_compose_kernel<<<(unsigned)ts_cdiv((int64_t)B * H * W, (int64_t)256), 256, 0, (hipStream_t)stream_>>>(
+      scan_a, label_a, scan_b, label_b, counts, records, B, H, W, out_scan, out_label);
+  TS_CHECK_LAUNCH("ts_rv_compose");
   return TS_OK;
 }
