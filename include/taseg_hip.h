@@ -1553,6 +1553,51 @@ int ts_nusc_fov_cloud(const float *points, const int64_t *labels, const uint8_t 
                       int32_t n_samples, float *out, int64_t *out_labels, int64_t *out_sample, int32_t *out_sample32,
                       int64_t capacity, int64_t *counts, void *ws, size_t ws_bytes, ts_stream_t stream);
 
+/* BatchNorm (training) -> (+ residual) -> LeakyReLU(slope) on rows [N, C]: the range-view trunks' conv -> BN -> LeakyReLU and
+ * conv -> BN -> `out += identity` -> LeakyReLU (R pcseg/model/segmentor/range/fidnet/model/semantic/fidnet.py:114-128).  The
+ * ts_bn_act_train_* contract with a slope, on the same kernel family (csrc/bn.hip, the activation is a template parameter):
+ *   forward   statistics of x; v = (x - mean) * invstd * weight + bias (+ residual); out = v > 0 ? v : v * slope, one rounding at a half
+ *             store; mean / invstd [C] kept; running_mean / running_var / num_batches_tracked (may be NULL) updated; mask = one bit per
+ *             element, set where the STORED value is > 0, in ts_bn_act_forward's layout (a byte per 16-byte chunk: 8 halves, or 4
+ *             floats in the low 4 bits).  A stored 0 has taken the slope branch, as leaky_relu_backward decides it
+ *   backward  g = grad_out * (bit ? 1 : slope); grad_x, grad_residual = g (may be NULL), grad_weight, grad_bias [C] (may be NULL)
+ * half != 0: IEEE half rows (C % 8 == 0), else float (C % 4 == 0); C <= 1024; the mask is required; ws >= the size
+ * ts_bn_train_workspace_bytes gives for c; pointers 16-byte aligned as for ts_bn_act_train_forward. */
+int ts_bn_leaky_act_train_forward(const void *x, const void *residual, const float *weight, const float *bias, float *running_mean,
+                                  float *running_var, int64_t *num_batches_tracked, int64_t n, int32_t c, float eps, float momentum,
+                                  float slope, int32_t half, float *mean, float *invstd, void *out, uint8_t *mask, void *ws,
+                                  size_t ws_bytes, ts_stream_t stream);
+int ts_bn_leaky_act_train_backward(const void *grad_out, const uint8_t *mask, const void *x, const float *mean, const float *invstd,
+                                   const float *weight, int64_t n, int32_t c, float slope, int32_t half, void *grad_x,
+                                   void *grad_residual, float *grad_weight, float *grad_bias, void *ws, size_t ws_bytes,
+                                   ts_stream_t stream);
+
+/* The interpolation decoder of FIDNet / CENet (fidnet.py:300-311, cenet.py:233-243) on channels-last rows, one pass over the result:
+ *   cat [T, H, W, Ca + Cb + 3 Cl] = concat(x [T, H, W, Ca], x1 [T, H, W, Cb], up(xk0), up(xk1), up(xk2)),  xk [T, hk[k], wk[k], Cl],
+ * up = bilinear interpolation to H x W with align_corners = True, evaluated in float32 as ATen's device kernel evaluates it:
+ *   scale = out > 1 ? (float)(in - 1) / (out - 1) : 0;  h1r = scale * (float)y;  h1 = (int)h1r;  h1p = h1 < in - 1;  h1lambda = h1r - h1;
+ *   h0lambda = 1 - h1lambda (the same along the width);
+ *   val = h0lambda * (w0lambda * v[h1][w1] + w1lambda * v[h1][w1 + w1p]) + h1lambda * (w0lambda * v[h1 + h1p][w1] + w1lambda * v[h1 + h1p][w1 + w1p])
+ * every operation rounded on its own, one rounding at a half store.  res0 .. res2 [T, H, W, Cl] (may be NULL) receive the three
+ * interpolated maps as well.  `tables` is what ts_fid_upcat_tables wrote for the same H, W, hk, wk (i0, lambda and the lower bounds
+ * of i0 per level and axis; the size ts_fid_upcat_tables_bytes gives); hk, wk are HOST arrays of 3.
+ *   backward  grad_x, grad_x1 = the slices of grad_cat; grad_xk[k] [T, hk, wk, Cl]: a coarse pixel (r, c) gathers the fine pixels of the
+ *             rows [first_h[max(r - 1, 0)], first_h[r + 1]) and columns [first_w[max(c - 1, 0)], first_w[c + 1]) - no atomics, no fill.
+ *             With g = grad_cat's slice (+ grad_res[k], may be NULL, one float sum), a fine pixel adds (ly[cy] * lx[cx]) * g for corner row
+ *             cy = 0, 1 then corner column cx = 0, 1 where that corner is (r, c).  ORDER: fine row y goes to partial (y - y_lo) % S;
+ *             a partial adds ascending y, then ascending x, then the corners, from 0; the result is partial 0 + partial 1 + ..;
+ *             S = max(1, min(8, (H / hk) / 2, 256 / (Cl / V))), V = 4 (float) or 8 (half).  Two calls give the same bits.
+ * half != 0: IEEE half (channel counts % 8), else float (% 4); each operand <= 1024 channels, else TS_ERR_UNSUPPORTED; 16-byte aligned. */
+size_t ts_fid_upcat_tables_bytes(int32_t H, int32_t W);
+int ts_fid_upcat_tables(int32_t H, int32_t W, const int32_t *hk, const int32_t *wk, void *tables, size_t tables_bytes, ts_stream_t stream);
+int ts_fid_upcat_rows_forward(const void *x, const void *x1, const void *xk0, const void *xk1, const void *xk2, const void *tables,
+                              int32_t T, int32_t H, int32_t W, const int32_t *hk, const int32_t *wk, int32_t Ca, int32_t Cb, int32_t Cl,
+                              int32_t half, void *cat, void *res0, void *res1, void *res2, ts_stream_t stream);
+int ts_fid_upcat_rows_backward(const void *grad_cat, const void *grad_res0, const void *grad_res1, const void *grad_res2,
+                               const void *tables, int32_t T, int32_t H, int32_t W, const int32_t *hk, const int32_t *wk, int32_t Ca,
+                               int32_t Cb, int32_t Cl, int32_t half, void *grad_x, void *grad_x1, void *grad_xk0, void *grad_xk1,
+                               void *grad_xk2, ts_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

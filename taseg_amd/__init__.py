@@ -26,6 +26,13 @@ def install_as_dropin():
     from .pcseg.model.segmentor.range.salsanext import model as sn_model
     from .pcseg.model.segmentor.range.salsanext.model import semantic as sn_semantic
     from .pcseg.model.segmentor.range.salsanext.model.semantic import salsanext as sn_file
+    from .pcseg.model.segmentor.range import cenet, fidnet
+    from .pcseg.model.segmentor.range.cenet import model as ce_model
+    from .pcseg.model.segmentor.range.cenet.model import semantic as ce_semantic
+    from .pcseg.model.segmentor.range.cenet.model.semantic import cenet as ce_file
+    from .pcseg.model.segmentor.range.fidnet import model as fid_model
+    from .pcseg.model.segmentor.range.fidnet.model import semantic as fid_semantic
+    from .pcseg.model.segmentor.range.fidnet.model.semantic import fidnet as fid_file
     names = {"torchsparse": ts, "torchsparse.nn": ts.nn, "torchsparse.nn.functional": ts.nn.functional,
              "torchsparse.nn.utils": ts.nn.utils, "torchsparse.utils": ts.utils,
              "torchsparse.utils.quantize": ts.utils.quantize, "torchsparse.utils.collate": ts.utils.collate,
@@ -38,7 +45,14 @@ def install_as_dropin():
              "pcseg.model.segmentor.range": range_view, "pcseg.model.segmentor.range.utils": range_utils,
              "pcseg.model.segmentor.range.salsanext": sn, "pcseg.model.segmentor.range.salsanext.model": sn_model,
              "pcseg.model.segmentor.range.salsanext.model.semantic": sn_semantic,
-             "pcseg.model.segmentor.range.salsanext.model.semantic.salsanext": sn_file}
+             "pcseg.model.segmentor.range.salsanext.model.semantic.salsanext": sn_file,
+             # (FIDNet and CENet, the same way)
+             "pcseg.model.segmentor.range.fidnet": fidnet, "pcseg.model.segmentor.range.fidnet.model": fid_model,
+             "pcseg.model.segmentor.range.fidnet.model.semantic": fid_semantic,
+             "pcseg.model.segmentor.range.fidnet.model.semantic.fidnet": fid_file,
+             "pcseg.model.segmentor.range.cenet": cenet, "pcseg.model.segmentor.range.cenet.model": ce_model,
+             "pcseg.model.segmentor.range.cenet.model.semantic": ce_semantic,
+             "pcseg.model.segmentor.range.cenet.model.semantic.cenet": ce_file}
     for name, mod in names.items():
         sys.modules.setdefault(name, mod)
     return names

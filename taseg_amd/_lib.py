@@ -247,6 +247,16 @@ SIGNATURES = {
     "ts_cylinder_cells": (_i32, [_vp, _i64, _i32, _vp, _c.POINTER(_c.c_double), _vp, _vp, _vp, _vp, _vp]),
     "ts_cylinder_voxels_workspace_bytes": (_sz, [_i64, _i32]),
     "ts_cylinder_voxels": (_i32, [_vp, _vp, _i64, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "ts_bn_leaky_act_train_forward": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _c.c_float, _c.c_float, _c.c_float, _i32,
+                                             _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "ts_bn_leaky_act_train_backward": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _c.c_float, _i32, _vp, _vp, _vp, _vp, _vp, _sz,
+                                              _vp]),
+    "ts_fid_upcat_tables_bytes": (_sz, [_i32, _i32]),
+    "ts_fid_upcat_tables": (_i32, [_i32, _i32, _c.POINTER(_i32), _c.POINTER(_i32), _vp, _sz, _vp]),
+    "ts_fid_upcat_rows_forward": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _c.POINTER(_i32), _c.POINTER(_i32), _i32, _i32,
+                                         _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "ts_fid_upcat_rows_backward": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _c.POINTER(_i32), _c.POINTER(_i32), _i32, _i32,
+                                          _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 

@@ -7,6 +7,8 @@ binds unchanged.  Section 2 exposes the fused rulebook / convolution entry point
 MI355X design adds.  Tensors must be contiguous ROCm tensors; outputs are allocated with
 torch (memory + stream plumbing only).
 """
+import ctypes
+
 import torch
 
 from . import _lib as L
@@ -25,6 +27,8 @@ __all__ = [
     "voxelize_max_forward", "voxelize_max_backward", "sigmoid3_gate_forward", "sigmoid3_gate_backward",
     "point_groups", "voxelize_mean_piece_rows", "voxelize_mean_forward", "voxelize_mean_backward", "point_tail_forward",
     "range_plan", "range_point_tail_forward", "range_inputs",
+    "fid_upcat_rows_takes", "fid_upcat_tables", "fid_upcat_rows_forward", "fid_upcat_rows_backward", "bn_leaky_act_train_forward",
+    "bn_leaky_act_train_backward",
 ]
 
 
@@ -971,6 +975,116 @@ def shuffle_cat_rows_backward(grad_cat, channels, scale=None):
     L.check(L.load().ts_shuffle_cat_rows_backward(L.ptr(grad_cat), L.ptr(scale), t, h2 // 2, w2 // 2, c, cs, int(grad_cat.dtype == torch.float16),
                                                   L.ptr(gx), L.ptr(gs), L.stream()), "ts_shuffle_cat_rows_backward")
     return gx, gs
+
+
+def _dense_rows(t):
+    """is this map's memory exactly [T, H, W, C]?  (size-1 axes carry no stride)"""
+    return t.dim() == 4 and t.permute(0, 2, 3, 1).is_contiguous()
+
+
+def fid_upcat_rows_takes(x, x1, coarse):
+    """whether ts_fid_upcat_rows_* takes these five maps: device float32 / float16 of one dtype, rows [T, H, W, C] in memory, every
+    channel count a multiple of the 16-byte piece and <= 1024, the three coarse maps of one channel count and no larger than x"""
+    maps = (x, x1, *coarse)
+    if len(coarse) != 3 or any(m.dim() != 4 or not m.is_cuda or m.dtype != x.dtype or m.shape[0] != x.shape[0] for m in maps):
+        return False
+    if x.dtype not in (torch.float16, torch.float32) or tuple(x1.shape[2:]) != tuple(x.shape[2:]) or x.shape[0] == 0:
+        return False
+    ve = 8 if x.dtype == torch.float16 else 4
+    if any(m.shape[1] % ve or m.shape[1] > 1024 or not _dense_rows(m) or m.data_ptr() % 16 for m in maps):
+        return False
+    return all(m.shape[1] == coarse[0].shape[1] and 1 <= m.shape[2] <= x.shape[2] and 1 <= m.shape[3] <= x.shape[3] for m in coarse)
+
+
+def _fid_sizes(coarse_hw):
+    arr = ctypes.c_int32 * 3
+    return arr(*(int(h) for h, _ in coarse_hw)), arr(*(int(w) for _, w in coarse_hw))
+
+
+def fid_upcat_tables(height, width, coarse_hw, device):
+    """the index / lambda / range tables of one decoder shape (ts_fid_upcat_tables): what the forward and its adjoint both read"""
+    lib = L.load()
+    nbytes = lib.ts_fid_upcat_tables_bytes(int(height), int(width))
+    tables = torch.empty(nbytes // 4, dtype=torch.int32, device=device)
+    hk, wk = _fid_sizes(coarse_hw)
+    L.check(lib.ts_fid_upcat_tables(int(height), int(width), hk, wk, L.ptr(tables), nbytes, L.stream()), "ts_fid_upcat_tables")
+    return tables
+
+
+def fid_upcat_rows_forward(x, x1, coarse, levels=False, tables=None):
+    """cat [T, Ca + Cb + 3 Cl, H, W] = concat(x, x1, the three coarse maps interpolated to H x W, bilinear, align_corners) in one pass,
+    channels-last in and out (csrc/fid.hip) -> (cat, (res_2, res_3, res_4) or None, tables)"""
+    L.require_device(x, x1, *coarse)
+    if not fid_upcat_rows_takes(x, x1, coarse):
+        raise ValueError("fid_upcat_rows_forward: unsupported maps " + ", ".join(f"{tuple(m.shape)} {m.dtype}" for m in (x, x1, *coarse)))
+    t, ca, h, w = x.shape
+    cb, cl = x1.shape[1], coarse[0].shape[1]
+    sizes = [tuple(m.shape[2:]) for m in coarse]
+    if tables is None:
+        tables = fid_upcat_tables(h, w, sizes, x.device)
+    hk, wk = _fid_sizes(sizes)
+    cat = torch.empty((t, h, w, ca + cb + 3 * cl), dtype=x.dtype, device=x.device).permute(0, 3, 1, 2)
+    res = [torch.empty((t, h, w, cl), dtype=x.dtype, device=x.device).permute(0, 3, 1, 2) for _ in range(3)] if levels else [None] * 3
+    L.check(L.load().ts_fid_upcat_rows_forward(L.ptr(x), L.ptr(x1), L.ptr(coarse[0]), L.ptr(coarse[1]), L.ptr(coarse[2]), L.ptr(tables), t, h,
+                                               w, hk, wk, ca, cb, cl, int(x.dtype == torch.float16), L.ptr(cat), L.ptr(res[0]),
+                                               L.ptr(res[1]), L.ptr(res[2]), L.stream()), "ts_fid_upcat_rows_forward")
+    return cat, (tuple(res) if levels else None), tables
+
+
+def fid_upcat_rows_backward(grad_cat, channels, coarse_hw, tables, grad_res=None):
+    """the adjoint of fid_upcat_rows_forward: (grad_x, grad_x1, [grad_x2, grad_x3, grad_x4]) from grad_cat [T, Ca + Cb + 3 Cl, H, W] and
+    the optional gradients of the three level maps; channels = (Ca, Cb, Cl); a gather in a fixed order (no atomics)"""
+    grad_res = list(grad_res) if grad_res is not None else [None] * 3
+    L.require_device(grad_cat, tables, *grad_res)
+    ca, cb, cl = (int(c) for c in channels)
+    t, cc, h, w = grad_cat.shape
+    ve = 8 if grad_cat.dtype == torch.float16 else 4
+    if (cc != ca + cb + 3 * cl or grad_cat.dtype not in (torch.float16, torch.float32) or not _dense_rows(grad_cat)
+            or any(g is not None and (g.dtype != grad_cat.dtype or tuple(g.shape) != (t, cl, h, w) or not _dense_rows(g)) for g in grad_res)
+            or any(c % ve or c > 1024 for c in (ca, cb, cl))):
+        raise ValueError(f"fid_upcat_rows_backward: unsupported gradient {tuple(grad_cat.shape)} {grad_cat.dtype} for channels {channels}")
+    new = lambda c, hh, ww: torch.empty((t, hh, ww, c), dtype=grad_cat.dtype, device=grad_cat.device).permute(0, 3, 1, 2)  # noqa: E731
+    gx, gx1 = new(ca, h, w), new(cb, h, w)
+    gk = [new(cl, hh, ww) for hh, ww in coarse_hw]
+    hk, wk = _fid_sizes(coarse_hw)
+    L.check(L.load().ts_fid_upcat_rows_backward(L.ptr(grad_cat), L.ptr(grad_res[0]), L.ptr(grad_res[1]), L.ptr(grad_res[2]), L.ptr(tables), t,
+                                                h, w, hk, wk, ca, cb, cl, int(grad_cat.dtype == torch.float16), L.ptr(gx), L.ptr(gx1),
+                                                L.ptr(gk[0]), L.ptr(gk[1]), L.ptr(gk[2]), L.stream()), "ts_fid_upcat_rows_backward")
+    return gx, gx1, gk
+
+
+def bn_leaky_act_train_forward(x, weight, bias, running_mean, running_var, nbt, eps, momentum, slope, residual=None):
+    """LeakyReLU_slope(BatchNorm_train(x) (+ residual)) on rows [N, C] (float32 / float16, contiguous) in one call (csrc/bn.hip, the
+    ts_bn_act_train_* family with the activation switched) -> (out, mask, stats [2, C] = mean, invstd); the running buffers and
+    num_batches_tracked (may be None) are updated in place"""
+    L.require_device(x, weight, bias, running_mean, running_var, nbt, residual)
+    n, c = x.shape
+    lib = L.load()
+    half = x.dtype == torch.float16
+    out = torch.empty_like(x)
+    mask = torch.empty(n * (c // (8 if half else 4)), dtype=torch.uint8, device=x.device)
+    stats = torch.empty((2, c), dtype=torch.float32, device=x.device)
+    ws = L.workspace(lib.ts_bn_train_workspace_bytes(c), x.device)
+    L.check(lib.ts_bn_leaky_act_train_forward(L.ptr(x), L.ptr(residual), L.ptr(weight), L.ptr(bias), L.ptr(running_mean), L.ptr(running_var),
+                                              L.ptr(nbt), n, c, float(eps), float(momentum), float(slope), int(half), L.ptr(stats[0]),
+                                              L.ptr(stats[1]), L.ptr(out), L.ptr(mask), L.ptr(ws), ws.numel(), L.stream()),
+            "ts_bn_leaky_act_train_forward")
+    return out, mask, stats
+
+
+def bn_leaky_act_train_backward(grad_out, mask, x, stats, weight, slope, with_residual=False):
+    """(grad_x, grad_residual or None, grad_weight, grad_bias) of bn_leaky_act_train_forward"""
+    L.require_device(grad_out, mask, x, stats, weight)
+    n, c = x.shape
+    lib = L.load()
+    grad_x = torch.empty_like(x)
+    grad_res = torch.empty_like(x) if with_residual else None
+    gwb = torch.empty((2, c), dtype=torch.float32, device=x.device)
+    ws = L.workspace(lib.ts_bn_train_workspace_bytes(c), x.device)
+    L.check(lib.ts_bn_leaky_act_train_backward(L.ptr(grad_out), L.ptr(mask), L.ptr(x), L.ptr(stats[0]), L.ptr(stats[1]), L.ptr(weight), n, c,
+                                               float(slope), int(x.dtype == torch.float16), L.ptr(grad_x), L.ptr(grad_res), L.ptr(gwb[0]),
+                                               L.ptr(gwb[1]), L.ptr(ws), ws.numel(), L.stream()), "ts_bn_leaky_act_train_backward")
+    return grad_x, grad_res, gwb[0], gwb[1]
 
 
 _conv3x3_takes = {}

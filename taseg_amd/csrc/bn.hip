@@ -10,6 +10,7 @@
 //     (ts_bn_finalize), the fp32 backward from double sums (bn_act_bwd_kernel, ts_bn_act_backward);
 //   * one host driver per operation on <T, VE> (bn_train_forward, bn_train_backward, bn_sync_stats,
 //     bn_sync_backward_reduce, bn_apply_forward, bn_apply_backward_coef); the extern "C" entry points pick an instantiation;
+//   * BatchNorm -> (+ residual) -> LeakyReLU of the range-view trunks (ts_bn_leaky_act_train_*): the same kernels with ACT = 1;
 //   * LeakyReLU -> BatchNorm2d of the dense 2-D branch (lbn_*), which shares the slice rule, the LDS fold and the finishes.
 // Accumulation: float per lane over one slice (<= ~350 rows), double across slices.
 #include <stdlib.h>
@@ -78,12 +79,15 @@ __device__ __forceinline__ BnVec<float, VE> bn_load_ch(const float *__restrict__
 //             gx = (g - sums[0]/N - (x - mean) invstd^2 sums[1]/N) invstd w ,  gres = g   (ts_bn_act_backward)
 // Activations, residual and gradients are T in HBM; every reduction / normalisation runs in fp32 (statistics, affine parameters
 // and parameter gradients stay fp32, as under torch.autocast).
-template <typename T, int VE>
+// ACT 0: ReLU when `relu` is set (the sparse blocks).  ACT 1: LeakyReLU(slope) behind the sum (the range-view trunks' BasicBlock,
+// ts_bn_leaky_act_train_*, which pass relu = 1 for the mask): the mask bit is still the sign of the stored value, and an element that is stored as 0
+// has taken the slope branch, as leaky_relu_backward decides it.
+template <typename T, int VE, int ACT = 0>
 __global__ __launch_bounds__(256) void bn_act_fwd_kernel(const BnVec<T, VE> *__restrict__ X, const BnVec<T, VE> *__restrict__ RES,
                                                          const float *__restrict__ mean, const float *__restrict__ invstd,
                                                          const float *__restrict__ w, const float *__restrict__ b, int64_t total,
                                                          int cq, int relu, BnVec<T, VE> *__restrict__ OUT,
-                                                         unsigned char *__restrict__ MASK) {
+                                                         unsigned char *__restrict__ MASK, float slope) {
   using V = BnVec<T, VE>;
   int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t step = (int64_t)gridDim.x * blockDim.x;
@@ -100,7 +104,8 @@ __global__ __launch_bounds__(256) void bn_act_fwd_kernel(const BnVec<T, VE> *__r
     for (int i = 0; i < VE; ++i) {
       float v = ((float)x.x[i] - m.x[i]) * s.x[i] * ww.x[i] + bb.x[i];
       if (RES) v += (float)r.x[i];
-      if (relu) v = fmaxf(v, 0.f);
+      if (ACT == 1) v = v > 0.f ? v : v * slope;
+      else if (relu) v = fmaxf(v, 0.f);
       const T h = (T)v;
       // the mask bit is the sign of the STORED value (what torch's ReLU backward looks at): a positive fp32 value below half's
       // smallest subnormal rounds to zero and passes no gradient
@@ -204,15 +209,16 @@ constexpr int bn_row_unroll = sizeof(T) == 4 ? 4 : 2;
 // waves per SIMD the compiler plans bn_partial_kernel for.  Half rows under the mask: 5 (94 VGPRs) - planning for 7 it fits 71
 // VGPRs by waiting for each row's loads before it issues the next one's, 0.0285 against 0.0259 ms at 178k x 32
 template <typename T, int MODE>
-constexpr int bn_partial_waves = sizeof(T) == 2 && MODE == 2 ? 5 : 8;
+constexpr int bn_partial_waves = sizeof(T) == 2 && MODE >= 2 ? 5 : 8;
 
-// MODE 0: (x, x^2)   1: (dy, dy (x - mean))   2: same with the ReLU mask applied to dy
+// MODE 0: (x, x^2)   1: (dy, dy (x - mean))   2: same with the ReLU mask applied to dy   3: same with the LeakyReLU mask (a cleared
+// bit scales dy by `slope` instead of dropping it)
 // The second sum takes every product by a fused multiply-add, written out so that the rounding does not hang on what the compiler
 // contracts (left to it, the half form once kept two channels of eight on a multiply and an add).
 template <typename T, int VE, int MODE>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, bn_partial_waves<T, MODE>)))
 void bn_partial_kernel(const T *__restrict__ X, const T *__restrict__ DY, const unsigned char *__restrict__ MASK,
-                       const float *__restrict__ mean, int64_t n, int c, int rows_per_wg, float *__restrict__ part) {
+                       const float *__restrict__ mean, int64_t n, int c, int rows_per_wg, float *__restrict__ part, float slope) {
   using V = BnVec<T, VE>;
   __shared__ float red[2][256 * VE];
   const int cq = c / VE, rpp = 256 / cq;
@@ -236,11 +242,11 @@ void bn_partial_kernel(const T *__restrict__ X, const T *__restrict__ DY, const 
         }
       } else {
         const V &d = *(const V *)(DY + r * c + VE * tx);
-        const unsigned mk = MODE == 2 ? MASK[r * cq + tx] : 0xFFu;
+        const unsigned mk = MODE >= 2 ? MASK[r * cq + tx] : 0xFFu;
 #pragma unroll
         for (int i = 0; i < VE; ++i) {
           const float dy = (float)d.x[i];                       // read before the test: every lane loads its whole chunk
-          const float dv = ((mk >> i) & 1) ? dy : 0.f;
+          const float dv = ((mk >> i) & 1) ? dy : (MODE == 3 ? dy * slope : 0.f);
           s0.x[i] += dv;
           s1.x[i] = __builtin_fmaf(dv, (float)x.x[i] - mu.x[i], s1.x[i]);
         }
@@ -327,13 +333,14 @@ __global__ __launch_bounds__(256) void bn_bwd_finish_kernel(const float *__restr
   if (grad_weight) grad_weight[ch] = (float)s1 * is;
 }
 
-template <typename T, int VE>
+template <typename T, int VE, int ACT = 0>
 __global__ __launch_bounds__(256) void bn_act_bwd_coef_kernel(const BnVec<T, VE> *__restrict__ GOUT,
                                                               const unsigned char *__restrict__ MASK,
                                                               const BnVec<T, VE> *__restrict__ X, const float *__restrict__ mean,
                                                               const float *__restrict__ invstd, const float *__restrict__ w,
                                                               const float *__restrict__ coef, int64_t total, int c,
-                                                              BnVec<T, VE> *__restrict__ GX, BnVec<T, VE> *__restrict__ GRES) {
+                                                              BnVec<T, VE> *__restrict__ GX, BnVec<T, VE> *__restrict__ GRES,
+                                                              float slope) {
   using V = BnVec<T, VE>;
   const int cq = c / VE;
   int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -347,7 +354,7 @@ __global__ __launch_bounds__(256) void bn_act_bwd_coef_kernel(const BnVec<T, VE>
     V g, gx;
 #pragma unroll
     for (int i = 0; i < VE; ++i) {
-      const float gv = ((mk >> i) & 1) ? (float)gin.x[i] : 0.f;
+      const float gv = ((mk >> i) & 1) ? (float)gin.x[i] : (ACT == 1 ? (float)gin.x[i] * slope : 0.f);
       g.x[i] = (T)gv;
       gx.x[i] = (T)((gv - c0.x[i] - ((float)x.x[i] - m.x[i]) * c1.x[i]) * s.x[i] * ww.x[i]);
     }
@@ -414,45 +421,48 @@ static int bn_check_size(const char *what, int64_t n, int32_t c) {
   return TS_OK;
 }
 
-// the sliced sums of one matrix into part [slices][2][C]; MODE from the arguments: no dy = 0, dy = 1, dy and mask = 2
-template <typename T, int VE>
+// the sliced sums of one matrix into part [slices][2][C]; MODE from the arguments: no dy = 0, dy = 1, dy and mask = 2 (ACT 0) or 3
+// (ACT 1, whose callers always hold a mask)
+template <typename T, int VE, int ACT = 0>
 static int bn_launch_partial(const void *x, const void *dy, const uint8_t *mask, const float *mean, int64_t n, int c, float *part,
-                             hipStream_t stream) {
+                             hipStream_t stream, float slope = 0.f) {
   const int rows = bn_rows_per_slice<VE>(n, c);
   const int slices = (int)ts_cdiv(n, rows);
   if (!dy)
-    bn_partial_kernel<T, VE, 0><<<slices, 256, 0, stream>>>((const T *)x, nullptr, nullptr, nullptr, n, c, rows, part);
+    bn_partial_kernel<T, VE, 0><<<slices, 256, 0, stream>>>((const T *)x, nullptr, nullptr, nullptr, n, c, rows, part, 0.f);
   else if (mask)
-    bn_partial_kernel<T, VE, 2><<<slices, 256, 0, stream>>>((const T *)x, (const T *)dy, mask, mean, n, c, rows, part);
+    bn_partial_kernel<T, VE, ACT == 1 ? 3 : 2><<<slices, 256, 0, stream>>>((const T *)x, (const T *)dy, mask, mean, n, c, rows, part,
+                                                                           slope);
   else
-    bn_partial_kernel<T, VE, 1><<<slices, 256, 0, stream>>>((const T *)x, (const T *)dy, nullptr, mean, n, c, rows, part);
+    bn_partial_kernel<T, VE, 1><<<slices, 256, 0, stream>>>((const T *)x, (const T *)dy, nullptr, mean, n, c, rows, part, 0.f);
   return slices;
 }
 
-template <typename T, int VE>
+template <typename T, int VE, int ACT = 0>
 static void bn_launch_act_fwd(const void *x, const void *residual, const float *mean, const float *invstd, const float *weight,
-                              const float *bias, int64_t n, int c, int relu, void *out, uint8_t *mask, hipStream_t stream) {
+                              const float *bias, int64_t n, int c, int relu, void *out, uint8_t *mask, hipStream_t stream,
+                              float slope = 0.f) {
   using V = BnVec<T, VE>;
   const int64_t total = n * (c / VE);
-  bn_act_fwd_kernel<T, VE><<<bn_grid(total), 256, 0, stream>>>((const V *)x, (const V *)residual, mean, invstd, weight, bias, total,
-                                                               c / VE, relu, (V *)out, mask);
+  bn_act_fwd_kernel<T, VE, ACT><<<bn_grid(total), 256, 0, stream>>>((const V *)x, (const V *)residual, mean, invstd, weight, bias,
+                                                                    total, c / VE, relu, (V *)out, mask, slope);
 }
 
-template <typename T, int VE>
+template <typename T, int VE, int ACT = 0>
 static void bn_launch_act_bwd_coef(const void *grad_out, const uint8_t *mask, const void *x, const float *mean, const float *invstd,
                                    const float *weight, const float *coef, int64_t n, int c, void *grad_x, void *grad_residual,
-                                   hipStream_t stream) {
+                                   hipStream_t stream, float slope = 0.f) {
   using V = BnVec<T, VE>;
   const int64_t total = n * (c / VE);
-  bn_act_bwd_coef_kernel<T, VE><<<bn_grid(total), 256, 0, stream>>>((const V *)grad_out, mask, (const V *)x, mean, invstd, weight,
-                                                                    coef, total, c, (V *)grad_x, (V *)grad_residual);
+  bn_act_bwd_coef_kernel<T, VE, ACT><<<bn_grid(total), 256, 0, stream>>>((const V *)grad_out, mask, (const V *)x, mean, invstd, weight,
+                                                                         coef, total, c, (V *)grad_x, (V *)grad_residual, slope);
 }
 
-template <typename T, int VE>
+template <typename T, int VE, int ACT = 0>
 static int bn_train_forward(const char *what, const void *x, const void *residual, const float *weight, const float *bias,
                             float *running_mean, float *running_var, int64_t *num_batches_tracked, int64_t n, int32_t c, float eps,
                             float momentum, int32_t relu, float *mean, float *invstd, void *out, uint8_t *mask, void *ws,
-                            size_t ws_bytes, hipStream_t stream) {
+                            size_t ws_bytes, hipStream_t stream, float slope = 0.f) {
   const int rc = bn_check_size<VE>(what, n, c);
   if (rc != TS_OK) return rc;
   TS_REQUIRE(x && weight && bias && mean && invstd && out && ws, TS_ERR_INVALID_ARGUMENT, "%s: null pointer", what);
@@ -461,24 +471,24 @@ static int bn_train_forward(const char *what, const void *x, const void *residua
                  bn_ch_aligned<VE>(bias) && (!residual || bn_aligned(residual)) && bn_aligned(ws),
              TS_ERR_INVALID_ARGUMENT, "%s: pointers must be 16-byte aligned", what);
   float *part = (float *)ws;
-  const int ablate = sizeof(T) == 4 ? bn_debug_ablate() : 0;   // diagnostic (wrong results, timing only), see above
+  const int ablate = sizeof(T) == 4 && ACT == 0 ? bn_debug_ablate() : 0;   // diagnostic (wrong results, timing only), see above
   int slices = (int)ts_cdiv(n, bn_rows_per_slice<VE>(n, c));
   if (!(ablate & 1)) slices = bn_launch_partial<T, VE>(x, nullptr, nullptr, nullptr, n, c, part, stream);
   if (ablate & 4) bn_launch_partial<T, VE>(x, nullptr, nullptr, nullptr, n, c, part, stream);   // the pass once more
   bn_fwd_finish_kernel<<<(unsigned)ts_cdiv(c, BN_FIN_CH), 256, 0, stream>>>(part, slices, (double)n, c, eps, momentum, running_mean,
                                                                            running_var, mean, invstd, num_batches_tracked);
   if (!((ablate & 2) && !residual && relu))
-    bn_launch_act_fwd<T, VE>(x, residual, mean, invstd, weight, bias, n, c, relu, out, mask, stream);
+    bn_launch_act_fwd<T, VE, ACT>(x, residual, mean, invstd, weight, bias, n, c, relu, out, mask, stream, slope);
   if ((ablate & 8) && !residual && relu)          // the same pass once more (same results)
     bn_launch_act_fwd<T, VE>(x, residual, mean, invstd, weight, bias, n, c, relu, out, mask, stream);
   TS_CHECK_LAUNCH(what);
   return TS_OK;
 }
 
-template <typename T, int VE>
+template <typename T, int VE, int ACT = 0>
 static int bn_train_backward(const char *what, const void *grad_out, const uint8_t *mask, const void *x, const float *mean,
                              const float *invstd, const float *weight, int64_t n, int32_t c, void *grad_x, void *grad_residual,
-                             float *grad_weight, float *grad_bias, void *ws, size_t ws_bytes, hipStream_t stream) {
+                             float *grad_weight, float *grad_bias, void *ws, size_t ws_bytes, hipStream_t stream, float slope = 0.f) {
   const int rc = bn_check_size<VE>(what, n, c);
   if (rc != TS_OK) return rc;
   TS_REQUIRE(grad_out && x && mean && invstd && weight && grad_x && ws, TS_ERR_INVALID_ARGUMENT, "%s: null pointer", what);
@@ -488,10 +498,10 @@ static int bn_train_backward(const char *what, const void *grad_out, const uint8
              TS_ERR_INVALID_ARGUMENT, "%s: pointers must be 16-byte aligned", what);
   float *part = (float *)ws;
   float *coef = part + (size_t)BN_MAX_SLICES * 2 * c;
-  const int slices = bn_launch_partial<T, VE>(x, grad_out, mask, mean, n, c, part, stream);
+  const int slices = bn_launch_partial<T, VE, ACT>(x, grad_out, mask, mean, n, c, part, stream, slope);
   bn_bwd_finish_kernel<<<(unsigned)ts_cdiv(c, BN_FIN_CH), 256, 0, stream>>>(part, slices, (double)n, c, invstd, coef, grad_weight,
                                                                            grad_bias);
-  bn_launch_act_bwd_coef<T, VE>(grad_out, mask, x, mean, invstd, weight, coef, n, c, grad_x, grad_residual, stream);
+  bn_launch_act_bwd_coef<T, VE, ACT>(grad_out, mask, x, mean, invstd, weight, coef, n, c, grad_x, grad_residual, stream, slope);
   TS_CHECK_LAUNCH(what);
   return TS_OK;
 }
@@ -674,6 +684,39 @@ extern "C" int ts_bn_act_backward_f16(const void *grad_out, const uint8_t *mask,
                                       void *grad_residual, void *ws, size_t ws_bytes, ts_stream_t stream) {
   return bn_apply_backward_coef<_Float16, 8>("ts_bn_act_backward_f16", grad_out, mask, x, mean, invstd, weight, sums, total_dev,
                                              total_host, n, c, grad_x, grad_residual, ws, ws_bytes, (hipStream_t)stream);
+}
+
+// BatchNorm (training) -> (+ residual) -> LeakyReLU(slope): the ts_bn_act_train_* chain on the ACT = 1 instantiations (the range-view
+// trunks' conv -> BN -> LeakyReLU and conv -> BN -> += identity -> LeakyReLU, R/pcseg/model/segmentor/range/fidnet/model/semantic/
+// fidnet.py:114-128).  The mask is required: the backward has nothing else to tell the two branches apart.
+extern "C" int ts_bn_leaky_act_train_forward(const void *x, const void *residual, const float *weight, const float *bias,
+                                             float *running_mean, float *running_var, int64_t *num_batches_tracked, int64_t n, int32_t c,
+                                             float eps, float momentum, float slope, int32_t half, float *mean, float *invstd, void *out,
+                                             uint8_t *mask, void *ws, size_t ws_bytes, ts_stream_t stream) {
+  const char *what = "ts_bn_leaky_act_train_forward";
+  const int rc = half ? bn_check_size<8>(what, n, c) : bn_check_size<4>(what, n, c);
+  if (rc != TS_OK) return rc;
+  TS_REQUIRE(c <= 1024, TS_ERR_UNSUPPORTED, "%s: C <= 1024", what);
+  TS_REQUIRE(mask, TS_ERR_INVALID_ARGUMENT, "%s: null mask", what);
+  return half ? bn_train_forward<_Float16, 8, 1>(what, x, residual, weight, bias, running_mean, running_var, num_batches_tracked, n, c,
+                                                 eps, momentum, 1, mean, invstd, out, mask, ws, ws_bytes, (hipStream_t)stream, slope)
+              : bn_train_forward<float, 4, 1>(what, x, residual, weight, bias, running_mean, running_var, num_batches_tracked, n, c, eps,
+                                              momentum, 1, mean, invstd, out, mask, ws, ws_bytes, (hipStream_t)stream, slope);
+}
+
+extern "C" int ts_bn_leaky_act_train_backward(const void *grad_out, const uint8_t *mask, const void *x, const float *mean,
+                                              const float *invstd, const float *weight, int64_t n, int32_t c, float slope, int32_t half,
+                                              void *grad_x, void *grad_residual, float *grad_weight, float *grad_bias, void *ws,
+                                              size_t ws_bytes, ts_stream_t stream) {
+  const char *what = "ts_bn_leaky_act_train_backward";
+  const int rc = half ? bn_check_size<8>(what, n, c) : bn_check_size<4>(what, n, c);
+  if (rc != TS_OK) return rc;
+  TS_REQUIRE(c <= 1024, TS_ERR_UNSUPPORTED, "%s: C <= 1024", what);
+  TS_REQUIRE(mask, TS_ERR_INVALID_ARGUMENT, "%s: null mask", what);
+  return half ? bn_train_backward<_Float16, 8, 1>(what, grad_out, mask, x, mean, invstd, weight, n, c, grad_x, grad_residual, grad_weight,
+                                                  grad_bias, ws, ws_bytes, (hipStream_t)stream, slope)
+              : bn_train_backward<float, 4, 1>(what, grad_out, mask, x, mean, invstd, weight, n, c, grad_x, grad_residual, grad_weight,
+                                               grad_bias, ws, ws_bytes, (hipStream_t)stream, slope);
 }
 
 // ------------------------------------------------------------------------------------------------------

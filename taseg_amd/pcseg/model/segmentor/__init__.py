@@ -6,7 +6,8 @@ SPVCNN is built too (`fusion/spvcnn/`), but is not in this registry: it is const
 `from pcseg.model.segmentor.fusion.spvcnn import SPVCNN; SPVCNN(model_cfgs, num_class)`, and `build_segmentor(NAME="SPVCNN")` keeps
 raising NotImplementedError - two existing tests pin that and `_OUT_OF_SCOPE` as they stand (tests/test_spvcnn_host.py says which).
 RPVNet (`fusion/rpvnet/`) is built and reached the same way, for the same reason, and so is SalsaNext
-(`range/salsanext/model/semantic/salsanext.py`, with the range-view family's losses and kNN step in `range/utils.py`)."""
+(`range/salsanext/model/semantic/salsanext.py`, with the range-view family's losses and kNN step in `range/utils.py`), FIDNet
+(`range/fidnet/model/semantic/fidnet.py`) and CENet (`range/cenet/model/semantic/cenet.py`)."""
 from .base_segmentors import BaseSegmentor
 from .voxel.cylinder3d.cylinder_ts import Cylinder_TS
 from .voxel.minkunet.minkunet import MinkUNet

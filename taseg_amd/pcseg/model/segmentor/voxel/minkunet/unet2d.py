@@ -209,6 +209,58 @@ def _act_bn(act, bn, x, residual=None):
     return y if residual is None else residual + y
 
 
+class _BatchNormLeakyRows(Function):
+    """LeakyReLU(BatchNorm2d_train(x) (+ residual)) of a channels-last map as ONE node on the library's row kernels (csrc/bn.hip,
+    ts_bn_leaky_act_train_*: the sparse blocks' BatchNorm family with the activation switched): x and one sign bit per output element
+    are kept for the backward pass; the residual's gradient is the masked gradient, written by the same pass"""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, running_mean, running_var, nbt, eps, momentum, slope, residual=None):
+        t, c, h, w = x.shape
+        rows = lambda m: m.permute(0, 2, 3, 1).reshape(t * h * w, c)  # noqa: E731  (views: the memory is [T, H, W, C])
+        out, mask, stats = B.bn_leaky_act_train_forward(rows(x), weight, bias, running_mean, running_var, nbt, eps, momentum, slope,
+                                                        None if residual is None else rows(residual))
+        for buf in (running_mean, running_var, nbt):      # written through raw pointers: move their version counters
+            if buf is not None:
+                torch.autograd.graph.increment_version(buf)
+        ctx.save_for_backward(x, weight, stats, mask)
+        ctx.slope, ctx.with_residual = float(slope), residual is not None
+        return out.view(t, h, w, c).permute(0, 3, 1, 2)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        x, weight, stats, mask = ctx.saved_tensors
+        t, c, h, w = x.shape
+        rows = lambda m: m.permute(0, 2, 3, 1).reshape(t * h * w, c)  # noqa: E731
+        grad_out = grad_out.to(x.dtype).contiguous(memory_format=torch.channels_last)
+        gx, gres, gw, gb = B.bn_leaky_act_train_backward(rows(grad_out), mask, rows(x), stats, weight, ctx.slope, ctx.with_residual)
+        back = lambda m: m.view(t, h, w, c).permute(0, 3, 1, 2)  # noqa: E731
+        return (back(gx), gw.to(weight.dtype), gb.to(weight.dtype), None, None, None, None, None, None,
+                back(gres) if ctx.with_residual else None)
+
+
+def _bn_act(bn, act, x, residual=None):
+    """act(bn(x)) of a layer, or act(bn(x) + residual) of a BasicBlock's ending (fidnet.py:117-128 `out = self.bn2(out); out +=
+    identity; out = self.relu(out)`).  The admission test is `_act_bn`'s: training-mode BatchNorm2d (or a SyncBatchNorm with local
+    statistics) in front of a LeakyReLU on a channels-last device map goes through ONE fused node; anything else - evaluation mode,
+    other layouts / dtypes, the CPU, modules with hooks, options.image_fused_bn off - is the modules themselves."""
+    c = x.shape[1] if x.dim() == 4 else 0
+    if (options.image_fused_bn and bn.training and x.is_cuda and x.dim() == 4 and isinstance(act, nn.LeakyReLU) and _local_bn2d(bn)
+            and bn.affine and bn.track_running_stats and bn.momentum is not None and x.dtype in (torch.float32, torch.float16)
+            and c % (8 if x.dtype == torch.float16 else 4) == 0 and c <= 1024 and bn.weight.dtype == torch.float32
+            and not x.is_contiguous() and x.is_contiguous(memory_format=torch.channels_last) and x.numel() > 0
+            and not (act._forward_hooks or act._forward_pre_hooks or act._backward_hooks or bn._forward_hooks or bn._forward_pre_hooks
+                     or bn._backward_hooks)):
+        if residual is None or (residual.shape == x.shape and residual.dtype == x.dtype and not residual.is_contiguous()
+                                and residual.is_contiguous(memory_format=torch.channels_last)):
+            return _BatchNormLeakyRows.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked, bn.eps,
+                                             bn.momentum, act.negative_slope, residual)
+    y = bn(x)
+    if residual is not None:
+        y = y + residual
+    return act(y)
+
+
 class _Conv3x3C32Rows(Function):
     """Conv2d(32, 32, 3, stride 1, padding = dilation) of a channels-last half map on csrc/conv2d_rows.hip: forward, data gradient
     (the weight lives in a wave's registers as MFMA operands) and weight gradient (pixel-major rows through LDS transposing reads,
