@@ -813,6 +813,36 @@ int ts_sgd_apply_segments(float *param, const float *grad, float *momentum_buf, 
                           const float *flags, const TsSgdGroup *groups, int32_t n_groups, float lr, float momentum,
                           float weight_decay, int32_t nesterov, int32_t first_step, ts_stream_t stream);
 
+/* Flat-buffer AdamW step (torch.optim.AdamW: decoupled weight decay, no amsgrad) on the same buckets, slot records,
+ * tile list and flags as ts_sgd_apply_segments.  ts_sgd_grad_stats and ts_sgd_decide come first; of their `state` only
+ * [2] (gradient multiplier gs) and [3] (skip flag) are read.
+ *   ts_adamw_prepare   one thread per slot, arithmetic in double.  Writes nothing when state[3] != 0 and nothing for a
+ *                      skipped slot (`unused` set and, with flags, flags[flag_index] == 0).  Else t = ++step[s] and, from
+ *                      groups[slots[s].group] = (lr, beta1, beta2, eps, weight_decay) - the CURRENT values -, coef[s]:
+ *                        decay = (float)(1 - lr wd)   w1 = (float)(1 - beta1)   b2 = (float)beta2   w2 = (float)(1 - beta2)
+ *                        neg_step_size = (float)(-(lr / (1 - beta1^t)))   bc2_sqrt = (float)sqrt(1 - beta2^t)
+ *                        eps = (float)eps   live = 1 | (wd != 0 ? 2 : 0)
+ *   ts_adamw_apply_segments   per element of a slot that is not skipped, every operation rounded to float on its own:
+ *                        g' = g gs;  p1 = p decay (left out when live bit 1 is clear, as torch leaves out the mul_)
+ *                        d = g' - m;  m' = w1 < 0.5 ? m + w1 d : g' - d (1 - w1)        (ATen's lerp)
+ *                        v' = b2 v + (w2 g') g';  den = sqrtf(v') / bc2_sqrt + eps;  p' = p1 + (neg_step_size m') / den
+ *                      with correctly rounded sqrtf and division.  The padding between slots (zeros in all four
+ *                      buckets) stays zero because eps > 0: the caller must refuse eps <= 0.  A skipped step and a skipped
+ *                      slot keep every bit of p, m, v.  n % 4 == 0, the four buckets 16-byte aligned,
+ *                      n_tiles = ceil(n / TS_SGD_TILE). */
+typedef struct TsAdamwGroup {
+  double lr, beta1, beta2, eps, weight_decay;
+} TsAdamwGroup;
+typedef struct TsAdamwCoef {
+  float decay, w1, b2, w2, neg_step_size, bc2_sqrt, eps;
+  int32_t live;
+} TsAdamwCoef;
+int ts_adamw_prepare(const TsSgdSlot *slots, int32_t n_slots, const float *flags, const float *state,
+                     const TsAdamwGroup *groups, int32_t n_groups, int32_t *step, TsAdamwCoef *coef, ts_stream_t stream);
+int ts_adamw_apply_segments(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, int64_t n,
+                            const float *state, const TsSgdSlot *slots, int32_t n_slots, const int32_t *tile_first,
+                            int64_t n_tiles, const float *flags, const TsAdamwCoef *coef, ts_stream_t stream);
+
 /* Half-storage forms of the SyncBatchNorm halves (ts_bn_sync_stats, ts_bn_act_forward, ts_bn_sync_backward_reduce,
  * ts_bn_act_backward): activations / gradients IEEE half [n, c] (c % 8 == 0), mask one byte per 8 elements, everything
  * else as in the fp32 forms.  ts_bn_act_backward_f16 needs 2 c floats of 16-byte aligned scratch. */

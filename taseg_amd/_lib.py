@@ -145,6 +145,8 @@ SIGNATURES = {
     "ts_sgd_apply": (_i32, [_vp, _vp, _vp, _i64, _vp, _c.c_float, _c.c_float, _c.c_float, _i32, _vp]),
     "ts_sgd_apply_segments": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _i32, _vp, _i64, _vp, _vp, _i32, _c.c_float, _c.c_float,
                                      _c.c_float, _i32, _i32, _vp]),
+    "ts_adamw_prepare": (_i32, [_vp, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp]),
+    "ts_adamw_apply_segments": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _i32, _vp, _i64, _vp, _vp, _vp]),
     "ts_bn_sync_stats_f16": (_i32, [_vp, _i64, _i32, _vp, _vp, _sz, _vp]),
     "ts_bn_act_forward_f16": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp]),
     "ts_bn_sync_backward_reduce_f16": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),

@@ -1,9 +1,10 @@
 """`pcseg.optim` for the hot path: `build_optimizer` / `build_scheduler` with the reference's names and argument lists
-(reference pcseg/optim/__init__.py), on the flat buckets of taseg_amd.optim.FlatSGD.
+(reference pcseg/optim/__init__.py), on the flat buckets of taseg_amd.optim.FlatSGD and FlatAdamW.
 
-`sgd` and `sgd_fc` return a `FlatOptimizer`: a torch.optim.Optimizer whose param_groups are the live hyper-parameters of a FlatSGD, so
-the schedulers (`LambdaLR`, `OneCycleLR`), a trainer's `optimizer.param_groups[0]['lr']` log line and `state_dict()` work as on
-torch.optim.SGD.  Two ways to run it:
+`sgd`, `sgd_fc` and `adamw` return a `FlatOptimizer`: a torch.optim.Optimizer whose param_groups are the live hyper-parameters of a
+FlatSGD / FlatAdamW, so the schedulers (`LambdaLR`, `OneCycleLR` - which cycles `momentum` of the one and `betas[0]` of the other), a
+trainer's `optimizer.param_groups[0]['lr']` log line and `state_dict()` work as on torch.optim.SGD / torch.optim.AdamW.  Two ways to
+run it:
 
     optimizer = build_optimizer(model, cfg.OPTIM)                     # the reference's loop, unchanged (one process)
     scaler.scale(loss).backward(); scaler.unscale_(optimizer); clip_grad_norm_(model.parameters(), 10)
@@ -12,31 +13,43 @@ torch.optim.SGD.  Two ways to run it:
     optimizer = build_optimizer(model, cfg.OPTIM, max_norm=10.0, amp=True)     # clip and loss scale decided on the device
     (loss * optimizer.flat.loss_scale()).backward(); optimizer.step(); scheduler.step()
 
-`adam` / `adamW` are torch's own optimizers (no recipe uses them); `adam_onecycle` (fastai's wrapper) is outside the path and raises.
+`adamw` is the spelling of the four range-view recipes (tools/cfgs/range/*.yaml), with their BETA1 / BETA2 / EPS keys.  The reference's
+build_optimizer knows only `adamW`, raises NotImplementedError on `adamw` and never reads those keys, so the recipes do not start
+there; here they do.  `adam` / `adamW` stay torch's own optimizers, built as the reference builds them; `adam_onecycle` (fastai's
+wrapper) is outside the path and raises.
 """
 import numpy as np
 import torch
 from torch.optim import lr_scheduler as lr_sched
 
-from ...optim import FlatSGD
+from ...optim import FlatAdamW, FlatSGD
 
 __all__ = ["FlatOptimizer", "build_optimizer", "build_scheduler", "linear_warmup_with_cosdecay", "cos_warmup_with_cosdecay",
            "linear_warmup_with_stepdecay", "coswarmup_with_stepdecay"]
 
 
 class FlatOptimizer(torch.optim.Optimizer):
-    """torch.optim.Optimizer face of a FlatSGD (`.flat`).  `param_groups` are FlatSGD's own dictionaries: what a scheduler writes
-    there is what the next step() hands to the kernel.  `state[p]['momentum_buffer']` are views of the momentum buckets."""
+    """torch.optim.Optimizer face of a FlatSGD or a FlatAdamW (`.flat`).  `param_groups` are the flat object's own dictionaries: what
+    a scheduler writes there is what the next step() hands to the kernels.  `defaults` are the flat object's (for AdamW they hold
+    `betas`, which is what lets OneCycleLR(cycle_momentum=True) accept it).  `state[p]` holds views of the state buckets:
+    'momentum_buffer' for SGD; 'exp_avg', 'exp_avg_sq' and 'step' (the slot's int32 counter ON THE DEVICE) for AdamW.
 
-    def __init__(self, model, groups=None, lr=1e-3, momentum=0.0, weight_decay=0.0, nesterov=False, **flat_kwargs):
-        self.flat = FlatSGD(model, lr=lr, momentum=momentum, weight_decay=weight_decay, nesterov=nesterov, groups=groups,
-                            **flat_kwargs)
-        defaults = {"lr": lr, "momentum": momentum, "dampening": 0, "weight_decay": weight_decay, "nesterov": nesterov,
-                    "maximize": False}
-        super().__init__(self.flat.param_groups, defaults)       # (keeps the dictionaries it is given)
+    `kind="adamw"` takes lr / betas / eps / weight_decay, else lr / momentum / weight_decay / nesterov; the other keyword arguments
+    go to the flat class."""
+
+    def __init__(self, model, groups=None, lr=1e-3, momentum=0.0, weight_decay=0.0, nesterov=False, kind="sgd", betas=(0.9, 0.999),
+                 eps=1e-8, **flat_kwargs):
+        if kind == "adamw":
+            self.flat = FlatAdamW(model, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, groups=groups, **flat_kwargs)
+        elif kind == "sgd":
+            self.flat = FlatSGD(model, lr=lr, momentum=momentum, weight_decay=weight_decay, nesterov=nesterov, groups=groups,
+                                **flat_kwargs)
+        else:
+            raise ValueError(f"FlatOptimizer: kind '{kind}'")
+        super().__init__(self.flat.param_groups, dict(self.flat.defaults))       # (keeps the dictionaries it is given)
         self.flat.param_groups = self.param_groups
         for p in self.flat._ordered():
-            self.state[p] = {"momentum_buffer": self.flat._momentum_of[id(p)]}
+            self.state[p] = self.flat.state_of(p)
 
     def step(self, closure=None):
         loss = None
@@ -64,8 +77,9 @@ class FlatOptimizer(torch.optim.Optimizer):
 
 
 def build_optimizer(model, optim_cfg, *, max_norm=0.0, amp=False, **flat_kwargs):
-    """reference build_optimizer(model, optim_cfg); the keyword arguments go to FlatSGD (`process_group=`, `bucket_mb=`, ...).
-    The yaml's NESTEROV key is ignored, as the reference ignores it."""
+    """reference build_optimizer(model, optim_cfg); the keyword arguments go to FlatSGD / FlatAdamW (`process_group=`, `bucket_mb=`,
+    ...).  The yaml's NESTEROV key is ignored, as the reference ignores it.  `adamw` reads LR, WEIGHT_DECAY and, where the config has
+    them, BETA1 / BETA2 / EPS (torch's defaults 0.9 / 0.999 / 1e-8 where it has not)."""
     key = optim_cfg.OPTIMIZER
     if key in ("sgd", "sgd_fc"):
         groups = None
@@ -74,6 +88,11 @@ def build_optimizer(model, optim_cfg, *, max_norm=0.0, amp=False, **flat_kwargs)
             groups.append({"params": list(model.classifier.parameters()), "lr": optim_cfg.LR * 10})
         return FlatOptimizer(model, groups, lr=optim_cfg.LR, momentum=optim_cfg.MOMENTUM, weight_decay=optim_cfg.WEIGHT_DECAY,
                              max_norm=max_norm, amp=amp, **flat_kwargs)
+    if key == "adamw":
+        get = optim_cfg.get if hasattr(optim_cfg, "get") else (lambda k, d: getattr(optim_cfg, k, d))
+        return FlatOptimizer(model, None, kind="adamw", lr=optim_cfg.LR, weight_decay=optim_cfg.WEIGHT_DECAY,
+                             betas=(get("BETA1", 0.9), get("BETA2", 0.999)), eps=get("EPS", 1e-8), max_norm=max_norm, amp=amp,
+                             **flat_kwargs)
     if key == "adam":
         return torch.optim.Adam(model.parameters(), lr=optim_cfg.LR, weight_decay=optim_cfg.WEIGHT_DECAY)
     if key == "adamW":
