@@ -143,6 +143,8 @@ extern "C" int ts_kernel_hash(const int32_t *coords, int64_t n, const int32_t *o
 }
 
 // ---------------------------------------------------------------- K3-K5: hash query
+// Contract for the key -1 (TS_EMPTY_KEY, the table's empty marker; no 60-bit FNV value equals it): a reference key -1 is not
+// inserted and a query key -1 is a miss - it is never found, whatever the references hold (tests/test_gpu_rulebook_edges.py).
 __global__ __launch_bounds__(256) void table_insert_keys_kernel(TsTable t, const int64_t *__restrict__ keys,
                                                                 int64_t n) {
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;

@@ -136,8 +136,9 @@ __global__ __launch_bounds__(256) void seg_min3_kernel(const float *__restrict__
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t step = (int64_t)gridDim.x * blockDim.x;
   for (; i < n; i += step) {
-    const int b = (int)seg[i];
-    if (b < 0 || b >= n_seg) continue;
+    const int64_t b64 = seg[i];
+    if (b64 < 0 || b64 >= n_seg) continue;      // (tested on the int64: an id of 2^32 must not alias segment 0)
+    const int b = (int)b64;
     const float *p = pts + i * pstride;
 #pragma unroll
     for (int d = 0; d < 3; ++d) {
