@@ -418,7 +418,7 @@ def build_kmap(in_coords, out_coords, offsets, want_pairs=True, want_inverse=Fal
 
 
 def gather_sum_kernel_name(c, k, half=False):
-    """The kernel ts_conv_gather_sum[_f16] launches for rows of c channels and K = k offsets (csrc/conv_pairs{,_h}.hip)."""
+    """The kernel ts_conv_gather_sum[_f16] launches for rows of c channels and K = k offsets (csrc/conv_pass2.hip, pass2_list_applies)."""
     import os
     lists = not options.gather_positions
     kt = k if k in (8, 27) else 0

@@ -248,16 +248,14 @@ static int block_conv(const void *feat, int64_t n_feat_rows, int32_t c_in, const
   // pass 2 of this convolution, with the tail where it applies
   auto pass2 = [&](const void *zz, const int32_t *table, int32_t kk, int64_t zrows) -> int {
     if (tail && tail_out) {
-      const int rc = half ? ts_conv_gather_sum_f16_epi(zz, c_out, table, kk, n_out, zrows, tail_out, *tail, stream)
-                          : ts_conv_gather_sum_epi((const float *)zz, c_out, table, kk, n_out, zrows, (float *)tail_out, *tail, stream);
+      const int rc = ts_conv_pass2(half, zz, c_out, table, kk, n_out, zrows, tail_out, nullptr, nullptr, tail, stream);
       if (rc == TS_OK) {
         if (tail_done) *tail_done = true;
         return TS_OK;
       }
       if (rc != TS_ERR_UNSUPPORTED) return rc;
     }
-    return half ? ts_conv_gather_sum_f16(zz, c_out, table, kk, n_out, zrows, conv_out, stream)
-                : ts_conv_gather_sum((const float *)zz, c_out, table, kk, n_out, zrows, (float *)conv_out, stream);
+    return ts_conv_pass2(half, zz, c_out, table, kk, n_out, zrows, conv_out, nullptr, nullptr, nullptr, stream);
   };
   if (o.natural) {
     // 1x1x1 convolution on the identity rulebook: the pair GEMM's rows are the result rows
@@ -398,7 +396,7 @@ extern "C" int ts_conv_block_eval(const void *feat, int64_t n_feat_rows, int32_t
   void *z = p;
   p += blk_align((size_t)n_pairs * cmax * es);
   void *conv_out = p;
-  // the elementwise tail rides on pass 2 where the convolution ends in its list form (csrc/conv_pairs*.hip: one launch and one
+  // the elementwise tail rides on pass 2 where the convolution ends in its list form (csrc/conv_pass2.hip: one launch and one
   // round trip of the convolution output less; TASEG_EVAL_TAIL_IN_PASS2=0 keeps the separate pass)
   const bool tail_in_pass2 = ts_get_option(TS_OPT_EVAL_TAIL_SEPARATE) == 0;
   const TsGatherEpilogue tail = {mean, invstd, bn_weight, bn_bias, residual, relu ? 1 : 0};
@@ -564,12 +562,8 @@ extern "C" int ts_conv_block_backward(const void *grad_out, const uint8_t *mask,
     }
     if (!cp->rows && !fused) {
       ProfScope ps(1, stream, plan_z_rows(cp), 0, c_in, cp->groups, (double)n_dgrad_rows, es_d, side_bytes);
-      if (half)
-        TS_TRY(ts_conv_gather_sum_f16_ex(z, c_in, cp->pos, cp->groups, n_dgrad_rows, cp->m_pad, grad_feat, ride ? &job : nullptr,
-                                         addend, stream));
-      else
-        TS_TRY(ts_conv_gather_sum_ex((const float *)z, c_in, cp->pos, cp->groups, n_dgrad_rows, cp->m_pad, (float *)grad_feat,
-                                     ride ? &job : nullptr, (const float *)addend, stream));
+      TS_TRY(ts_conv_pass2(half, z, c_in, cp->pos, cp->groups, n_dgrad_rows, cp->m_pad, grad_feat, ride ? &job : nullptr, addend, nullptr,
+                           stream));
     }
   } else if (grad_feat && o.natural) {
     // identity rulebook: the rows of the product through W^T are the input gradient's rows
@@ -594,12 +588,7 @@ extern "C" int ts_conv_block_backward(const void *grad_out, const uint8_t *mask,
     }
     {
       ProfScope ps(1, stream, (double)n_pairs, 0, c_in, K, (double)n_dgrad_rows, es_d, side_bytes);
-      if (half)
-        TS_TRY(ts_conv_gather_sum_f16_ex(z, c_in, pos_dgrad, K, n_dgrad_rows, n_pairs, grad_feat, ride ? &job : nullptr,
-                                         addend, stream));
-      else
-        TS_TRY(ts_conv_gather_sum_ex((const float *)z, c_in, pos_dgrad, K, n_dgrad_rows, n_pairs, (float *)grad_feat,
-                                     ride ? &job : nullptr, (const float *)addend, stream));
+      TS_TRY(ts_conv_pass2(half, z, c_in, pos_dgrad, K, n_dgrad_rows, n_pairs, grad_feat, ride ? &job : nullptr, addend, nullptr, stream));
     }
   }
   if (det && !ride && !side_on) TS_TRY(ts_wgrad_reduce(job, stream));

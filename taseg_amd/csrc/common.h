@@ -246,7 +246,7 @@ extern thread_local TsPlanesHint g_ts_planes_hint;   // one-shot: set by ts_conv
 // + the finish of a three-group plan inside the product (fin != NULL, rows == NULL, groups == 3): two launches - the groups
 // without the centre offset write their Z' rows, then the centre group's tiles (every row is in one: a row is its own centre
 // neighbour) add the other groups' rows of their output rows in pass 2's order, the addend, and store the RESULT rows - no pass 2,
-// a third of Z' never written; the same bits as class GEMM + ts_conv_gather_sum_ex.
+// a third of Z' never written; the same bits as class GEMM + ts_conv_pass2.
 struct TsClassFinish {
   const int32_t *pos;        // [3][n] position table of the plan
   int64_t n;                 // output rows
@@ -265,24 +265,21 @@ int ts_conv_class_gemm_f16_ex(const void *feat, int32_t c_red, const void *w, in
 // Library-internal forms used by the fused block calls (csrc/block.hip): the gather-sum pass can form the ordered sum
 // of the weight-gradient partials on the side (saves the reduce launch), and the atomic form of the weight gradient
 // can be told that its output is already zero.
+// Pass 2 (csrc/conv_pass2.hip), fp32 rows or (half != 0) half rows: ts_conv_gather_sum[_f16] with
+// side (optional): the ordered sum of the weight-gradient partials rides on the launch;
 // addend (optional, [n_rows, c] like out): out = (sum_k z rows) + addend - the gradient that reaches the block's input
-// along its other path (a residual connection) lands in the same store instead of a separate add launch
-int ts_conv_gather_sum_ex(const float *z, int32_t c, const int32_t *pos, int32_t K, int64_t n_rows, int64_t n_pairs,
-                          float *out, const TsWgradReduce *side, const float *addend, ts_stream_t stream);
-int ts_conv_gather_sum_f16_ex(const void *z, int32_t c, const int32_t *pos, int32_t K, int64_t n_rows, int64_t n_pairs,
-                              void *out, const TsWgradReduce *side, const void *addend, ts_stream_t stream);
-// Pass 2 with the evaluation block's elementwise tail in its store: out = act((sum - mean) invstd w + b [+ residual]) - the
-// arithmetic of bn_act_fwd_kernel on the fp32 sum (half storage: the sum is not rounded to half in between).  Returns
-// TS_ERR_UNSUPPORTED (and launches nothing) where the list form of pass 2 does not apply: the caller then runs the two launches.
+// along its other path (a residual connection) lands in the same store instead of a separate add launch;
+// epi (optional; then side == addend == NULL): the evaluation block's elementwise tail in the store,
+// out = act((sum - mean) invstd w + b [+ residual]) - the arithmetic of bn_act_fwd_kernel on the fp32 sum (half storage: the sum is
+// not rounded to half in between).  With epi the call returns TS_ERR_UNSUPPORTED (and launches nothing) where the list form of
+// pass 2 does not apply: the caller then runs the two launches.
 struct TsGatherEpilogue {
   const float *mean, *invstd, *w, *b;      // [c]
   const void *residual;                    // optional [n_rows, c]
   int relu;
 };
-int ts_conv_gather_sum_epi(const float *z, int32_t c, const int32_t *pos, int32_t K, int64_t n_rows, int64_t n_pairs, float *out,
-                           const TsGatherEpilogue &epi, ts_stream_t stream);
-int ts_conv_gather_sum_f16_epi(const void *z, int32_t c, const int32_t *pos, int32_t K, int64_t n_rows, int64_t n_pairs, void *out,
-                               const TsGatherEpilogue &epi, ts_stream_t stream);
+int ts_conv_pass2(int32_t half, const void *z, int32_t c, const int32_t *pos, int32_t K, int64_t n_rows, int64_t n_pairs, void *out,
+                  const TsWgradReduce *side, const void *addend, const TsGatherEpilogue *epi, ts_stream_t stream);
 int ts_conv_wgrad_ex(const float *a_feat, int32_t c_a, const float *b_feat, int32_t c_b, const int32_t *nbmaps,
                      const int32_t *nboffs, int32_t K, int32_t col_a, int64_t n_pairs, float *grad_kernel,
                      int32_t already_zero, ts_stream_t stream);

@@ -7,9 +7,9 @@
 //           stays L2 resident.  No flops are spent on missing neighbours, no padding per (tile, offset),
 //           every workgroup does the same amount of work.  Tiles that straddle an offset boundary
 //           (<= K - 1 of them) run once per offset with the foreign rows zeroed.
-//   pass 2  gather_sum_kernel   Y[j, :] = sum_k Z[pos[k, j], :]  - a streaming reduction: for a fixed k the
+//   pass 2  csrc/conv_pass2.hip Y[j, :] = sum_k Z[pos[k, j], :]  - a streaming reduction: for a fixed k the
 //           rows Z[pos[k, j]] of consecutive j are consecutive in memory.  Deterministic (k ascending),
-//           no atomics, every output row written once.
+//           no atomics, every output row written once.  One kernel family for fp32 and half rows, not in this file.
 //
 // Reference algorithm: torchsparse backend/convolution/convolution_cuda.cu:101-164 runs, per offset, a
 // gather kernel, a cuBLAS GEMM and a read-modify-write scatter kernel (3 K launches, host-synchronised).
@@ -739,225 +739,6 @@ extern "C" int ts_conv_pair_gemm(const float *feat, int64_t n_rows, int32_t c_in
   if (c_out % 96 == 0) return TS_PG(96, 2);  // 96 / 192 / 384 channels: three 16-col blocks per wave, no padding
   return TS_PG(128, 2);
 #undef TS_PG
-}
-
-// ------------------------------------------------------------------------------------- pass 2
-// KT > 0: kernel volume known at compile time (27, 8): all K position loads are issued first, then all row
-// loads - up to K independent 16-byte loads in flight per lane.  KT == 0: generic loop.
-// every Z row is read exactly once: non-temporal loads keep it out of the way of the position table and of the next
-// kernel's operands in L2 (step 19.33 -> 19.10 ms)
-typedef float ts_f32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ float4 ts_zload(const float4 *p) {
-  const ts_f32x4 v = __builtin_nontemporal_load((const ts_f32x4 *)p);
-  return make_float4(v[0], v[1], v[2], v[3]);
-}
-#define TS_ZLOAD(ptr) ts_zload(ptr)
-template <int VEC, int KT>
-__global__ __launch_bounds__(256) void gather_sum_kernel(const float *__restrict__ Z, int C,
-                                                         const int *__restrict__ pos, int K, int64_t n,
-                                                         int64_t n_pairs, float *__restrict__ out,
-                                                         TsWgradReduce side, const float *__restrict__ addend) {
-  const int cv = C / VEC;
-  const int64_t total = n * cv;
-  int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int64_t step = (int64_t)gridDim.x * blockDim.x;
-  // side job (common.h): the ordered sum of the weight-gradient partials of the launch before this one
-  for (int64_t i = e; i < (int64_t)side.K * side.cacb4; i += step) ts_wgrad_reduce_one(side, i);
-  for (; e < total; e += step) {
-    const int64_t j = e / cv;
-    const int c = (int)(e - j * cv) * VEC;
-    float acc[VEC];
-#pragma unroll
-    for (int v = 0; v < VEC; ++v) acc[v] = 0.f;
-    if (KT > 0 && VEC == 4) {
-      int p[KT > 0 ? KT : 1];
-#pragma unroll
-      for (int k = 0; k < KT; ++k) p[k] = pos[(int64_t)k * n + j];
-      float4 f[KT > 0 ? KT : 1];
-#pragma unroll
-      for (int k = 0; k < KT; ++k) {
-        f[k] = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (p[k] >= 0 && p[k] < n_pairs) f[k] = TS_ZLOAD((const float4 *)(Z + (int64_t)p[k] * C + c));
-      }
-#pragma unroll
-      for (int k = 0; k < KT; ++k) {  // k ascending: fixed summation order
-        acc[0] += f[k].x;
-        acc[1 % VEC] += f[k].y;
-        acc[2 % VEC] += f[k].z;
-        acc[3 % VEC] += f[k].w;
-      }
-    } else {
-#pragma unroll 4
-      for (int k = 0; k < K; ++k) {
-        const int p = pos[(int64_t)k * n + j];
-        if (p >= 0 && p < n_pairs) {
-          if (VEC == 4) {
-            const float4 f = *(const float4 *)(Z + (int64_t)p * C + c);
-            acc[0] += f.x;
-            acc[1 % VEC] += f.y;
-            acc[2 % VEC] += f.z;
-            acc[3 % VEC] += f.w;
-          } else {
-            acc[0] += Z[(int64_t)p * C + c];
-          }
-        }
-      }
-    }
-    if (addend) {          // one add per element after the sum over the offsets: the same bits as a separate a + b
-      if (VEC == 4) {
-        const float4 a = *(const float4 *)(addend + j * C + c);
-        acc[0] += a.x;
-        acc[1 % VEC] += a.y;
-        acc[2 % VEC] += a.z;
-        acc[3 % VEC] += a.w;
-      } else {
-        acc[0] += addend[j * C + c];
-      }
-    }
-    if (VEC == 4) {
-      *(float4 *)(out + j * C + c) = make_float4(acc[0], acc[1 % VEC], acc[2 % VEC], acc[3 % VEC]);
-    } else {
-      out[j * C + c] = acc[0];
-    }
-  }
-}
-
-// Pass 2 with the live positions of a row compacted in LDS first: a workgroup owns 256 / (C / 4) whole rows; half-waves
-// load the K positions of a row (lane = offset), ballot the live ones and leave them - ascending offset, the fixed
-// summation order - as a list in LDS; then a lane walks its row's list with R independent 16-byte loads per round.
-// Against gather_sum_kernel<4, K>: one position load per lane instead of K, only live rows requested, R + a few instead
-// of 5 K registers (8 instead of 3 waves per SIMD).  Same additions in the same order: bit-identical sums.  K <= 32.
-template <int R>
-__global__ __launch_bounds__(256) void gather_list_kernel(const float *__restrict__ Z, int C,
-                                                          const int *__restrict__ pos, int K, int64_t n,
-                                                          int64_t n_pairs, float *__restrict__ out, TsWgradReduce side,
-                                                          const float *__restrict__ addend, int rpw, TsGatherEpilogue epi) {
-  __shared__ int lst[64][33];
-  __shared__ int cnt[64];
-  const int tid = threadIdx.x;
-  {
-    const int64_t e = (int64_t)blockIdx.x * blockDim.x + tid, step = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = e; i < (int64_t)side.K * side.cacb4; i += step) ts_wgrad_reduce_one(side, i);
-  }
-  const int64_t j0 = (int64_t)blockIdx.x * rpw;
-  const int hw = tid >> 5, l = tid & 31;
-  for (int base = 0; base < rpw; base += 8) {          // uniform trip count: the ballot below needs every lane
-    const int r = base + hw;
-    const int64_t j = j0 + r;
-    int p = -1;
-    if (r < rpw && j < n && l < K) p = pos[(int64_t)l * n + j];
-    const bool live = p >= 0 && p < n_pairs;
-    const unsigned long long m64 = __builtin_amdgcn_ballot_w64(live);
-    const unsigned m = (tid & 32) ? (unsigned)(m64 >> 32) : (unsigned)m64;
-    if (live) lst[r][__builtin_popcount(m & ((1u << l) - 1u))] = p;
-    if (l == 0 && r < rpw) cnt[r] = __builtin_popcount(m);
-  }
-  __syncthreads();
-  const int cv = C >> 2;
-  const int r = tid / cv;
-  const int64_t j = j0 + r;
-  if (r >= rpw || j >= n) return;
-  const int c = (tid - r * cv) << 2;
-  const int m = cnt[r];
-  float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-  for (int b = 0; b < m; b += R) {
-    float4 f[R];
-#pragma unroll
-    for (int i = 0; i < R; ++i) {
-      f[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (b + i < m) f[i] = TS_ZLOAD((const float4 *)(Z + (int64_t)lst[r][b + i] * C + c));
-    }
-#pragma unroll
-    for (int i = 0; i < R; ++i) {
-      acc.x += f[i].x;
-      acc.y += f[i].y;
-      acc.z += f[i].z;
-      acc.w += f[i].w;
-    }
-  }
-  if (addend) {
-    const float4 a = *(const float4 *)(addend + j * C + c);
-    acc.x += a.x;
-    acc.y += a.y;
-    acc.z += a.z;
-    acc.w += a.w;
-  }
-  if (epi.mean) {                        // evaluation block: bn_act_fwd_kernel's arithmetic on the sum
-    const float4 m = *(const float4 *)(epi.mean + c), s = *(const float4 *)(epi.invstd + c);
-    const float4 ww = *(const float4 *)(epi.w + c), bb = *(const float4 *)(epi.b + c);
-    acc.x = (acc.x - m.x) * s.x * ww.x + bb.x;
-    acc.y = (acc.y - m.y) * s.y * ww.y + bb.y;
-    acc.z = (acc.z - m.z) * s.z * ww.z + bb.z;
-    acc.w = (acc.w - m.w) * s.w * ww.w + bb.w;
-    if (epi.residual) {
-      const float4 r = *(const float4 *)((const float *)epi.residual + j * C + c);
-      acc.x += r.x; acc.y += r.y; acc.z += r.z; acc.w += r.w;
-    }
-    if (epi.relu) {
-      acc.x = fmaxf(acc.x, 0.f); acc.y = fmaxf(acc.y, 0.f); acc.z = fmaxf(acc.z, 0.f); acc.w = fmaxf(acc.w, 0.f);
-    }
-  }
-  *(float4 *)(out + j * C + c) = acc;
-}
-
-static int launch_gather_list(const float *z, int c, const int *pos, int K, int64_t n_rows, int64_t n_pairs, float *out,
-                              const TsWgradReduce &side, const float *addend, hipStream_t stream,
-                              const TsGatherEpilogue &epi = TsGatherEpilogue{nullptr, nullptr, nullptr, nullptr, nullptr, 0}) {
-  const int cv = c >> 2, rpw = 256 / cv;
-  const unsigned grid = (unsigned)ts_cdiv(n_rows, rpw);
-  // R = 4 / 8 / 12 / 16 measured within 3 % of each other on every layer (profiles/r02_v9_gather_forms_probe.txt)
-  gather_list_kernel<8><<<grid, 256, 0, stream>>>(z, c, pos, K, n_rows, n_pairs, out, side, addend, rpw, epi);
-  TS_CHECK_LAUNCH("conv_gather_sum (list)");
-  return TS_OK;
-}
-
-extern "C" int ts_conv_gather_sum(const float *z, int32_t c, const int32_t *pos, int32_t K, int64_t n_rows,
-                                  int64_t n_pairs, float *out, ts_stream_t stream_) {
-  return ts_conv_gather_sum_ex(z, c, pos, K, n_rows, n_pairs, out, nullptr, nullptr, stream_);
-}
-
-int ts_conv_gather_sum_ex(const float *z, int32_t c, const int32_t *pos, int32_t K, int64_t n_rows, int64_t n_pairs,
-                          float *out, const TsWgradReduce *side_job, const float *addend, ts_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  TsWgradReduce side = {};
-  if (side_job) side = *side_job;
-  TS_REQUIRE(!side_job || (n_rows > 0 && side.part && side.dW && side.nboffs && side.chunk > 0 &&
-                           ((((uintptr_t)side.part) | ((uintptr_t)side.dW)) & 15) == 0),
-             TS_ERR_INVALID_ARGUMENT, "ts_conv_gather_sum: bad side job");
-  TS_REQUIRE(c > 0 && K > 0 && n_rows >= 0 && n_pairs >= 0, TS_ERR_INVALID_ARGUMENT, "ts_conv_gather_sum: bad sizes");
-  if (n_rows == 0) return TS_OK;
-  TS_REQUIRE(pos && out && (z || n_pairs == 0), TS_ERR_INVALID_ARGUMENT, "ts_conv_gather_sum: null pointer");
-  const bool vec = (c % 4 == 0) && ((((uintptr_t)z) & 15) == 0) && ((((uintptr_t)out) & 15) == 0);
-  // default: live positions compacted in LDS first (gather_list_kernel); TASEG_GATHER_POSITIONS=1 in the environment
-  // keeps the K-register form (A/B runs)
-  const bool k_registers = ts_get_option(TS_OPT_GATHER_POSITIONS) != 0;
-  if (vec && K <= 32 && c >= 16 && c <= 1024 && !k_registers && g_ts_conv_impl != 1)
-    return launch_gather_list(z, c, pos, K, n_rows, n_pairs, out, side, addend, stream);
-  if (vec) {
-    int grid = (int)std::min<int64_t>(ts_cdiv(n_rows * (c / 4), 256), 1 << 20);
-    if (K == 27)
-      gather_sum_kernel<4, 27><<<grid, 256, 0, stream>>>(z, c, pos, K, n_rows, n_pairs, out, side, addend);
-    else if (K == 8)
-      gather_sum_kernel<4, 8><<<grid, 256, 0, stream>>>(z, c, pos, K, n_rows, n_pairs, out, side, addend);
-    else
-      gather_sum_kernel<4, 0><<<grid, 256, 0, stream>>>(z, c, pos, K, n_rows, n_pairs, out, side, addend);
-  } else {
-    int grid = (int)std::min<int64_t>(ts_cdiv(n_rows * c, 256), 1 << 20);
-    gather_sum_kernel<1, 0><<<grid, 256, 0, stream>>>(z, c, pos, K, n_rows, n_pairs, out, side, addend);
-  }
-  TS_CHECK_LAUNCH("conv_gather_sum");
-  return TS_OK;
-}
-
-int ts_conv_gather_sum_epi(const float *z, int32_t c, const int32_t *pos, int32_t K, int64_t n_rows, int64_t n_pairs, float *out,
-                           const TsGatherEpilogue &epi, ts_stream_t stream_) {
-  const bool k_registers = ts_get_option(TS_OPT_GATHER_POSITIONS) != 0;
-  const bool vec = (c % 4 == 0) && ((((uintptr_t)z) | ((uintptr_t)out) | ((uintptr_t)epi.residual) | ((uintptr_t)epi.mean) |
-                                     ((uintptr_t)epi.invstd) | ((uintptr_t)epi.w) | ((uintptr_t)epi.b)) & 15) == 0;
-  if (!(vec && K > 0 && K <= 32 && c >= 16 && c <= 1024 && !k_registers && g_ts_conv_impl != 1 && n_rows > 0 && z && pos && out &&
-        epi.mean && epi.invstd && epi.w && epi.b))
-    return TS_ERR_UNSUPPORTED;
-  return launch_gather_list(z, c, pos, K, n_rows, n_pairs, out, TsWgradReduce{}, nullptr, (hipStream_t)stream_, epi);
 }
 
 // ------------------------------------------------------------------------------------- weight gradient

@@ -6,7 +6,8 @@
 //                            the reduction dimension for forward (W16T) and dgrad (W16))
 //   pair_gemm_h_kernel       Z[p, :] = X[g_p, :] @ W_k  with v_mfma_f32_16x16x32_f16 (16x the f32 MFMA rate: the
 //                            kernel is bound by the gathered-row and Z traffic, half of the fp32 path's)
-//   gather_sum_h_kernel      Y[j, :] = sum_k Z[pos[k, j], :], fp32 accumulation, half in / half out
+//   pass 2                   Y[j, :] = sum_k Z[pos[k, j], :], fp32 accumulation, half in / half out: csrc/conv_pass2.hip, the
+//                            kernel family it shares with the fp32 rows
 // Tiling = pair_gemm_fast_kernel (128 pairs x BN columns per workgroup, tiles cut per offset, 32-deep slices,
 // double-buffered LDS, one register stage).  Lane l of the MFMA holds A[row l & 15][k = 8 (l >> 4) + j] and
 // B[k = 8 (l >> 4) + j][col l & 15], j = 0..7: with both operands stored row-major in the reduction index every
@@ -303,179 +304,6 @@ static int pair_gemm_f16_any(const void *feat, int64_t n_rows, int32_t c_red, co
   if (c_out % 64 == 0) return TS_PH(64, 2);
   return TS_PH(32, 4);
 #undef TS_PH
-}
-
-// ------------------------------------------------------------------------------------- pass 2, half storage
-template <int KT>
-__global__ __launch_bounds__(256) void gather_sum_h_kernel(const _Float16 *__restrict__ Z, int C,
-                                                           const int *__restrict__ pos, int K, int64_t n_rows,
-                                                           _Float16 *__restrict__ out, TsWgradReduce side,
-                                                           const _Float16 *__restrict__ addend) {
-  const int c8n = C >> 3;
-  int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int64_t total = n_rows * c8n, step = (int64_t)gridDim.x * blockDim.x;
-  // side job (common.h): the ordered sum of the weight-gradient partials of the launch before this one
-  for (int64_t i = e; i < (int64_t)side.K * side.cacb4; i += step) ts_wgrad_reduce_one(side, i);
-  for (; e < total; e += step) {
-    const int64_t j = e / c8n;
-    const int c8 = (int)(e - j * c8n) << 3;
-    float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    if (KT > 0) {
-      int p[KT > 0 ? KT : 1];
-#pragma unroll
-      for (int k = 0; k < KT; ++k) p[k] = pos[(int64_t)k * n_rows + j];
-      h8 v[KT > 0 ? KT : 1];
-#pragma unroll
-      for (int k = 0; k < KT; ++k)
-        v[k] = p[k] >= 0 ? __builtin_nontemporal_load((const h8 *)(Z + (int64_t)p[k] * C + c8)) : (h8){0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-      for (int k = 0; k < KT; ++k)
-#pragma unroll
-        for (int i = 0; i < 8; ++i) acc[i] += (float)v[k][i];
-    } else {
-      for (int k = 0; k < K; ++k) {
-        const int p = pos[(int64_t)k * n_rows + j];
-        if (p >= 0) {
-          const h8 v = *(const h8 *)(Z + (int64_t)p * C + c8);
-#pragma unroll
-          for (int i = 0; i < 8; ++i) acc[i] += (float)v[i];
-        }
-      }
-    }
-    if (addend) {
-      const h8 a = *(const h8 *)(addend + j * C + c8);
-#pragma unroll
-      for (int i = 0; i < 8; ++i) acc[i] += (float)a[i];
-    }
-    h8 o;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) o[i] = (_Float16)acc[i];
-    *(h8 *)(out + j * C + c8) = o;
-  }
-}
-
-// The list form of pass 2 (gather_list_kernel, conv_pairs.hip) for half rows: a workgroup owns 256 / (C / 8) whole rows,
-// half-waves compact the live positions of a row into LDS (lane = offset, ballot), a lane walks its row's list with R
-// independent 16-byte loads per round.  float32 sums in ascending offset order, one rounding: the bits of
-// gather_sum_h_kernel.  K <= 32, C >= 64.
-template <int R>
-__global__ __launch_bounds__(256) void gather_list_h_kernel(const _Float16 *__restrict__ Z, int C,
-                                                            const int *__restrict__ pos, int K, int64_t n,
-                                                            _Float16 *__restrict__ out, TsWgradReduce side,
-                                                            const _Float16 *__restrict__ addend, int rpw, TsGatherEpilogue epi) {
-  __shared__ int lst[64][33];
-  __shared__ int cnt[64];
-  const int tid = threadIdx.x;
-  {
-    const int64_t e = (int64_t)blockIdx.x * blockDim.x + tid, step = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = e; i < (int64_t)side.K * side.cacb4; i += step) ts_wgrad_reduce_one(side, i);
-  }
-  const int64_t j0 = (int64_t)blockIdx.x * rpw;
-  const int hw = tid >> 5, l = tid & 31;
-  for (int base = 0; base < rpw; base += 8) {          // uniform trip count: the ballot below needs every lane
-    const int r = base + hw;
-    const int64_t j = j0 + r;
-    int p = -1;
-    if (r < rpw && j < n && l < K) p = pos[(int64_t)l * n + j];
-    const bool live = p >= 0;
-    const unsigned long long m64 = __builtin_amdgcn_ballot_w64(live);
-    const unsigned m = (tid & 32) ? (unsigned)(m64 >> 32) : (unsigned)m64;
-    if (live) lst[r][__builtin_popcount(m & ((1u << l) - 1u))] = p;
-    if (l == 0 && r < rpw) cnt[r] = __builtin_popcount(m);
-  }
-  __syncthreads();
-  const int c8n = C >> 3;
-  const int r = tid / c8n;
-  const int64_t j = j0 + r;
-  if (r >= rpw || j >= n) return;
-  const int c8 = (tid - r * c8n) << 3;
-  const int m = cnt[r];
-  float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  for (int b = 0; b < m; b += R) {
-    h8 v[R];
-#pragma unroll
-    for (int i = 0; i < R; ++i)
-      v[i] = b + i < m ? __builtin_nontemporal_load((const h8 *)(Z + (int64_t)lst[r][b + i] * C + c8)) : (h8){0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-    for (int i = 0; i < R; ++i)
-#pragma unroll
-      for (int q = 0; q < 8; ++q) acc[q] += (float)v[i][q];
-  }
-  if (addend) {
-    const h8 a = *(const h8 *)(addend + j * C + c8);
-#pragma unroll
-    for (int q = 0; q < 8; ++q) acc[q] += (float)a[q];
-  }
-  if (epi.mean) {                        // evaluation block: bn_act_fwd_h_kernel's arithmetic on the fp32 sum
-    h8 r;
-    if (epi.residual) r = *(const h8 *)((const _Float16 *)epi.residual + j * C + c8);
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-      float v = (acc[q] - epi.mean[c8 + q]) * epi.invstd[c8 + q] * epi.w[c8 + q] + epi.b[c8 + q];
-      if (epi.residual) v += (float)r[q];
-      if (epi.relu) v = fmaxf(v, 0.f);
-      acc[q] = v;
-    }
-  }
-  h8 o;
-#pragma unroll
-  for (int q = 0; q < 8; ++q) o[q] = (_Float16)acc[q];
-  *(h8 *)(out + j * C + c8) = o;
-}
-
-extern "C" int ts_conv_gather_sum_f16(const void *z, int32_t c, const int32_t *pos, int32_t K, int64_t n_rows,
-                                      int64_t n_pairs, void *out, ts_stream_t stream_) {
-  return ts_conv_gather_sum_f16_ex(z, c, pos, K, n_rows, n_pairs, out, nullptr, nullptr, stream_);
-}
-
-int ts_conv_gather_sum_f16_ex(const void *z, int32_t c, const int32_t *pos, int32_t K, int64_t n_rows, int64_t n_pairs,
-                              void *out, const TsWgradReduce *side_job, const void *addend, ts_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  TsWgradReduce side = {};
-  if (side_job) side = *side_job;
-  TS_REQUIRE(!side_job || (n_rows > 0 && side.part && side.dW && side.nboffs && side.chunk > 0 &&
-                           ((((uintptr_t)side.part) | ((uintptr_t)side.dW)) & 15) == 0),
-             TS_ERR_INVALID_ARGUMENT, "ts_conv_gather_sum_f16: bad side job");
-  TS_REQUIRE(c > 0 && (c & 7) == 0 && K > 0 && n_rows >= 0 && n_pairs >= 0, TS_ERR_INVALID_ARGUMENT,
-             "ts_conv_gather_sum_f16: bad sizes (C must be a multiple of 8)");
-  if (n_rows == 0) return TS_OK;
-  TS_REQUIRE(pos && out && (z || n_pairs == 0), TS_ERR_INVALID_ARGUMENT, "ts_conv_gather_sum_f16: null pointer");
-  TS_REQUIRE(((((uintptr_t)z) | ((uintptr_t)out)) & 15) == 0, TS_ERR_INVALID_ARGUMENT,
-             "ts_conv_gather_sum_f16: pointers must be 16-byte aligned");
-  const _Float16 *zz = (const _Float16 *)z;
-  // default: live positions compacted in LDS first; TASEG_GATHER_POSITIONS=1 keeps the K-register form (A/B runs)
-  const bool k_registers = ts_get_option(TS_OPT_GATHER_POSITIONS) != 0;
-  if (K <= 32 && c >= 64 && c <= 2048 && !k_registers && g_ts_conv_impl != 1) {   // 32 channels: 64 rows per workgroup, the list build costs more than it saves
-    const int rpw = 256 / (c >> 3);
-    gather_list_h_kernel<8><<<(unsigned)ts_cdiv(n_rows, rpw), 256, 0, stream>>>(zz, c, pos, K, n_rows, (_Float16 *)out, side,
-                                                                                (const _Float16 *)addend, rpw,
-                                                                                TsGatherEpilogue{nullptr, nullptr, nullptr, nullptr, nullptr, 0});
-    TS_CHECK_LAUNCH("ts_conv_gather_sum_f16 (list)");
-    return TS_OK;
-  }
-  const int grid = (int)std::min<int64_t>(ts_cdiv(n_rows * (c / 8), 256), 1 << 20);
-  if (K == 27)
-    gather_sum_h_kernel<27><<<grid, 256, 0, stream>>>(zz, c, pos, K, n_rows, (_Float16 *)out, side, (const _Float16 *)addend);
-  else if (K == 8)
-    gather_sum_h_kernel<8><<<grid, 256, 0, stream>>>(zz, c, pos, K, n_rows, (_Float16 *)out, side, (const _Float16 *)addend);
-  else
-    gather_sum_h_kernel<0><<<grid, 256, 0, stream>>>(zz, c, pos, K, n_rows, (_Float16 *)out, side, (const _Float16 *)addend);
-  TS_CHECK_LAUNCH("ts_conv_gather_sum_f16");
-  return TS_OK;
-}
-
-int ts_conv_gather_sum_f16_epi(const void *z, int32_t c, const int32_t *pos, int32_t K, int64_t n_rows, int64_t n_pairs, void *out,
-                               const TsGatherEpilogue &epi, ts_stream_t stream_) {
-  const bool k_registers = ts_get_option(TS_OPT_GATHER_POSITIONS) != 0;
-  if (!(K > 0 && K <= 32 && c >= 64 && c <= 2048 && (c & 7) == 0 && !k_registers && g_ts_conv_impl != 1 && n_rows > 0 && z && pos &&
-        out && epi.mean && epi.invstd && epi.w && epi.b &&
-        ((((uintptr_t)z) | ((uintptr_t)out) | ((uintptr_t)epi.residual)) & 15) == 0))
-    return TS_ERR_UNSUPPORTED;
-  const int rpw = 256 / (c >> 3);
-  gather_list_h_kernel<8><<<(unsigned)ts_cdiv(n_rows, rpw), 256, 0, (hipStream_t)stream_>>>(
-      (const _Float16 *)z, c, pos, K, n_rows, (_Float16 *)out, TsWgradReduce{}, nullptr, rpw, epi);
-  TS_CHECK_LAUNCH("ts_conv_gather_sum_f16 (list + evaluation tail)");
-  return TS_OK;
 }
 
 // ------------------------------------------------------------------------------------- weight gradient, half inputs

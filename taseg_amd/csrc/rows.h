@@ -1,4 +1,4 @@
-// What the row kernels of csrc/cylinder.hip, csrc/spvcnn.hip, csrc/rpvnet.hip and csrc/point_tail.h share: 16-byte accesses per lane,
+// What the row kernels of csrc/cylinder.hip, csrc/spvcnn.hip, csrc/rpvnet.hip, csrc/point_tail.h and csrc/conv_pass2.hip share: 16-byte accesses per lane,
 // one group of c / V lanes per row, voxel or piece, blocks of 256 threads.  Templates and inline functions only - every file that
 // includes this keeps its own -ffp-contract setting (csrc/build.py).
 #pragma once

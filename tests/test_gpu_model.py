@@ -184,7 +184,7 @@ def test_eval_block_call_equals_the_module_chain(g_minkunet, monkeypatch, amp):
 
 
 def test_eval_tail_in_pass_2_has_the_bits_of_the_separate_pass(tmp_path):
-    """ts_conv_block_eval applies the BatchNorm / residual / ReLU tail in the store of pass 2 (TsGatherEpilogue, csrc/conv_pairs*.hip)
+    """ts_conv_block_eval applies the BatchNorm / residual / ReLU tail in the store of pass 2 (TsGatherEpilogue, csrc/conv_pass2.hip)
     where the convolution ends in its list form.  Same arithmetic as the separate elementwise pass: fp32 logits of a whole evaluation
     pass are bit-equal with TASEG_EVAL_TAIL_IN_PASS2=0 (the switch is read once per process: two child processes); half storage rounds
     once instead of twice and stays within half precision of it."""

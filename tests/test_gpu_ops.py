@@ -1105,37 +1105,55 @@ def test_fused_loss_fails_loudly_on_a_label_outside_the_classes():
 
 
 @pytest.mark.parametrize("k,n,c", [(27, 10007, 96), (27, 4099, 128), (27, 257, 256), (8, 5003, 64), (27, 3001, 32), (27, 1500, 20),
-                                   (27, 700, 16), (1, 2000, 96), (27, 9, 1024)])
+                                   (27, 700, 16), (1, 2000, 96), (27, 9, 1024),
+                                   # the edges of the rules that pick the form (csrc/conv_pass2.hip): the half list form's first width and
+                                   # the width below it; its last width (fp32 above its own range: register form); fp32 just above its
+                                   # list range; the last K of the list form and the generic-K register form behind it; one full
+                                   # workgroup of 64 rows plus one row at fp32's narrowest list width
+                                   (27, 300, 64), (27, 300, 56), (27, 40, 2048), (27, 40, 1032), (32, 200, 96), (33, 200, 96),
+                                   (8, 65, 16)])
 def test_gather_sum_list_form_gives_the_bits_of_the_register_form(B, k, n, c):
     """Pass 2 of the convolution: gather_list_kernel (live positions compacted in LDS, the default) against
     gather_sum_kernel (K position registers per lane; what ts_set_conv_impl(1) keeps) - the same additions in the same
     order, so the same bits; rows without any position, positions at both ends of Z, a ragged last workgroup; fp32 rows and
-    (C >= 64) half rows."""
+    (C % 8 == 0) half rows.  Pass 2 only adds, in a stated order, so numpy gives its exact bits: float32 += over k ascending from +0
+    (half rows: the same on the half-rounded Z, then one rounding to half) - every element of both forms is compared with it.
+    Z = 3 + 0.5 randn: every partial and final sum of 1 to 33 terms is a normal number in both types (no subnormal handling enters)
+    and the mantissas are random (another order of the additions shows)."""
     rs = np.random.RandomState(k * 1000 + c)
     p = int(0.3 * k * n) + 1
     pos = np.full((k, n), -1, dtype=np.int32)
     flat = rs.permutation(k * n)[:p]
     pos.reshape(-1)[flat] = rs.permutation(p).astype(np.int32)          # every Z row used exactly once
     pos[:, n // 2] = -1                                                   # a row with no neighbour at all
-    z = T(rs.randn(p, c).astype(np.float32))
+    zz = (3.0 + 0.5 * rs.randn(p, c)).astype(np.float32)
+    zz16 = zz.astype(np.float16)
+    z, zh = T(zz), T(zz16)
     pos_t = T(pos)
     try:
         B.set_conv_impl(1)
         want = B.conv_gather_sum(z, pos_t, n)
-        want_h = B.conv_gather_sum_f16(z.half(), pos_t, n) if c % 8 == 0 else None
+        want_h = B.conv_gather_sum_f16(zh, pos_t, n) if c % 8 == 0 else None
     finally:
         B.set_conv_impl(0)
     got = B.conv_gather_sum(z, pos_t, n)
     assert torch.equal(got, want)
     assert float(got[n // 2].abs().max()) == 0.0 or bool((pos[:, n // 2] >= 0).any())
     ref = np.zeros((n, c), np.float32)
-    zz = z.cpu().numpy()
+    ref16 = np.zeros((n, c), np.float32)
+    z16 = zz16.astype(np.float32)
     for kk in range(k):
         live = pos[kk] >= 0
         ref[live] += zz[pos[kk][live]]
-    close(got, ref, 1e-5)
+        ref16[live] += z16[pos[kk][live]]
+    assert ref.dtype == np.float32 and ref16.dtype == np.float32
+    same(got, ref)
+    same(want, ref)
     if want_h is not None:
-        assert torch.equal(B.conv_gather_sum_f16(z.half(), pos_t, n), want_h)
+        got_h = B.conv_gather_sum_f16(zh, pos_t, n)
+        assert torch.equal(got_h, want_h)
+        same(got_h, ref16.astype(np.float16))
+        same(want_h, ref16.astype(np.float16))
 
 
 @pytest.mark.parametrize("dup", [False, True])
